@@ -15,6 +15,12 @@ enqueued before the host part of step k's decode); the timed region contains
 exactly K forwards and K decodes, the last decode included.  Inputs are synthetic and resident in HBM before the timed
 region; weights are seeded random (no checkpoint / dataset is reachable).
 Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set-up, warm-up, the K timed steps, the line.
+--full adds per-op events in two of the timed steps, the forward-only rate, the
+rooflines and the CPU baseline (as well as --config 1 / 4, --list and --dump-ops).
+--dump-outputs DIR writes the keypoint records of the last timed step as .npy files;
+with the same arguments the inputs are the same in every run.
 """
 import argparse
 import json
@@ -37,8 +43,8 @@ MFMA_PEAK_TFS = 2500.0       # dense fp16/bf16 MFMA
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # 100 steps of ~14 ms: the fill / drain of the software pipeline and the two recorded steps that run alone are 3 % of 20
-    # steps (2,274-2,329 img/s on one box) and 1 % of 100 (2,361-2,368)
+    # 100 steps of ~14 ms: the fill / drain of the software pipeline and (--full) the two recorded steps that run alone are
+    # 3 % of 20 steps (2,274-2,329 img/s on one MI355X) and 1 % of 100 (2,361-2,368)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
@@ -65,7 +71,21 @@ def parse_args():
                     help="BASELINE.json configs[]: 2 (default) = batch 32 fp16 teacher forward + decode, the headline; "
                          "1 = batch 1 fp32 teacher forward + decode (latency form of the same metric); 4 = the "
                          "AttentionStudent at 320x320, dual-head decode.  1 and 4 print their own JSON line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-op events in the first two timed steps (which then run "
+                         "alone), forward-only rate, rooflines, the CPU baseline (unless --no-cpu-baseline); needed by "
+                         "--config 1 / 4, --list and --dump-ops")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the keypoint records of the last step (all ranks) as float32 "
+                         "DIR/{image_ids,num_people,scores,keypoints}.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.config != 2 or args.list or args.dump_ops):
+        ap.error("--config 1 / 4, --list and --dump-ops need --full")
+    if args.dump_outputs and (args.config != 2 or args.list or args.rehearsal):
+        ap.error("--dump-outputs writes the outputs of the default configuration (configs[2])")
+    return args
 
 
 def csrc_sha16():
@@ -441,7 +461,8 @@ def main():
     op_ms = np.zeros(n_ops)
     people = [0]
 
-    n_slots = 2          # per-op events in the first two timed steps only: ~330 marker packets cost ~1 ms of stream time per step
+    # --full: per-op events in the first two timed steps only: ~330 marker packets cost ~1 ms of stream time per step
+    n_slots = 2 if args.full else 0
     for slot in range(n_slots):          # creates the per-op events of every record slot outside the timed region
         eng.forward_record(x, slot)
 
@@ -467,7 +488,7 @@ def main():
     run_steps(args.warmup, False)
     fence()
     t0, c0 = time.perf_counter(), time.process_time()
-    rec = run_steps(args.steps, True)
+    rec = run_steps(args.steps, args.full)
     fence()
     dt = time.perf_counter() - t0
     host_cpu_ms = (time.process_time() - c0) / args.steps * 1e3      # CPU time of this rank's process (all threads) per step
@@ -478,14 +499,18 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec)
 
-    # forward-only and decode-only rates (outside the timed region, for the record)
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(max(2, args.steps // 2)):
-        eng.forward(x)
-    torch.cuda.synchronize(dev)
-    fwd_s = (time.perf_counter() - t1) / max(2, args.steps // 2)
+    fwd_s = None
+    if args.full:
+        # forward-only rate (outside the timed region, for the record)
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(max(2, args.steps // 2)):
+            eng.forward(x)
+        torch.cuda.synchronize(dev)
+        fwd_s = (time.perf_counter() - t1) / max(2, args.steps // 2)
 
     if rank != 0:
         if world > 1:
@@ -493,8 +518,61 @@ def main():
             dist.destroy_process_group()
         return
 
+    value = world * B * args.steps / dt
+    out = {
+        "metric": "images/sec at 640x640 (HRNet-w48 fwd+decode)", "value": round(value, 2), "unit": "images/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16 (fp32 accumulate, fp32 BatchNorm; fp32 NCHW in/out)",
+        "data": "synthetic",
+        "config": {"workload": "configs[2]: batch=%d per GPU, %dx%d, half-wrapper teacher forward + decode of "
+                               "17 keypoint channels, weights %s (seeded random)" % (B, S, S, args.weights),
+                   "batch_per_gpu": B, "people_per_batch_rank0": people[0],
+                   "pipeline": "software-pipelined steps (TeacherPipeline.stream): %s forward(s) in flight on internal streams, "
+                               "decode of batch k-1 beside forward k" % os.environ.get("RTPE_FORWARDS_IN_FLIGHT", "2") + (
+                                   "; the %d recorded steps run alone" % n_slots if n_slots else ""),
+                   **({"forward_only_images_per_sec_per_gpu": round(B / fwd_s, 1)} if args.full else {}),
+                   "host_cpu_ms_per_step": round(host_cpu_ms, 2), "host_threads": host_threads},
+        "roofline": None, "roofline_secondary": None, "build_mode": entry.BUILD_INFO.get("mode"), "cpu_baseline": None,
+    }
+    if args.full:
+        td, roofline = rooflines(args, eng, op_ms / max(1, n_rec), fwd_s)
+        # roofline = the time-dominant kernel family (MFMA-bound 3x3 convs with C >= 96); roofline_secondary = the fused
+        # C = 48 BasicBlock (HBM-bound by SURVEY 8d's layer-fused bytes), the second-largest share of the forward
+        out["roofline"], out["roofline_secondary"] = (td, roofline) if td is not None else (roofline, None)
+        # ---- CPU baseline: the oracle (a port of the reference path) on the host cores -------------------
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(sd, x, S)
+    print(json.dumps(out))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, rec):
+    """--dump-outputs: what the last timed step returned, the gathered keypoint records of every rank's images, as
+    float32 arrays: image id, number of people, their scores and keypoints (x, y, score, tag), zero-padded to
+    MAX_PEOPLE_RECORD people.  8,288 B per image; above 64 MB, a fixed sample of the images (the same in every run)."""
+    from rtpe import engine
+    r = rec.cpu().numpy()
+    keep = (64 << 20) // r[0].nbytes
+    if len(r) > keep:
+        r = r[np.sort(np.random.default_rng(0).choice(len(r), keep, replace=False))]
+    P, J = engine.MAX_PEOPLE_RECORD, engine.NUM_HEATMAPS
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("image_ids", r[:, 0]), ("num_people", r[:, 1]), ("scores", r[:, 2:2 + P]),
+                    ("keypoints", r[:, 2 + P:].reshape(len(r), P, J, 4))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def rooflines(args, eng, op_ms, fwd_s):
+    """--full: from the per-op event times of the recorded steps (``op_ms``, averaged), the roofline of the
+    time-dominant kernel family and of the fused C = 48 BasicBlock; writes the --dump-ops table"""
+    from rtpe import _native as nat
+    B, S = args.batch, args.size
+    n_ops = len(eng.program.ops)
+
     # ---- roofline of the dominant kernel --------------------------------------
-    op_ms /= max(1, n_rec)
     names = eng.program.names
     costs = [eng.op_cost(i, B, S, S) for i in range(n_ops)]
     by_name = {}
@@ -638,36 +716,7 @@ def main():
                     nm, d["n"], d["ms"], d["flops"] / max(d["ms"], 1e-9) / 1e9,
                     d["bytes"] / max(d["ms"], 1e-9) / 1e6, d["ms"] / d["n"] * 1e3))
             f.write("forward total (events) %.3f ms; wall %.3f ms\n" % (fwd_ms_events, fwd_s * 1e3))
-
-    # ---- CPU baseline: the oracle (a port of the reference path) on the host cores -------------------
-    cpu = None
-    if not args.no_cpu_baseline:
-        cpu = cpu_baseline(sd, x, S)
-
-    value = world * B * args.steps / dt
-    out = {
-        "metric": "images/sec at 640x640 (HRNet-w48 fwd+decode)", "value": round(value, 2), "unit": "images/sec",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f16 (fp32 accumulate, fp32 BatchNorm; fp32 NCHW in/out)",
-        "data": "synthetic",
-        "config": {"workload": "configs[2]: batch=%d per GPU, %dx%d, half-wrapper teacher forward + decode of "
-                               "17 keypoint channels, weights %s (seeded random)" % (B, S, S, args.weights),
-                   "batch_per_gpu": B, "people_per_batch_rank0": people[0],
-                   "pipeline": "software-pipelined steps (TeacherPipeline.stream): %s forward(s) in flight on internal streams, "
-                               "decode of batch k-1 beside forward k; the %d recorded steps run alone" % (
-                                   os.environ.get("RTPE_FORWARDS_IN_FLIGHT", "2"), n_slots),
-                   "forward_only_images_per_sec_per_gpu": round(B / fwd_s, 1),
-                   "host_cpu_ms_per_step": round(host_cpu_ms, 2), "host_threads": host_threads},
-        # roofline = the time-dominant kernel family (MFMA-bound 3x3 convs with C >= 96); roofline_secondary = the fused
-        # C = 48 BasicBlock (HBM-bound by SURVEY 8d's layer-fused bytes), the second-largest share of the forward
-        "roofline": td if td is not None else roofline, "roofline_secondary": roofline if td is not None else None,
-        "build_mode": entry.BUILD_INFO.get("mode"), "cpu_baseline": cpu,
-    }
-    print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return td, roofline
 
 
 if __name__ == "__main__":

@@ -2472,3 +2472,27 @@ def test_full_size_batch_invariance(nat, teacher):
     with torch.no_grad():
         preds2, refined2 = model(x)
     assert torch.equal(preds, preds2) and torch.equal(refined, refined2)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(nat, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (a plain run, small batch and size): one JSON line with the
+    headline fields, exactly K timed steps, and the keypoint records of the last step as float32 .npy files"""
+    import json
+    import subprocess
+    import sys
+    out = tmp_path / "outs"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--batch", "2", "--size", "256", "--dump-outputs", str(out)],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "forward_only_images_per_sec_per_gpu" not in d["config"]
+    got = {n: np.load(str(out / (n + ".npy"))) for n in ("image_ids", "num_people", "scores", "keypoints")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["image_ids"].tolist() == [0, 1] and got["keypoints"].shape == (2, 30, 17, 4)
+    assert got["num_people"].sum() == d["config"]["people_per_batch_rank0"] > 0
+    assert np.isfinite(got["keypoints"]).all() and np.isfinite(got["scores"]).all()

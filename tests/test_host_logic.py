@@ -674,3 +674,30 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["config"]["records_gathered"] == 3 and "starting" not in res.stderr
+
+
+def test_bench_dump_outputs_and_what_needs_full(tmp_path):
+    """bench.py --dump-outputs writes the gathered keypoint records of the last timed step as float32 arrays, one row
+    per image (zero-padded to MAX_PEOPLE_RECORD people); a plain run refuses what only --full measures"""
+    import importlib.util
+    import subprocess
+    import sys
+    from rtpe import engine
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    people = np.arange(2 * 17 * 4, dtype=np.float32).reshape(2, 17, 4)
+    rec = engine.pack_records([7, 9], [(people, [0.5, 0.25]), (np.zeros((0, 17, 4), np.float32), [])], "cpu")
+    bench.dump_outputs(str(tmp_path / "out"), rec)
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("image_ids", "num_people", "scores", "keypoints")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["image_ids"].tolist() == [7, 9] and got["num_people"].tolist() == [2, 0]
+    assert got["scores"].shape == (2, engine.MAX_PEOPLE_RECORD) and got["scores"][0, :3].tolist() == [0.5, 0.25, 0]
+    assert got["keypoints"].shape == (2, engine.MAX_PEOPLE_RECORD, 17, 4)
+    np.testing.assert_array_equal(got["keypoints"][0, :2], people)
+    assert not got["keypoints"][0, 2:].any() and not got["keypoints"][1].any() and not got["scores"][1].any()
+    for extra in (["--config", "1"], ["--list", os.path.join(ROOT, "tests", "golden", "coco_minival2017_100.txt")],
+                  ["--dump-ops", str(tmp_path / "ops.txt")]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True,
+                             timeout=600)
+        assert res.returncode == 2 and "need --full" in res.stderr, (extra, res.stderr[-500:])

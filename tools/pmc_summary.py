@@ -144,7 +144,7 @@ def main():
     except (OSError, ValueError, IndexError):
         pass
     cfg = bench.get("config", {})
-    out = {"command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 "
+    out = {"command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 "
                       "(one pass per group: fetch, write, mfma, lds; tools/pmc_passes.sh)",
            "csrc_sha16": csrc_sha16(),        # the kernel sources these counters belong to (bench.py compares)
            "batch": cfg.get("batch_per_gpu"), "size": 640, "unprofiled_bench": {k: bench.get(k) for k in ("value", "ms_per_step")},

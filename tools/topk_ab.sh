@@ -4,11 +4,11 @@
 out=$1; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 export RTPE_AUTOTUNE_CACHE=$PWD/$out/autotune.json
-python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_plain.json 2> $out/bench_plain.err || exit 1
+python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_plain.json 2> $out/bench_plain.err || exit 1
 for v in base new; do
   if [ $v = base ]; then export RTPE_LIBRARY=$PWD/realtime-pose-estimation_amd/librtpe_base.so; else unset RTPE_LIBRARY; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$v -o t -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_$v -o p -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_pmc_$v.json 2> $out/bench_pmc_$v.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$v -o t -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_$v -o p -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 > $out/bench_pmc_$v.json 2> $out/bench_pmc_$v.err || exit 1
   echo "== $v: $(cut -c1-100 $out/bench_$v.json)"
   grep -h "topk_tile_kernel\|topk_merge\|plane_argmax\|refine_scan" $out/trace_$v/*/*kernel_stats.csv | cut -c1-200
   python3 - $out/pmc_$v <<'PY'
