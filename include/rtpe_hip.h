@@ -485,6 +485,41 @@ int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_t hw, int64
                                   const float* topk_val, const int32_t* topk_ind, int32_t K,
                                   void* scratch, size_t scratch_bytes, void* stream);
 
+/* Flip test decode (single scale; rtpe/inference.py multi_scale_inference with scale_factors=(1,),
+ * flip_test=True, project2image=True; upstream HigherHRNet get_multi_stage_outputs / aggregate_results) for a
+ * batch, never building the maps at the projection size.  Inputs: the network outputs of the images, preds
+ * (N,2J,h4,w4) and refined (N,J,h2,w2), and of their mirror images, preds_f / refined_f (same shapes), fp32 on the
+ * device, each with its own image stride in elements.  rs = F.interpolate(bilinear, align_corners=False) with
+ * rtpe_resize_combine's arithmetic, flip = mirror of the resized map, q = flip_index[j] (HOST ints, a permutation
+ * of 0..J-1, e.g. the COCO flip index):
+ *     A_o = (rs(preds[:, j]) + refined[:, j]) / 2      A_f = (flip(rs(preds_f[:, q])) + flip(refined_f[:, q])) / 2
+ *     T_o = rs(preds[:, J + j])                         T_f = flip(rs(preds_f[:, J + q]))           at (h2, w2)
+ *     heat = (rs(A_o) + rs(A_f)) / 2,  tag = [rs(T_o), rs(T_f)] (D = 2)                         at (oh, ow)
+ * Bytes of the (h2, w2) maps buffer (A_o, A_f, T_o, T_f, device) for N images of J joints: */
+int rtpe_flip_maps_bytes(int32_t N, int32_t J, int32_t h2, int32_t w2, size_t* bytes);
+
+/* Writes A_o, A_f, T_o, T_f into `maps` (one pass over the four inputs), then NMS + top-k + tag gather of heat / tag
+ * as rtpe_topk does on the materialised maps: val_k / ind_k (N*J,K), tag_k (N*J,K,2).  J <= 32.  scratch: device,
+ * rtpe_topk_scratch_bytes(N*J, oh, ow, K).  Stream-ordered. */
+int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                   const float* refined, int32_t h2, int32_t w2, int64_t refined_img_stride,
+                   const float* preds_f, int64_t preds_f_img_stride,
+                   const float* refined_f, int64_t refined_f_img_stride,
+                   int32_t N, int32_t J, const int32_t* flip_index, int32_t oh, int32_t ow, int32_t K,
+                   int32_t nms_ksize, int32_t nms_pad,
+                   float* val_k, int32_t* ind_k, float* tag_k,
+                   float* maps, size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
+/* rtpe_adjust_refine on heat / tag (D = 2) from the `maps` rtpe_topk_flip wrote for the same batch; ans_in /
+ * ans_out (P,J,5).  topk_val / topk_ind (N*J,K), device-addressable: the top-k table of the same call for refine's
+ * arg-max shortcut (as rtpe_adjust_refine_fused_topk), or both NULL.  scratch: device,
+ * rtpe_adjust_refine_scratch_bytes(P, J, 2). */
+int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh, int32_t ow,
+                            const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                            int32_t do_adjust, int32_t do_refine, float* scores,
+                            const float* topk_val, const int32_t* topk_ind, int32_t K,
+                            void* scratch, size_t scratch_bytes, void* stream);
+
 /* match_by_tag for a batch of N images on `n_threads` host threads.  Inputs as
  * rtpe_match_by_tag with a leading image axis.  People of image n follow those
  * of image n-1 in `ans` (max_people_total rows of (J,3+D)); person_img[i] =

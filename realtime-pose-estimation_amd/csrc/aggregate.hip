@@ -14,6 +14,7 @@
 //   * dst + v and the TRUE division by div as separate fp32 operations (x / 3.0 is not x * (1/3)).
 // HBM-bound: one read of the (smaller) source planes through L2, one read-modify-write of dst.
 #include "rtpe_common.h"
+#include "resize_nc.h"          // axis_nc / taps_nc (shared with the flip-test decode samplers)
 
 namespace rtpe {
 
@@ -28,20 +29,6 @@ struct ResizeArgs {
   int flip, accumulate;
   float div;            // 1: no division
 };
-
-__device__ __forceinline__ void axis_nc(float scale, int n_in, int n_out, int o, int* i0, int* i1, float* l0, float* l1) {
-  if (n_in == n_out) { *i0 = *i1 = o; *l0 = 1.f; *l1 = 0.f; return; }
-  float real = __builtin_fmaf(scale, (float)o + 0.5f, -0.5f);   // ATen's build contracts scale * (o + 0.5) - 0.5
-  real = real < 0.f ? 0.f : real;
-  int a = (int)real;
-  a = a < n_in - 1 ? a : n_in - 1;
-  *i0 = a;
-  *i1 = a + (a < n_in - 1 ? 1 : 0);
-  float l = real - (float)a;
-  l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);             // guard_index_and_lambda
-  *l1 = l;
-  *l0 = 1.f - l;
-}
 
 __global__ void __launch_bounds__(256) resize_combine_kernel(const ResizeArgs a) {
   const size_t plane = (size_t)a.oh * a.ow;
@@ -58,16 +45,7 @@ __global__ void __launch_bounds__(256) resize_combine_kernel(const ResizeArgs a)
     float ly0, ly1, lx0, lx1;
     axis_nc(a.sy, a.h, a.oh, y, &y0, &y1, &ly0, &ly1);
     axis_nc(a.sx, a.w, a.ow, xs, &x0, &x1, &lx0, &lx1);
-    float v;
-    if (a.h == a.oh && a.w == a.ow) {
-      v = b[(size_t)y0 * a.w + x0];
-    } else {
-      const float v00 = b[(size_t)y0 * a.w + x0], v01 = b[(size_t)y0 * a.w + x1];
-      const float v10 = b[(size_t)y1 * a.w + x0], v11 = b[(size_t)y1 * a.w + x1];
-      const float t0 = __builtin_fmaf(v00, lx0, v01 * lx1);
-      const float t1 = __builtin_fmaf(v10, lx0, v11 * lx1);
-      v = __builtin_fmaf(t0, ly0, t1 * ly1);
-    }
+    float v = taps_nc(b, a.w, a.h == a.oh && a.w == a.ow, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
     if (a.accumulate) v = a.dst[i] + v;
     if (a.div != 1.f) v = v / a.div;
     a.dst[i] = v;

@@ -13,6 +13,7 @@
 //     first-occurrence semantics); keys are (order-preserving value bits << 32
 //     | ~index) so one unsigned 64-bit max does both.
 #include "rtpe_common.h"
+#include "resize_nc.h"          // align_corners=False bilinear of the flip-test chain (aggregate.hip's arithmetic)
 
 namespace rtpe {
 
@@ -268,6 +269,141 @@ __device__ __forceinline__ bool fill_raw<BilinearMap>(const BilinearMap& m, int 
   // lane = column (its axis entry stays in registers), wave = every 4th row (its axis entry is wave-uniform):
   // per sample only the four taps and the result touch LDS - with one table look-up per sample and axis the
   // kernel was bound by the LDS instruction rate.  Columns 64.. of the padded tile go in one extra pass.
+  {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c0 = tx->i0[lane], c1 = tx->i1[lane];
+    const float lx0 = tx->l0[lane], lx1 = tx->l1[lane];
+    for (int py = wv; py < PH; py += 4) {
+      const int r0 = __builtin_amdgcn_readfirstlane(ty->i0[py]), r1 = __builtin_amdgcn_readfirstlane(ty->i1[py]);
+      const float ly0 = ty->l0[py], ly1 = ty->l1[py];
+      raw[py * PW + lane] = sample(r0, r1, ly0, ly1, c0, c1, lx0, lx1);
+    }
+    const int extra = PW - 64;                             // 2 * pad columns
+    for (int i = threadIdx.x; i < PH * extra; i += 256) {
+      const int py = i / extra, px = 64 + i - py * extra;
+      raw[py * PW + px] = sample(ty->i0[py], ty->i1[py], ty->l0[py], ty->l1[py], tx->i0[px], tx->i1[px], tx->l0[px],
+                                 tx->l1[px]);
+    }
+  }
+  if (staged) __syncthreads();                          // `stage` becomes the row-max buffer again
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// flip test (upstream single-scale + flip protocol, rtpe/inference.py): the heat map at the projection size (oh, ow)
+//     heat(y, x) = (rs(A_o)(y, x) + rs(A_f)(y, x)) / 2
+// with rs = F.interpolate(bilinear, align_corners=False) from the refined resolution (sh, sw), evaluated with
+// aggregate.hip's arithmetic (resize_nc.h): the two rs values are exactly what aggregate_results' copy and its
+// accumulate-and-divide call read, and (a + b) / 2 is the kernel's dst + v, then / div.  A_o / A_f are the
+// stage-averaged maps of the image and of its mirror image (flip_prep_kernel below) as dense (planes, sh, sw).
+// ---------------------------------------------------------------------------
+struct NcAxes {             // (sh, sw) -> (oh, ow) planes, align_corners=False
+  int sh, sw, oh, ow;
+  float sy, sx;             // float(in) / float(out)
+  bool ident;               // both sizes agree: the kernel copies
+  __device__ __forceinline__ float at(const float* plane, int y, int x) const {
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    axis_nc(sy, sh, oh, y, &y0, &y1, &ly0, &ly1);
+    axis_nc(sx, sw, ow, x, &x0, &x1, &lx0, &lx1);
+    return taps_nc(plane, sw, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+  }
+};
+
+struct FlipHeatMap {
+  const float* ao;          // (planes, sh, sw) stage average of the image
+  const float* af;          // (planes, sh, sw) the same of the mirror image, mirrored back, joints swapped
+  NcAxes a;
+  __device__ __forceinline__ float at(int plane, int y, int x) const {
+    const size_t off = (size_t)plane * a.sh * a.sw;
+    const float o = a.at(ao + off, y, x), f = a.at(af + off, y, x);
+    return (o + f) / 2.f;
+  }
+};
+
+struct FlipTag {            // D == 2: [rs(T_o), rs(T_f)], the image's tag first (torch.cat order of aggregate_results)
+  const float* to;
+  const float* tf;
+  NcAxes a;
+  __device__ __forceinline__ float at(int plane, int y, int x, int d) const {
+    return a.at((d == 0 ? to : tf) + (size_t)plane * a.sh * a.sw, y, x);
+  }
+};
+
+// The tile of the flip heat map: axis tables once per tile row / column, the source rectangles of BOTH planes staged
+// in LDS (in `stage`, the row-max buffer, free at this point), then per sample the eight taps from there and the
+// arithmetic of FlipHeatMap::at (same operations, same operands: bit-equal).  The separable form of the
+// align_corners=True sampler does not apply: the identity branch and the two planes per sample would need two
+// row buffers; the register-blocked max passes of the 5x5 path (nms_tile / topk_tile_kernel) run on its output.
+template <>
+__device__ __forceinline__ bool fill_raw<FlipHeatMap>(const FlipHeatMap& m, int plane, int h, int w, int y0, int x0,
+                                                      int pad, float* raw, AxisTab* ty, AxisTab* tx, float* stage,
+                                                      int stage_floats, int* pos_flag, float*) {
+  const int PW = kTW + 2 * pad, PH = kTH + 2 * pad;
+  const NcAxes& A = m.a;
+  for (int i = threadIdx.x; i < PH + PW; i += 256) {
+    const bool isy = i < PH;
+    const int k = isy ? i : i - PH;
+    const int o = (isy ? y0 : x0) - pad + k;
+    AxisTab* t = isy ? ty : tx;
+    int a0 = -1, a1 = -1;
+    float f0 = 0.f, f1 = 0.f;
+    if ((unsigned)o < (unsigned)(isy ? h : w)) {
+      if (isy) axis_nc(A.sy, A.sh, A.oh, o, &a0, &a1, &f0, &f1);
+      else axis_nc(A.sx, A.sw, A.ow, o, &a0, &a1, &f0, &f1);
+    }
+    t->i0[k] = a0; t->i1[k] = a1; t->l0[k] = f0; t->l1[k] = f1;
+  }
+  __syncthreads();
+  const size_t off = (size_t)plane * A.sh * A.sw;
+  const float* bo = m.ao + off;
+  const float* bf = m.af + off;
+  const int ky0 = max(0, pad - y0), ky1 = min(PH - 1, h - 1 - (y0 - pad));
+  const int kx0 = max(0, pad - x0), kx1 = min(PW - 1, w - 1 - (x0 - pad));
+  const int sr0 = ty->i0[ky0], sr1 = ty->i1[ky1], sc0 = tx->i0[kx0], sc1 = tx->i1[kx1];   // i0, i1 grow with o
+  const int er = sr1 - sr0 + 1, ec = sc1 - sc0 + 1;
+  const bool staged = stage != nullptr && ky0 <= ky1 && kx0 <= kx1 && er > 0 && ec > 0 && 2 * er * ec <= stage_floats;
+  const int ne = er * ec;
+  if (staged) {
+    bool pos = false;
+    for (int i0 = threadIdx.x; i0 < 2 * ne; i0 += 4 * 256) {
+      float v4[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * 256;
+        const int ii = i < 2 * ne ? i : 0;                // (no branch around the load)
+        const int q = ii < ne ? ii : ii - ne;
+        const int r = q / ec, c = q - r * ec;
+        v4[k] = (ii < ne ? bo : bf)[(size_t)(sr0 + r) * A.sw + sc0 + c];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * 256;
+        if (i < 2 * ne) {
+          stage[i] = v4[k];
+          pos |= v4[k] > 0.f;
+        }
+      }
+    }
+    if (pos_flag != nullptr && pos) *pos_flag = 1;         // (the caller zeroed it before the axis-table barrier)
+    __syncthreads();
+    // every sample is (a + b) / 2 of combinations of these values with weights >= 0: none positive, no candidate
+    if (pos_flag != nullptr && *pos_flag == 0) return false;
+  }
+  auto sample = [&](int r0, int r1, float ly0, float ly1, int c0, int c1, float lx0, float lx1) -> float {
+    if (r0 < 0 || c0 < 0) return -INFINITY;               // outside the image
+    float o, f;
+    if (staged) {
+      const float* so = stage - sc0;
+      const float* sf = stage + ne - sc0;
+      o = taps_nc(so + (r0 - sr0) * ec, ec, A.ident, 0, r1 - r0, c0, c1, ly0, ly1, lx0, lx1);
+      f = taps_nc(sf + (r0 - sr0) * ec, ec, A.ident, 0, r1 - r0, c0, c1, ly0, ly1, lx0, lx1);
+    } else {
+      o = taps_nc(bo, A.sw, A.ident, r0, r1, c0, c1, ly0, ly1, lx0, lx1);
+      f = taps_nc(bf, A.sw, A.ident, r0, r1, c0, c1, ly0, ly1, lx0, lx1);
+    }
+    return (o + f) / 2.f;
+  };
   {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c0 = tx->i0[lane], c1 = tx->i1[lane];
@@ -1087,6 +1223,51 @@ static int topk_run(const Map& m, const TagMap& tm, int planes, int tag_shared_j
   return RTPE_OK;
 }
 
+// ---------------------------------------------------------------------------
+// flip test, step 1: the four maps at the refined resolution (h2, w2) the projection samples, from the network
+// outputs of the image (P (N,2J,h4,w4), R (N,J,h2,w2)) and of its mirror image (Pf, Rf), in ONE pass over them:
+//     A_o = (rs(P[:, j]) + R[:, j]) / 2                        T_o = rs(P[:, J + j])
+//     A_f = (flip(rs(Pf[:, q])) + flip(Rf[:, q])) / 2          T_f = flip(rs(Pf[:, J + q]))      q = perm[j]
+// rs = align_corners=False to (h2, w2), flip = mirror of the RESIZED map (x -> w2 - 1 - x): the values the
+// get_multi_stage_outputs calls of rtpe/inference.py write (rs, then dst + v and / 2 as separate operations).
+// ---------------------------------------------------------------------------
+struct FlipPrepArgs {
+  const float *p, *r, *pf, *rf;
+  long long p_st, r_st, pf_st, rf_st;   // elements between images
+  int J, h4, w4, h2, w2;
+  float sy, sx;                         // float(h4) / float(h2), float(w4) / float(w2)
+  int perm[kMaxJ];
+  float *ao, *af, *to, *tf;             // (N*J, h2, w2) each
+};
+
+__global__ void __launch_bounds__(256) flip_prep_kernel(const FlipPrepArgs a) {
+  const int plane = blockIdx.y, n = plane / a.J, j = plane - n * a.J, q = a.perm[j];
+  const int npix = a.h2 * a.w2;
+  const size_t src_plane = (size_t)a.h4 * a.w4;
+  const bool ident = a.h4 == a.h2 && a.w4 == a.w2;
+  const float* P = a.p + (size_t)n * a.p_st;
+  const float* Pf = a.pf + (size_t)n * a.pf_st;
+  const float* R = a.r + (size_t)n * a.r_st + (size_t)j * npix;
+  const float* Rf = a.rf + (size_t)n * a.rf_st + (size_t)q * npix;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
+    const int y = i / a.w2, x = i - y * a.w2, xs = a.w2 - 1 - x;
+    int y0, y1, x0, x1, f0, f1;
+    float ly0, ly1, lx0, lx1, lf0, lf1;
+    axis_nc(a.sy, a.h4, a.h2, y, &y0, &y1, &ly0, &ly1);
+    axis_nc(a.sx, a.w4, a.w2, x, &x0, &x1, &lx0, &lx1);
+    axis_nc(a.sx, a.w4, a.w2, xs, &f0, &f1, &lf0, &lf1);
+    const float ph = taps_nc(P + (size_t)j * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+    const float pt = taps_nc(P + (size_t)(a.J + j) * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+    const float fh = taps_nc(Pf + (size_t)q * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
+    const float ft = taps_nc(Pf + (size_t)(a.J + q) * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
+    const size_t o = (size_t)plane * npix + i;
+    a.ao[o] = (ph + R[i]) / 2.f;
+    a.af[o] = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
+    a.to[o] = pt;
+    a.tf[o] = ft;
+  }
+}
+
 }  // namespace rtpe
 
 using namespace rtpe;
@@ -1193,4 +1374,93 @@ extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_
   BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
   return adjust_refine_run(m, tm, N, J, oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores,
                            scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+}
+
+// ---------------------------------------------------------------------------
+// flip test (single scale): rtpe/inference.py multi_scale_inference(scale_factors=(1,), flip_test=True,
+// project2image=True) for a whole batch, the projected maps never built
+// ---------------------------------------------------------------------------
+static FlipHeatMap flip_heat(const float* maps, int N, int J, int h2, int w2, int oh, int ow) {
+  const size_t n = (size_t)N * J * h2 * w2;
+  FlipHeatMap m;
+  m.ao = maps; m.af = maps + n;
+  m.a.sh = h2; m.a.sw = w2; m.a.oh = oh; m.a.ow = ow;
+  m.a.sy = (float)h2 / (float)oh;
+  m.a.sx = (float)w2 / (float)ow;
+  m.a.ident = h2 == oh && w2 == ow;
+  return m;
+}
+
+static FlipTag flip_tag(const float* maps, int N, int J, int h2, int w2, int oh, int ow) {
+  const size_t n = (size_t)N * J * h2 * w2;
+  FlipTag t;
+  t.to = maps + 2 * n; t.tf = maps + 3 * n;
+  t.a = flip_heat(maps, N, J, h2, w2, oh, ow).a;
+  return t;
+}
+
+extern "C" int rtpe_flip_maps_bytes(int32_t N, int32_t J, int32_t h2, int32_t w2, size_t* bytes) {
+  RTPE_REQUIRE(bytes && N > 0 && J > 0 && h2 > 0 && w2 > 0, "flip_maps_bytes: bad argument");
+  *bytes = (size_t)4 * N * J * h2 * w2 * sizeof(float);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                              const float* refined, int32_t h2, int32_t w2, int64_t refined_img_stride,
+                              const float* preds_f, int64_t preds_f_img_stride, const float* refined_f,
+                              int64_t refined_f_img_stride, int32_t N, int32_t J, const int32_t* flip_index,
+                              int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
+                              int32_t* ind_k, float* tag_k, float* maps, size_t maps_bytes, void* scratch,
+                              size_t scratch_bytes, void* stream) {
+  RTPE_REQUIRE(preds && refined && preds_f && refined_f && flip_index && val_k && ind_k && tag_k && maps && scratch,
+               "topk_flip: null argument");
+  RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "topk_flip: N=%d J=%d (1 <= J <= %d)", N, J, kMaxJ);
+  RTPE_REQUIRE(h4 > 0 && w4 > 0 && h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && K > 0 && (int64_t)h2 * w2 < 0x7fffffff,
+               "topk_flip: bad shape");
+  RTPE_REQUIRE(N * J <= 65535, "topk_flip: at most 65535 planes per call");
+  RTPE_REQUIRE(preds_img_stride >= (int64_t)2 * J * h4 * w4 && preds_f_img_stride >= (int64_t)2 * J * h4 * w4 &&
+                   refined_img_stride >= (int64_t)J * h2 * w2 && refined_f_img_stride >= (int64_t)J * h2 * w2,
+               "topk_flip: an image stride is shorter than the image");
+  size_t need = 0;
+  rtpe_flip_maps_bytes(N, J, h2, w2, &need);
+  RTPE_REQUIRE(maps_bytes >= need, "topk_flip: maps buffer too small (%zu < %zu bytes)", maps_bytes, need);
+  FlipPrepArgs a;
+  memset(&a, 0, sizeof(a));
+  unsigned seen = 0;
+  for (int j = 0; j < J; ++j) {
+    const int q = flip_index[j];
+    RTPE_REQUIRE(q >= 0 && q < J && !(seen & (1u << q)), "topk_flip: flip_index is not a permutation of 0..%d", J - 1);
+    seen |= 1u << q;
+    a.perm[j] = q;
+  }
+  a.p = preds; a.r = refined; a.pf = preds_f; a.rf = refined_f;
+  a.p_st = preds_img_stride; a.r_st = refined_img_stride; a.pf_st = preds_f_img_stride; a.rf_st = refined_f_img_stride;
+  a.J = J; a.h4 = h4; a.w4 = w4; a.h2 = h2; a.w2 = w2;
+  a.sy = (float)h4 / (float)h2;
+  a.sx = (float)w4 / (float)w2;
+  const size_t n = (size_t)N * J * h2 * w2;
+  a.ao = maps; a.af = maps + n; a.to = maps + 2 * n; a.tf = maps + 3 * n;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int npix = h2 * w2;
+  const int bx = (npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024;
+  hipLaunchKernelGGL(flip_prep_kernel, dim3(bx, N * J), dim3(256), 0, s, a);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return topk_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N * J, 0, 2, oh, ow,
+                  K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes, s);
+}
+
+extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
+                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                       size_t scratch_bytes, void* stream) {
+  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
+                   h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && N * J <= 65535,
+               "adjust_refine_flip: bad argument (1 <= J <= %d)", kMaxJ);
+  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
+               "adjust_refine_flip: topk_val and topk_ind go together (K > 0)");
+  if (P <= 0) return RTPE_OK;
+  return adjust_refine_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N, J, oh, ow,
+                           2, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch, scratch_bytes,
+                           reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
 }

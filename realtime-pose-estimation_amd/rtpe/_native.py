@@ -113,6 +113,14 @@ _SIGS = {
                                                 c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                                 c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                                 c_int32, c_void_p, c_size_t, c_void_p]),
+    "rtpe_flip_maps_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_topk_flip": (c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int64,
+                                 c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, POINTER(c_int32),
+                                 c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rtpe_adjust_refine_flip": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "rtpe_match_by_tag_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_double, c_double, c_int32, c_int32, c_void_p,
                                           c_int32, c_void_p, c_void_p, c_int32]),

@@ -114,23 +114,43 @@ def unpack_records(rec):
 
 
 class TeacherPipeline:
-    """forward + decode for batches of pre-processed images on one GPU."""
+    """forward + decode for batches of pre-processed images on one GPU.
 
-    def __init__(self, model, parser=None, device=None):
+    ``flip_test=True``: the upstream single-scale + flip test protocol (rtpe/inference.py ``multi_scale_inference``
+    with ``scale_factors=(1,), flip_test=True, project2image=True``) for whole batches: every batch is mirrored on
+    the GPU, both forwards run and ``HeatmapParser.parse_flip`` decodes the pair (``flip_index``: the joint
+    permutation, default ``FLIP_CONFIG["COCO"]``).  People then carry 5 columns (x, y, val, tag of the image, tag of
+    the mirror image) in input-pixel coordinates of the projection size; ``gather`` / ``pack_records`` keep the
+    first 4, i.e. the mirror image's tag is dropped from the records."""
+
+    def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None):
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.model = model.to(self.device).eval()
         self.parser = parser or HeatmapParser(num_joints=NUM_HEATMAPS, **HM_PARSER_PARAMS)
+        self.flip_test = bool(flip_test)
+        self.flip_index = None if flip_index is None else [int(q) for q in flip_index]
+        if self.flip_test and not self.parser.tag_per_joint:
+            raise ValueError("TeacherPipeline: the flip test needs a parser with tag_per_joint=True")
 
     @torch.no_grad()
     def forward(self, images):
         return self.model(images)
 
+    @staticmethod
+    def mirror(images):
+        """``torch.flip(images, [3])`` with the resize_combine kernel (an identity resize of the mirrored planes)"""
+        from .inference import resize_combine
+        return resize_combine(images, images.shape[2:], flip=True)
+
     @torch.no_grad()
     def __call__(self, images, out_hw=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
-        out_hw = decode resolution (original image size), default (H, W)."""
+        out_hw = decode resolution (original image size), default (H, W); with ``flip_test`` the projection size."""
         preds, refined = self.model(images)
         hw = tuple(out_hw) if out_hw is not None else tuple(images.shape[2:])
+        if self.flip_test:
+            preds_f, refined_f = self.model(self.mirror(images))
+            return self.parser.parse_flip(preds, refined, preds_f, refined_f, hw, self.flip_index)
         return self.parser.parse_lowres(refined, preds[:, NUM_HEATMAPS:], hw)
 
     def stream(self, batches, out_hw=None, on_forward=None, decode_stream=None, in_flight=None, exclusive=None):
@@ -159,7 +179,8 @@ class TeacherPipeline:
 
         Yields one ``[(people, scores)] * N`` list per batch, in order, two steps after the batch
         was submitted.  ``on_forward(k, x)`` may replace the plain forward (bench.py records op
-        events).  Keep the host thread pools small (``torch.set_num_threads``): a burst of idle-
+        events); with ``flip_test`` it is called for the batch and for its mirror image, on the same stream,
+        and T(k) is ``HeatmapParser.flip_topk`` of the pair.  Keep the host thread pools small (``torch.set_num_threads``): a burst of idle-
         spinning OpenMP threads can exhaust a container's CPU quota and stall the launches."""
         import os
         mode = decode_stream or os.environ.get("RTPE_DECODE_STREAM", "side")
@@ -202,6 +223,16 @@ class TeacherPipeline:
 
         # ``on_forward`` must return FRESH output tensors for every batch (the plain forward does): the decode of
         # batch k runs on the side stream while F(k+1) runs on the main one, and nothing makes F(k+1) wait for it.
+        def run_forwards(k, x):
+            """(preds, refined) of batch k, followed by those of its mirror image with flip_test (both on the current
+            stream: the mirrored input is made and read there)"""
+            fwd = on_forward if on_forward is not None else (lambda _k, t: self.model(t))
+            preds, refined = fwd(k, x)
+            if not self.flip_test:
+                return preds, refined
+            preds_f, refined_f = fwd(k, self.mirror(x))
+            return preds, refined, preds_f, refined_f
+
         try:
             with torch.no_grad():
                 for k, x in enumerate(batches):
@@ -223,12 +254,12 @@ class TeacherPipeline:
                         prev_flags = set_forward_flags(0 if os.environ.get("RTPE_STREAM_LANES", "0") == "1" else FWD_NO_LANES)
                         try:
                             with torch.cuda.stream(fs):
-                                preds, refined = on_forward(k, x) if on_forward is not None else self.model(x)
+                                outs = run_forwards(k, x)
                         finally:
                             set_forward_flags(prev_flags)
                             set_workspace_slot(prev_slot)
                     else:
-                        preds, refined = on_forward(k, x) if on_forward is not None else self.model(x)
+                        outs = run_forwards(k, x)
                     hw = tuple(out_hw) if out_hw is not None else tuple(x.shape[2:])
                     f_done = None
                     if side is not None or fs is not main:
@@ -236,12 +267,16 @@ class TeacherPipeline:
                         f_done.record(fs)
                         if side is None:
                             main.wait_event(f_done)          # the decode runs on the caller's stream
-                            preds.record_stream(main)
-                            refined.record_stream(main)
+                            for t in outs:
+                                t.record_stream(main)
                     if topk_done is not None:
                         on_decode_stream(P.lowres_match, topk_done)     # host matching overlaps F(k) on the GPU
-                    st = on_decode_stream(P.lowres_topk, refined, preds[:, NUM_HEATMAPS:], hw, after=f_done,
-                                          uses=(preds, refined))
+                    if self.flip_test:
+                        st = on_decode_stream(P.flip_topk, *outs, hw, self.flip_index, after=f_done, uses=outs)
+                    else:
+                        preds, refined = outs
+                        st = on_decode_stream(P.lowres_topk, refined, preds[:, NUM_HEATMAPS:], hw, after=f_done,
+                                              uses=outs)
                     if refine_done is not None:
                         yield P.lowres_finish(refine_done)
                     refine_done, topk_done = topk_done, st

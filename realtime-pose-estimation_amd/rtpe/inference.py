@@ -151,3 +151,52 @@ def multi_scale_inference(model, parser, image, input_size=640, scale_factors=(1
     final_results = transforms.get_final_preds(grouped, center, scale,
                                                [final_heatmaps.size(3), final_heatmaps.size(2)])
     return final_results, scores, final_heatmaps, tags
+
+
+def group_by_input_size(sizes):
+    """``sizes``: the network input size of every image (anything hashable, e.g. the ``(w, h)`` that
+    ``transforms.get_multi_scale_size`` returns) -> ``[(size, [indices])]``: one group per distinct size, groups in
+    the order their first image appears, indices ascending within a group.  Pure host function."""
+    groups = {}
+    for i, s in enumerate(sizes):
+        groups.setdefault(s, []).append(i)
+    return list(groups.items())
+
+
+def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
+                        device="cuda"):
+    """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
+    flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
+    warped to its network input size, images of one size are batched (``batch_size`` at a time) through
+    ``TeacherPipeline(flip_test=True).stream`` - both forwards on the GPU, the decode from the network outputs
+    (``HeatmapParser.parse_flip``) - and the keypoints are mapped back with ``get_final_preds``.  Returns
+    ``[(final_results, scores)]`` in input order, each bit-identical to the first two items the per-image call
+    returns (the forward is batch-invariant)."""
+    from .engine import TeacherPipeline
+    from .third_party import transforms
+    if not parser.tag_per_joint:
+        raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
+    if batch_size < 1:
+        raise ValueError("flip_test_inference: batch_size must be positive")
+    images = list(images)
+    sizes = [transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0] for img in images]
+    pipe = TeacherPipeline(model, parser, device=device, flip_test=True)
+    out = [None] * len(images)
+    for (w, h), idx in group_by_input_size(sizes):
+        chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
+        meta = {}
+
+        def batches():
+            for c in chunks:
+                ts = []
+                for i in c:
+                    t, center, scale = transforms.warp_normalize(images[i], input_size, 1, 1, device=pipe.device)
+                    ts.append(t)
+                    meta[i] = (center, scale)
+                yield torch.cat(ts)
+        with torch.no_grad():
+            for c, res in zip(chunks, pipe.stream(batches(), out_hw=(h, w))):
+                for i, (people, scores) in zip(c, res):
+                    center, scale = meta.pop(i)
+                    out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
+    return out
