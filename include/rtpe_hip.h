@@ -520,6 +520,50 @@ int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N
                             const float* topk_val, const int32_t* topk_ind, int32_t K,
                             void* scratch, size_t scratch_bytes, void* stream);
 
+/* Multi-scale test decode (rtpe/inference.py multi_scale_inference with any scale_factors containing 1, flip_test 0 / 1,
+ * project2image=True; upstream get_multi_stage_outputs + aggregate_results over the scales) for a batch, never
+ * building the maps at the projection size (oh, ow) = the scale-1 input size.  S <= 4 scales in the loop order
+ * (descending); h2[i] x w2[i] (HOST ints) = the refined resolution of scale i; base = the index of scale 1; rs_i =
+ * align_corners=False from (h2[i], w2[i]) to (oh, ow) (a copy when the sizes agree); A_o / A_f / T_o / T_f of every
+ * scale as in rtpe_topk_flip:
+ *     H_i  = flip ? (rs_i(A_o^i) + rs_i(A_f^i)) / 2 : rs_i(A_o^i)
+ *     heat = H_0, heat = heat + H_i for i = 1, 2, ... in order, then heat / S (a true division) when S > 1
+ *     tag  = [rs_base(T_o)] (D = 1), or [rs_base(T_o), rs_base(T_f)] with flip (D = 2)
+ * Bytes of the maps buffer (device): per scale A_o and, with flip, A_f, (N*J, h2[i], w2[i]) each, then T_o and, with
+ * flip, T_f of scale `base`. */
+int rtpe_ms_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2, int32_t base,
+                       int32_t flip, size_t* bytes);
+
+/* Writes the maps of scale `scale` for images n0 .. n0+n-1 of the batch of N (one pass over the network outputs of
+ * those n images: preds (n,2J,h4,w4), refined (n,J,h2[scale],w2[scale]) and, with flip, those of the mirror images;
+ * each with its own image stride in elements), so that a scale's forward can run in sub-batches.  flip_index (HOST,
+ * a permutation of 0..J-1) is read with flip only.  Stream-ordered. */
+int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                 const float* refined, int64_t refined_img_stride,
+                 const float* preds_f, int64_t preds_f_img_stride,
+                 const float* refined_f, int64_t refined_f_img_stride,
+                 int32_t n0, int32_t n, int32_t N, int32_t J, const int32_t* flip_index,
+                 int32_t S, const int32_t* h2, const int32_t* w2, int32_t base, int32_t flip, int32_t scale,
+                 float* maps, size_t maps_bytes, void* stream);
+
+/* NMS + top-k + tag gather of heat / tag from the `maps` of ALL scales (rtpe_ms_prep done for every scale and image)
+ * as rtpe_topk does on the materialised maps: val_k / ind_k (N*J,K), tag_k (N*J,K,D).  scratch: device,
+ * rtpe_topk_scratch_bytes(N*J, oh, ow, K).  Stream-ordered. */
+int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                 int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad,
+                 float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
+                 void* scratch, size_t scratch_bytes, void* stream);
+
+/* rtpe_adjust_refine on heat / tag (D = 1 + flip) from the same `maps`; ans_in / ans_out (P,J,3+D).  topk_val /
+ * topk_ind (N*J,K): the top-k table of the same batch for refine's arg-max shortcut, or both NULL.  scratch: device,
+ * rtpe_adjust_refine_scratch_bytes(P, J, D). */
+int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                          int32_t base, int32_t flip, int32_t oh, int32_t ow, size_t maps_bytes,
+                          const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                          int32_t do_adjust, int32_t do_refine, float* scores,
+                          const float* topk_val, const int32_t* topk_ind, int32_t K,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 /* match_by_tag for a batch of N images on `n_threads` host threads.  Inputs as
  * rtpe_match_by_tag with a leading image axis.  People of image n follow those
  * of image n-1 in `ans` (max_people_total rows of (J,3+D)); person_img[i] =

@@ -424,6 +424,188 @@ __device__ __forceinline__ bool fill_raw<FlipHeatMap>(const FlipHeatMap& m, int 
   return true;
 }
 
+
+// ---------------------------------------------------------------------------
+// multi-scale test (upstream protocol with scale_factors s_0 > s_1 > ..., rtpe/inference.py multi_scale_inference
+// with project2image=True): the heat map at the projection size (oh, ow) of the scale-1 input
+//     H_i = flip ? (rs_i(A_o^i) + rs_i(A_f^i)) / 2 : rs_i(A_o^i)
+//     F = H_0, then F = F + H_i for i = 1, 2, ... in this order, then F = F / S (a true division) when S > 1
+// rs_i = align_corners=False from the refined resolution of scale i (a copy when the sizes agree, as for s = 2).
+// These are the values of aggregate_results' copy / accumulate calls and of the final resize_combine(div=S): the
+// sum order is part of the result.  A_o^i / A_f^i as written by ms_prep_kernel (below), dense (planes, sh_i, sw_i).
+// ---------------------------------------------------------------------------
+constexpr int kMaxScales = 4;
+
+struct MultiScaleHeatMap {
+  const float* ao[kMaxScales];
+  const float* af[kMaxScales];  // flip only
+  NcAxes a[kMaxScales];
+  int S;
+  bool flip;
+  __device__ __forceinline__ float entry(int i, int plane, int y, int x) const {
+    const size_t off = (size_t)plane * a[i].sh * a[i].sw;
+    const float o = a[i].at(ao[i] + off, y, x);
+    if (!flip) return o;
+    const float f = a[i].at(af[i] + off, y, x);
+    return (o + f) / 2.f;
+  }
+  __device__ __forceinline__ float at(int plane, int y, int x) const {
+    float F = entry(0, plane, y, x);
+#pragma unroll
+    for (int i = 1; i < kMaxScales; ++i)
+      if (i < S) F = F + entry(i, plane, y, x);
+    return S > 1 ? F / (float)S : F;
+  }
+};
+
+// The tile of the multi-scale heat map.  Per scale, the source rectangle of its plane(s) is staged in LDS (`stage`,
+// the row-max buffer, free at this point) while it fits, in scale order; an identity entry (a copy: every source value
+// read once per tile) and an entry that no longer fits are read from global memory.  The axes are evaluated in
+// registers (lane = column, row axes per wave-uniform row) - S AxisTab pairs would not fit beside the tile.  Per sample
+// the operations of MultiScaleHeatMap::at on the same operands: bit-equal.  The early-out (no positive source value:
+// no candidate) needs every entry staged.
+template <>
+__device__ __forceinline__ bool fill_raw<MultiScaleHeatMap>(const MultiScaleHeatMap& m, int plane, int h, int w, int y0,
+                                                            int x0, int pad, float* raw, AxisTab*, AxisTab*, float* stage,
+                                                            int stage_floats, int* pos_flag, float*) {
+  const int PW = kTW + 2 * pad, PH = kTH + 2 * pad;
+  const int np = m.flip ? 2 : 1;
+  const int ky0 = max(0, pad - y0), ky1 = min(PH - 1, h - 1 - (y0 - pad));
+  const int kx0 = max(0, pad - x0), kx1 = min(PW - 1, w - 1 - (x0 - pad));
+  const bool can = stage != nullptr && ky0 <= ky1 && kx0 <= kx1;
+  int sr0[kMaxScales], sc0[kMaxScales], ec[kMaxScales], ne[kMaxScales], at0[kMaxScales];   // at0 < 0: not staged
+  int used = 0;
+  bool all = can;
+#pragma unroll
+  for (int i = 0; i < kMaxScales; ++i) {
+    sr0[i] = sc0[i] = 0;
+    ec[i] = ne[i] = 0;
+    at0[i] = -1;
+    if (i >= m.S || !can) continue;
+    const NcAxes& A = m.a[i];
+    int r0, r1, c0, c1, d;
+    float f0, f1;
+    axis_nc(A.sy, A.sh, A.oh, y0 - pad + ky0, &r0, &d, &f0, &f1);    // i0, i1 grow with o
+    axis_nc(A.sy, A.sh, A.oh, y0 - pad + ky1, &d, &r1, &f0, &f1);
+    axis_nc(A.sx, A.sw, A.ow, x0 - pad + kx0, &c0, &d, &f0, &f1);
+    axis_nc(A.sx, A.sw, A.ow, x0 - pad + kx1, &d, &c1, &f0, &f1);
+    sr0[i] = r0;
+    sc0[i] = c0;
+    ec[i] = c1 - c0 + 1;
+    ne[i] = (r1 - r0 + 1) * ec[i];
+    if (!A.ident && used + np * ne[i] <= stage_floats) {
+      at0[i] = used;
+      used += np * ne[i];
+    } else {
+      all = false;
+    }
+  }
+  __syncthreads();                                         // the caller zeroed pos_flag
+  if (used > 0) {
+    bool pos = false;
+    for (int i0 = threadIdx.x; i0 < used; i0 += 4 * 256) {
+      float v4[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ii = i0 + k * 256 < used ? i0 + k * 256 : 0;    // (no branch around the load)
+        const float* src = m.ao[0];
+        int q = 0, e = 1, sw = 0;
+#pragma unroll
+        for (int s = 0; s < kMaxScales; ++s) {             // the staged entry ii falls in (offsets grow with s)
+          if (at0[s] >= 0 && ii >= at0[s]) {
+            const bool second = ii >= at0[s] + ne[s];
+            q = ii - at0[s] - (second ? ne[s] : 0);
+            src = (second ? m.af[s] : m.ao[s]) + (size_t)plane * m.a[s].sh * m.a[s].sw +
+                  (size_t)sr0[s] * m.a[s].sw + sc0[s];
+            e = ec[s];
+            sw = m.a[s].sw;
+          }
+        }
+        const int r = q / e, c = q - r * e;
+        v4[k] = src[(size_t)r * sw + c];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * 256;
+        if (i < used) {
+          stage[i] = v4[k];
+          pos |= v4[k] > 0.f;
+        }
+      }
+    }
+    if (pos_flag != nullptr && pos) *pos_flag = 1;
+    __syncthreads();
+    // every sample combines these values with weights >= 0 (and divides by S > 0): none positive, no candidate
+    if (all && pos_flag != nullptr && *pos_flag == 0) return false;
+  }
+  auto value = [&](int s, int r0, int r1, float ly0, float ly1, int c0, int c1, float lx0, float lx1) -> float {
+    const NcAxes& A = m.a[s];
+    float o, f = 0.f;
+    if (at0[s] >= 0) {
+      const float* so = stage + at0[s] + (r0 - sr0[s]) * ec[s] - sc0[s];
+      o = taps_nc(so, ec[s], A.ident, 0, r1 - r0, c0, c1, ly0, ly1, lx0, lx1);
+      if (m.flip) f = taps_nc(so + ne[s], ec[s], A.ident, 0, r1 - r0, c0, c1, ly0, ly1, lx0, lx1);
+    } else {
+      const size_t off = (size_t)plane * A.sh * A.sw;
+      o = taps_nc(m.ao[s] + off, A.sw, A.ident, r0, r1, c0, c1, ly0, ly1, lx0, lx1);
+      if (m.flip) f = taps_nc(m.af[s] + off, A.sw, A.ident, r0, r1, c0, c1, ly0, ly1, lx0, lx1);
+    }
+    return m.flip ? (o + f) / 2.f : o;
+  };
+  auto combine = [&](int y, const int (&c0)[kMaxScales], const int (&c1)[kMaxScales], const float (&l0)[kMaxScales],
+                     const float (&l1)[kMaxScales]) -> float {
+    float F = 0.f;
+#pragma unroll
+    for (int s = 0; s < kMaxScales; ++s) {
+      if (s >= m.S) continue;
+      int r0, r1;
+      float ly0, ly1;
+      axis_nc(m.a[s].sy, m.a[s].sh, m.a[s].oh, y, &r0, &r1, &ly0, &ly1);
+      const float hv = value(s, r0, r1, ly0, ly1, c0[s], c1[s], l0[s], l1[s]);
+      F = s == 0 ? hv : F + hv;
+    }
+    return m.S > 1 ? F / (float)m.S : F;
+  };
+  auto x_axes = [&](int x, int (&c0)[kMaxScales], int (&c1)[kMaxScales], float (&l0)[kMaxScales],
+                    float (&l1)[kMaxScales]) {
+#pragma unroll
+    for (int s = 0; s < kMaxScales; ++s) {
+      c0[s] = c1[s] = 0;
+      l0[s] = 1.f;
+      l1[s] = 0.f;
+      if (s < m.S) axis_nc(m.a[s].sx, m.a[s].sw, m.a[s].ow, x, &c0[s], &c1[s], &l0[s], &l1[s]);
+    }
+  };
+  {
+    // lane = column (its x axes stay in registers), wave = every 4th row; columns 64.. in one extra pass
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = x0 - pad + lane;
+    const bool xin = (unsigned)x < (unsigned)w;
+    int c0[kMaxScales], c1[kMaxScales];
+    float l0[kMaxScales], l1[kMaxScales];
+    x_axes(xin ? x : 0, c0, c1, l0, l1);
+    for (int py = wv; py < PH; py += 4) {
+      const int y = y0 - pad + py;
+      raw[py * PW + lane] = xin && (unsigned)y < (unsigned)h ? combine(y, c0, c1, l0, l1) : -INFINITY;
+    }
+    const int extra = PW - 64;                             // 2 * pad columns
+    for (int i = threadIdx.x; i < PH * extra; i += 256) {
+      const int py = i / extra, px = 64 + i - py * extra;
+      const int y = y0 - pad + py, xe = x0 - pad + px;
+      float v = -INFINITY;
+      if ((unsigned)y < (unsigned)h && (unsigned)xe < (unsigned)w) {
+        int e0[kMaxScales], e1[kMaxScales];
+        float m0[kMaxScales], m1[kMaxScales];
+        x_axes(xe, e0, e1, m0, m1);
+        v = combine(y, e0, e1, m0, m1);
+      }
+      raw[py * PW + px] = v;
+    }
+  }
+  if (used > 0) __syncthreads();                        // `stage` becomes the row-max buffer again
+  return true;
+}
+
 template <class Map>
 __device__ __forceinline__ bool nms_tile(const Map& m, int plane, int h, int w, int y0, int x0, int pad,
                                          float* raw, float* rowmax, AxisTab* ty, AxisTab* tx, int* pos_flag = nullptr,
@@ -1237,36 +1419,49 @@ struct FlipPrepArgs {
   int J, h4, w4, h2, w2;
   float sy, sx;                         // float(h4) / float(h2), float(w4) / float(w2)
   int perm[kMaxJ];
-  float *ao, *af, *to, *tf;             // (N*J, h2, w2) each
+  int plane0;                           // first output plane: image offset * J (a sub-batch lands in a larger buffer)
+  float *ao, *af, *to, *tf;             // (planes, h2, w2) each; those an instance does not write may be null
 };
 
-__global__ void __launch_bounds__(256) flip_prep_kernel(const FlipPrepArgs a) {
+// FLIP: also the mirror image's maps (A_f, T_f); TAGS: also the tag maps (T_o, T_f)
+template <bool FLIP, bool TAGS>
+__device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
   const int plane = blockIdx.y, n = plane / a.J, j = plane - n * a.J, q = a.perm[j];
   const int npix = a.h2 * a.w2;
   const size_t src_plane = (size_t)a.h4 * a.w4;
   const bool ident = a.h4 == a.h2 && a.w4 == a.w2;
   const float* P = a.p + (size_t)n * a.p_st;
-  const float* Pf = a.pf + (size_t)n * a.pf_st;
   const float* R = a.r + (size_t)n * a.r_st + (size_t)j * npix;
-  const float* Rf = a.rf + (size_t)n * a.rf_st + (size_t)q * npix;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
-    const int y = i / a.w2, x = i - y * a.w2, xs = a.w2 - 1 - x;
-    int y0, y1, x0, x1, f0, f1;
-    float ly0, ly1, lx0, lx1, lf0, lf1;
+    const int y = i / a.w2, x = i - y * a.w2;
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
     axis_nc(a.sy, a.h4, a.h2, y, &y0, &y1, &ly0, &ly1);
     axis_nc(a.sx, a.w4, a.w2, x, &x0, &x1, &lx0, &lx1);
-    axis_nc(a.sx, a.w4, a.w2, xs, &f0, &f1, &lf0, &lf1);
+    const size_t o = (size_t)(a.plane0 + plane) * npix + i;
     const float ph = taps_nc(P + (size_t)j * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
-    const float pt = taps_nc(P + (size_t)(a.J + j) * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
-    const float fh = taps_nc(Pf + (size_t)q * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
-    const float ft = taps_nc(Pf + (size_t)(a.J + q) * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
-    const size_t o = (size_t)plane * npix + i;
     a.ao[o] = (ph + R[i]) / 2.f;
-    a.af[o] = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
-    a.to[o] = pt;
-    a.tf[o] = ft;
+    if (TAGS) a.to[o] = taps_nc(P + (size_t)(a.J + j) * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+    if (FLIP) {
+      const float* Pf = a.pf + (size_t)n * a.pf_st;
+      const float* Rf = a.rf + (size_t)n * a.rf_st + (size_t)q * npix;
+      const int xs = a.w2 - 1 - x;
+      int f0, f1;
+      float lf0, lf1;
+      axis_nc(a.sx, a.w4, a.w2, xs, &f0, &f1, &lf0, &lf1);
+      const float fh = taps_nc(Pf + (size_t)q * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
+      a.af[o] = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
+      if (TAGS)
+        a.tf[o] = taps_nc(Pf + (size_t)(a.J + q) * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
+    }
   }
 }
+
+__global__ void __launch_bounds__(256) flip_prep_kernel(const FlipPrepArgs a) { prep_planes<true, true>(a); }
+
+// multi-scale test, step 1 for one scale (and one sub-batch of its images): A_o [, A_f] [, T_o [, T_f]] of the scale
+template <bool FLIP, bool TAGS>
+__global__ void __launch_bounds__(256) ms_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, TAGS>(a); }
 
 }  // namespace rtpe
 
@@ -1463,4 +1658,172 @@ extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2
   return adjust_refine_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N, J, oh, ow,
                            2, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch, scratch_bytes,
                            reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+}
+
+// ---------------------------------------------------------------------------
+// multi-scale test: rtpe/inference.py multi_scale_inference(scale_factors, flip_test, project2image=True) for a whole
+// batch, the maps at the projection size never built.  The maps buffer, in floats: per scale i (the loop order,
+// descending) A_o^i then, with flip, A_f^i, each (N*J, h2_i, w2_i); then T_o and, with flip, T_f of the scale-1 entry
+// `base`, (N*J, h2_base, w2_base) each.
+// ---------------------------------------------------------------------------
+struct MsLayout {
+  size_t ao[kMaxScales], af[kMaxScales], to, tf, total;   // float offsets into the maps buffer; total floats
+};
+
+static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, MsLayout* L) {
+  RTPE_REQUIRE(h2 && w2, "ms: null size array");
+  RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "ms: N=%d J=%d (1 <= J <= %d)", N, J, kMaxJ);
+  RTPE_REQUIRE((int64_t)N * J <= 65535, "ms: at most 65535 planes per call");
+  RTPE_REQUIRE(S >= 1 && S <= kMaxScales, "ms: %d scales (1 <= S <= %d)", S, kMaxScales);
+  RTPE_REQUIRE(base >= 0 && base < S, "ms: the scale-1 entry %d is not one of the %d scales", base, S);
+  RTPE_REQUIRE(flip == 0 || flip == 1, "ms: flip must be 0 or 1");
+  size_t o = 0;
+  for (int i = 0; i < S; ++i) {
+    RTPE_REQUIRE(h2[i] > 0 && w2[i] > 0 && (int64_t)h2[i] * w2[i] < 0x7fffffff, "ms: bad size %d x %d of scale %d",
+                 h2[i], w2[i], i);
+    const size_t n = (size_t)N * J * h2[i] * w2[i];
+    L->ao[i] = o;
+    o += n;
+    L->af[i] = o;
+    if (flip) o += n;
+  }
+  const size_t nb = (size_t)N * J * h2[base] * w2[base];
+  L->to = o;
+  o += nb;
+  L->tf = o;
+  if (flip) o += nb;
+  L->total = o;
+  return RTPE_OK;
+}
+
+static NcAxes nc_axes(int sh, int sw, int oh, int ow) {
+  NcAxes a;
+  a.sh = sh; a.sw = sw; a.oh = oh; a.ow = ow;
+  a.sy = (float)sh / (float)oh;
+  a.sx = (float)sw / (float)ow;
+  a.ident = sh == oh && sw == ow;
+  return a;
+}
+
+static MultiScaleHeatMap ms_heat(const float* maps, const MsLayout& L, int S, const int32_t* h2, const int32_t* w2,
+                                 int flip, int oh, int ow) {
+  MultiScaleHeatMap m;
+  memset(&m, 0, sizeof(m));
+  m.S = S;
+  m.flip = flip != 0;
+  for (int i = 0; i < S; ++i) {
+    m.ao[i] = maps + L.ao[i];
+    m.af[i] = flip ? maps + L.af[i] : nullptr;
+    m.a[i] = nc_axes(h2[i], w2[i], oh, ow);
+  }
+  return m;
+}
+
+// D = 1 + flip: FlipTag's second map is never read with D = 1
+static FlipTag ms_tag(const float* maps, const MsLayout& L, const int32_t* h2, const int32_t* w2, int base, int flip,
+                      int oh, int ow) {
+  FlipTag t;
+  t.to = maps + L.to;
+  t.tf = flip ? maps + L.tf : nullptr;
+  t.a = nc_axes(h2[base], w2[base], oh, ow);
+  return t;
+}
+
+extern "C" int rtpe_ms_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2, int32_t base,
+                                  int32_t flip, size_t* bytes) {
+  RTPE_REQUIRE(bytes, "ms_maps_bytes: null argument");
+  MsLayout L;
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  *bytes = L.total * sizeof(float);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride, const float* refined,
+                            int64_t refined_img_stride, const float* preds_f, int64_t preds_f_img_stride,
+                            const float* refined_f, int64_t refined_f_img_stride, int32_t n0, int32_t n, int32_t N,
+                            int32_t J, const int32_t* flip_index, int32_t S, const int32_t* h2, const int32_t* w2,
+                            int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream) {
+  MsLayout L;
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(preds && refined && maps && (!flip || (preds_f && refined_f && flip_index)), "ms_prep: null argument");
+  RTPE_REQUIRE(scale >= 0 && scale < S, "ms_prep: scale %d of %d", scale, S);
+  RTPE_REQUIRE(n > 0 && n0 >= 0 && (int64_t)n0 + n <= N, "ms_prep: images %d..%d of %d", n0, n0 + n - 1, N);
+  RTPE_REQUIRE(h4 > 0 && w4 > 0, "ms_prep: bad shape");
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "ms_prep: maps buffer too small (%zu < %zu bytes)", maps_bytes,
+               L.total * sizeof(float));
+  const int hs = h2[scale], ws = w2[scale];
+  RTPE_REQUIRE(preds_img_stride >= (int64_t)2 * J * h4 * w4 && refined_img_stride >= (int64_t)J * hs * ws &&
+                   (!flip || (preds_f_img_stride >= (int64_t)2 * J * h4 * w4 &&
+                              refined_f_img_stride >= (int64_t)J * hs * ws)),
+               "ms_prep: an image stride is shorter than the image");
+  FlipPrepArgs a;
+  memset(&a, 0, sizeof(a));
+  if (flip) {
+    unsigned seen = 0;
+    for (int j = 0; j < J; ++j) {
+      const int q = flip_index[j];
+      RTPE_REQUIRE(q >= 0 && q < J && !(seen & (1u << q)), "ms_prep: flip_index is not a permutation of 0..%d", J - 1);
+      seen |= 1u << q;
+      a.perm[j] = q;
+    }
+  }
+  a.p = preds; a.r = refined; a.pf = preds_f; a.rf = refined_f;
+  a.p_st = preds_img_stride; a.r_st = refined_img_stride; a.pf_st = preds_f_img_stride; a.rf_st = refined_f_img_stride;
+  a.J = J; a.h4 = h4; a.w4 = w4; a.h2 = hs; a.w2 = ws;
+  a.sy = (float)h4 / (float)hs;
+  a.sx = (float)w4 / (float)ws;
+  a.plane0 = n0 * J;
+  a.ao = maps + L.ao[scale];
+  a.af = flip ? maps + L.af[scale] : nullptr;
+  const bool tags = scale == base;
+  a.to = tags ? maps + L.to : nullptr;
+  a.tf = tags && flip ? maps + L.tf : nullptr;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int npix = hs * ws;
+  const dim3 grid((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024, n * J);
+  if (flip && tags) hipLaunchKernelGGL((ms_prep_kernel<true, true>), grid, dim3(256), 0, s, a);
+  else if (flip) hipLaunchKernelGGL((ms_prep_kernel<true, false>), grid, dim3(256), 0, s, a);
+  else if (tags) hipLaunchKernelGGL((ms_prep_kernel<false, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((ms_prep_kernel<false, false>), grid, dim3(256), 0, s, a);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                            int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize,
+                            int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+  MsLayout L;
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(maps && val_k && ind_k && tag_k && scratch, "topk_ms: null argument");
+  RTPE_REQUIRE(oh > 0 && ow > 0 && K > 0, "topk_ms: bad shape");
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "topk_ms: maps buffer too small (%zu < %zu bytes)", maps_bytes,
+               L.total * sizeof(float));
+  return topk_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N * J, 0,
+                  1 + flip, oh, ow, K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes,
+                  reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                     size_t scratch_bytes, void* stream) {
+  MsLayout L;
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && oh > 0 && ow > 0,
+               "adjust_refine_ms: bad argument");
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "adjust_refine_ms: maps buffer too small (%zu < %zu bytes)",
+               maps_bytes, L.total * sizeof(float));
+  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
+               "adjust_refine_ms: topk_val and topk_ind go together (K > 0)");
+  if (P <= 0) return RTPE_OK;
+  return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N,
+                           J, oh, ow, 1 + flip, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
+                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
 }

@@ -20,6 +20,19 @@ HM_PARSER_PARAMS = {"max_num_people": 30, "detection_threshold": 0.1, "tag_thres
 NUM_HEATMAPS = 17
 MAX_PEOPLE_RECORD = 30
 RECORD_FLOATS = 2 + MAX_PEOPLE_RECORD + MAX_PEOPLE_RECORD * NUM_HEATMAPS * 4   # 8,288 B
+# the most input pixels one forward of the multi-scale pipeline takes: the bench shape (32 x 640 x 640), i.e. tensors
+# and workspaces no larger than those the plain pipeline uses (several kernels index with 32 bits)
+MAX_FORWARD_PIXELS = 32 * 640 * 640
+
+
+def forward_plan(n, hw, max_forward_pixels=MAX_FORWARD_PIXELS):
+    """sub-batches ``[(n0, count)]`` of a batch of n images of input size hw = (H, W) such that no forward has more
+    than ``max_forward_pixels`` input pixels (per image: H * W).  Pure host function."""
+    per = int(max_forward_pixels) // (int(hw[0]) * int(hw[1]))
+    if per < 1:
+        raise ValueError("an input of %d x %d pixels exceeds the forward pixel budget of %d"
+                         % (hw[0], hw[1], max_forward_pixels))
+    return [(o, min(per, n - o)) for o in range(0, n, per)]
 
 
 def eval_student(model, hm_parser, val_dataloader, device,
@@ -121,9 +134,17 @@ class TeacherPipeline:
     the GPU, both forwards run and ``HeatmapParser.parse_flip`` decodes the pair (``flip_index``: the joint
     permutation, default ``FLIP_CONFIG["COCO"]``).  People then carry 5 columns (x, y, val, tag of the image, tag of
     the mirror image) in input-pixel coordinates of the projection size; ``gather`` / ``pack_records`` keep the
-    first 4, i.e. the mirror image's tag is dropped from the records."""
+    first 4, i.e. the mirror image's tag is dropped from the records.
 
-    def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None):
+    ``scale_factors`` (a tuple containing 1, at most 4 distinct scales; None: a single scale, as above): the upstream
+    multi-scale test protocol (``multi_scale_inference(..., scale_factors, flip_test, project2image=True)``).
+    ``__call__`` and ``stream()`` then take one input tensor per scale - the same images warped at every scale - in
+    descending scale order, run every scale's forward(s) in sub-batches of at most ``max_forward_pixels`` input
+    pixels (``forward_plan``; the forward is batch-invariant, so the bits do not depend on it) and decode with
+    ``HeatmapParser.parse_multi_scale`` at the scale-1 input size.  People carry 4 + flip_test columns."""
+
+    def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
+                 max_forward_pixels=MAX_FORWARD_PIXELS):
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.model = model.to(self.device).eval()
         self.parser = parser or HeatmapParser(num_joints=NUM_HEATMAPS, **HM_PARSER_PARAMS)
@@ -131,6 +152,42 @@ class TeacherPipeline:
         self.flip_index = None if flip_index is None else [int(q) for q in flip_index]
         if self.flip_test and not self.parser.tag_per_joint:
             raise ValueError("TeacherPipeline: the flip test needs a parser with tag_per_joint=True")
+        self.scale_factors = None
+        self.max_forward_pixels = int(max_forward_pixels)
+        if scale_factors is not None:
+            from .inference import check_scale_factors
+            self.scale_factors = check_scale_factors(scale_factors)
+            if not self.parser.tag_per_joint:
+                raise ValueError("TeacherPipeline: the multi-scale test needs a parser with tag_per_joint=True")
+
+    def _ms_inputs(self, images):
+        """the per-scale input tensors of one batch, checked: one (N,3,H_i,W_i) tensor per scale"""
+        xs = list(images) if isinstance(images, (list, tuple)) else None
+        if xs is None or len(xs) != len(self.scale_factors):
+            raise ValueError("TeacherPipeline: the multi-scale pipeline takes one input tensor per scale (%d)"
+                             % len(self.scale_factors))
+        for x in xs:
+            if x.dim() != 4 or x.shape[0] != xs[0].shape[0]:
+                raise ValueError("TeacherPipeline: the inputs of the scales must be (N,3,H,W) with the same N")
+        return xs
+
+    def _ms_begin(self, xs, out_hw):
+        """maps buffer of a multi-scale batch (current stream); the decode size defaults to the scale-1 input size"""
+        base = self.scale_factors.index(1)
+        hw = tuple(out_hw) if out_hw is not None else tuple(xs[base].shape[2:])
+        return self.parser.ms_begin(xs[0].shape[0], [(x.shape[2] // 2, x.shape[3] // 2) for x in xs], hw,
+                                    self.scale_factors, self.flip_test, self.flip_index, self.device)
+
+    def _ms_forwards(self, xs, fwd, on_outputs):
+        """every scale's forward (and that of the mirror image) in sub-batches, in scale order, on the current stream;
+        ``on_outputs(i, n0, outs)`` after each sub-batch"""
+        for i, x in enumerate(xs):
+            for n0, n in forward_plan(x.shape[0], x.shape[2:], self.max_forward_pixels):
+                xb = x[n0:n0 + n]
+                outs = tuple(fwd(xb))
+                if self.flip_test:
+                    outs = outs + tuple(fwd(self.mirror(xb)))
+                on_outputs(i, n0, outs)
 
     @torch.no_grad()
     def forward(self, images):
@@ -145,7 +202,15 @@ class TeacherPipeline:
     @torch.no_grad()
     def __call__(self, images, out_hw=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
-        out_hw = decode resolution (original image size), default (H, W); with ``flip_test`` the projection size."""
+        out_hw = decode resolution (original image size), default (H, W); with ``flip_test`` the projection size.
+        With ``scale_factors``: images = one tensor per scale (descending), out_hw default = the scale-1 (H, W)."""
+        if self.scale_factors is not None:
+            xs = self._ms_inputs(images)
+            st = self._ms_begin(xs, out_hw)
+            self._ms_forwards(xs, self.model, lambda i, n0, outs: self.parser.ms_prep(st, i, outs, n0))
+            self.parser.ms_topk(st)
+            self.parser.lowres_match(st)
+            return self.parser.lowres_finish(st)
         preds, refined = self.model(images)
         hw = tuple(out_hw) if out_hw is not None else tuple(images.shape[2:])
         if self.flip_test:
@@ -180,7 +245,10 @@ class TeacherPipeline:
         Yields one ``[(people, scores)] * N`` list per batch, in order, two steps after the batch
         was submitted.  ``on_forward(k, x)`` may replace the plain forward (bench.py records op
         events); with ``flip_test`` it is called for the batch and for its mirror image, on the same stream,
-        and T(k) is ``HeatmapParser.flip_topk`` of the pair.  Keep the host thread pools small (``torch.set_num_threads``): a burst of idle-
+        and T(k) is ``HeatmapParser.flip_topk`` of the pair.  With ``scale_factors`` every batch is a list of one tensor
+        per scale; ``on_forward`` is called for every sub-batch (and its mirror image), all on the forward stream and
+        workspace slot of step k; each sub-batch's maps are prepared on the decode stream as soon as its forwards are
+        done (``HeatmapParser.ms_prep``) and T(k) is ``ms_topk``.  Keep the host thread pools small (``torch.set_num_threads``): a burst of idle-
         spinning OpenMP threads can exhaust a container's CPU quota and stall the launches."""
         import os
         mode = decode_stream or os.environ.get("RTPE_DECODE_STREAM", "side")
@@ -233,9 +301,28 @@ class TeacherPipeline:
             preds_f, refined_f = fwd(k, self.mirror(x))
             return preds, refined, preds_f, refined_f
 
+        ms = self.scale_factors is not None
+
+        def run_ms_forwards(k, xs, st):
+            """every forward of multi-scale batch k on the current stream, the maps of each sub-batch prepared on the
+            decode stream behind an event; returns () (the network outputs are consumed)"""
+            fwd = (lambda t: on_forward(k, t)) if on_forward is not None else self.model
+
+            def prep(i, n0, outs):
+                ev = None
+                if side is not None:
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(self.device))
+                on_decode_stream(P.ms_prep, st, i, outs, n0, after=ev, uses=outs)
+            self._ms_forwards(xs, fwd, prep)
+            return ()
+
         try:
             with torch.no_grad():
                 for k, x in enumerate(batches):
+                    if ms:
+                        xs = self._ms_inputs(x)
+                        st_ms = on_decode_stream(self._ms_begin, xs, out_hw)
                     fs = main
                     if fwd_streams is not None:
                         # forward k on stream k % n with workspace slot 1 + k % n; the input was produced on `main`
@@ -247,20 +334,21 @@ class TeacherPipeline:
                                 if other is not fs:
                                     fs.wait_stream(other)
                         after_alone = fs if alone else None
-                        x.record_stream(fs)
+                        for t in (xs if ms else [x]):
+                            t.record_stream(fs)
                         # lanes off for THIS call only (a per-call flag of the ABI: nothing process-wide is touched,
                         # and nothing stays changed while the generator is suspended or if it is abandoned)
                         prev_slot = set_workspace_slot(1 + k % n_fwd)
                         prev_flags = set_forward_flags(0 if os.environ.get("RTPE_STREAM_LANES", "0") == "1" else FWD_NO_LANES)
                         try:
                             with torch.cuda.stream(fs):
-                                outs = run_forwards(k, x)
+                                outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
                         finally:
                             set_forward_flags(prev_flags)
                             set_workspace_slot(prev_slot)
                     else:
-                        outs = run_forwards(k, x)
-                    hw = tuple(out_hw) if out_hw is not None else tuple(x.shape[2:])
+                        outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
+                    hw = None if ms else tuple(out_hw) if out_hw is not None else tuple(x.shape[2:])
                     f_done = None
                     if side is not None or fs is not main:
                         f_done = torch.cuda.Event()
@@ -271,7 +359,9 @@ class TeacherPipeline:
                                 t.record_stream(main)
                     if topk_done is not None:
                         on_decode_stream(P.lowres_match, topk_done)     # host matching overlaps F(k) on the GPU
-                    if self.flip_test:
+                    if ms:
+                        st = on_decode_stream(P.ms_topk, st_ms, after=f_done)
+                    elif self.flip_test:
                         st = on_decode_stream(P.flip_topk, *outs, hw, self.flip_index, after=f_done, uses=outs)
                     else:
                         preds, refined = outs

@@ -200,3 +200,81 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
                     center, scale = meta.pop(i)
                     out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
     return out
+
+
+def check_scale_factors(scale_factors):
+    """the test scales of the batched multi-scale path in the loop order of ``multi_scale_inference`` (descending),
+    refused unless 1 is among them, they are distinct and there are at most 4.  Pure host function."""
+    scales = list(scale_factors)
+    if not scales or 1 not in scales:
+        raise ValueError("multi-scale test: 1 must be among the scales %s (the tags and the projection size come "
+                         "from scale 1)" % (tuple(scales),))
+    if len(set(float(s) for s in scales)) != len(scales):
+        raise ValueError("multi-scale test: the scales %s are not distinct" % (tuple(scales),))
+    if len(scales) > 4:
+        raise ValueError("multi-scale test: at most 4 scales, got %d" % len(scales))
+    if any(not s > 0 for s in scales):
+        raise ValueError("multi-scale test: the scales %s must be positive" % (tuple(scales),))
+    return tuple(sorted(scales, reverse=True))
+
+
+def multi_scale_input_sizes(image, input_size, scale_factors):
+    """the network input size ``(w, h)`` of ``image`` at every scale of ``scale_factors`` (descending, as
+    ``check_scale_factors`` returns them), as ``warp_normalize`` makes them; refused unless every size is a multiple
+    of 32 (the network's total stride).  Pure host function."""
+    from .third_party import transforms
+    lo = min(scale_factors)
+    sizes = tuple(transforms.get_multi_scale_size(image, input_size, s, lo)[0] for s in scale_factors)
+    for s, (w, h) in zip(scale_factors, sizes):
+        if w % 32 or h % 32:
+            raise ValueError("multi-scale test: the input size %d x %d at scale %s is not a multiple of 32"
+                             % (w, h, s))
+    return sizes
+
+
+def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
+                                adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda"):
+    """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
+    project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
+    sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
+    time through ``TeacherPipeline(scale_factors=...)`` - every scale's forwards in sub-batches of at most
+    ``max_forward_pixels`` input pixels (default ``engine.MAX_FORWARD_PIXELS``), the decode from the network outputs
+    (``HeatmapParser.parse_multi_scale``) - and the keypoints are mapped back with ``get_final_preds`` and the
+    centre / scale of the smallest-scale warp (what the per-image loop's last iteration leaves).  Returns
+    ``[(final_results, scores)]`` in input order, each bit-identical to the first two items the per-image call
+    returns.  The scales and every input size are checked before any GPU work."""
+    from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
+    from .third_party import transforms
+    scales = check_scale_factors(scale_factors)
+    if not parser.tag_per_joint:
+        raise ValueError("multi_scale_batch_inference: needs a parser with tag_per_joint=True")
+    if batch_size < 1:
+        raise ValueError("multi_scale_batch_inference: batch_size must be positive")
+    images = list(images)
+    sizes = [multi_scale_input_sizes(img, input_size, scales) for img in images]
+    lo, base = min(scales), scales.index(1)
+    pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
+                           max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels)
+    out = [None] * len(images)
+    for key, idx in group_by_input_size(sizes):
+        w, h = key[base]
+        chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
+        meta = {}
+
+        def batches():
+            for c in chunks:
+                per_scale = []
+                for s in scales:
+                    ts = []
+                    for i in c:
+                        t, center, scale = transforms.warp_normalize(images[i], input_size, s, lo, device=pipe.device)
+                        ts.append(t)
+                        meta[i] = (center, scale)          # the last scale is the smallest
+                    per_scale.append(torch.cat(ts))
+                yield per_scale
+        with torch.no_grad():
+            for c, res in zip(chunks, pipe.stream(batches(), out_hw=(h, w))):
+                for i, (people, scores) in zip(c, res):
+                    center, scale = meta.pop(i)
+                    out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
+    return out
