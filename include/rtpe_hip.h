@@ -564,6 +564,43 @@ int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, co
                           const float* topk_val, const int32_t* topk_ind, int32_t K,
                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* AGS multi-scale test decode (rtpe/inference.py multi_scale_inference(..., ags=True), the AGS branch of the upstream
+ * validation script): heat maps as rtpe_topk_ms; the grouping sees ONE tag map per image, shared by all joints (D = 1
+ * with or without flip): channel J (joint 0's tag) of the un-mirrored preds of the SMALLEST scale S-1, resized to
+ * that scale's refined size and then projected,
+ *     tag = rs_{S-1}(rs_(h2[S-1],w2[S-1])(P_{S-1}[:, J]))
+ * Bytes of the maps buffer (device): per scale A_o and, with flip, A_f, (N*J, h2[i], w2[i]) each, as rtpe_ms_maps_bytes;
+ * then the shared tag planes, (N, h2[S-1], w2[S-1]); no per-joint tag maps.  Same arguments and checks as
+ * rtpe_ms_maps_bytes. */
+int rtpe_ms_ags_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2, int32_t base,
+                           int32_t flip, size_t* bytes);
+
+/* rtpe_ms_prep for the AGS layout: the maps of scale `scale` for images n0 .. n0+n-1; scale S-1 also writes the
+ * shared tag planes of those images.  Stream-ordered. */
+int rtpe_ms_ags_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                     const float* refined, int64_t refined_img_stride,
+                     const float* preds_f, int64_t preds_f_img_stride,
+                     const float* refined_f, int64_t refined_f_img_stride,
+                     int32_t n0, int32_t n, int32_t N, int32_t J, const int32_t* flip_index,
+                     int32_t S, const int32_t* h2, const int32_t* w2, int32_t base, int32_t flip, int32_t scale,
+                     float* maps, size_t maps_bytes, void* stream);
+
+/* rtpe_topk_ms on the AGS maps: val_k / ind_k (N*J,K), tag_k (N*J,K,1), every joint of an image reading its shared
+ * tag plane.  scratch: device, rtpe_topk_scratch_bytes(N*J, oh, ow, K).  Stream-ordered. */
+int rtpe_topk_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                     int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad,
+                     float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
+                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* rtpe_adjust_refine_ms on the AGS maps (D = 1); ans_in / ans_out (P,J,4).  scratch: device,
+ * rtpe_adjust_refine_scratch_bytes(P, J, 1). */
+int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                              int32_t base, int32_t flip, int32_t oh, int32_t ow, size_t maps_bytes,
+                              const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                              int32_t do_adjust, int32_t do_refine, float* scores,
+                              const float* topk_val, const int32_t* topk_ind, int32_t K,
+                              void* scratch, size_t scratch_bytes, void* stream);
+
 /* match_by_tag for a batch of N images on `n_threads` host threads.  Inputs as
  * rtpe_match_by_tag with a leading image axis.  People of image n follow those
  * of image n-1 in `ans` (max_people_total rows of (J,3+D)); person_img[i] =

@@ -330,6 +330,18 @@ struct FlipTag {            // D == 2: [rs(T_o), rs(T_f)], the image's tag first
   }
 };
 
+// AGS (one tag map shared by all joints of an image, valid_ae1dim.py's AGS branch): D == 1, ONE plane per image,
+// (N, sh, sw).  The (image * J + joint) plane index that the top-k merge (tag_shared_joints = 0) and the adjust /
+// refine kernels pass is mapped to the image here, and only here.
+struct AgsTag {
+  const float* p;
+  int J;
+  NcAxes a;
+  __device__ __forceinline__ float at(int plane, int y, int x, int) const {
+    return a.at(p + (size_t)(plane / J) * a.sh * a.sw, y, x);
+  }
+};
+
 // The tile of the flip heat map: axis tables once per tile row / column, the source rectangles of BOTH planes staged
 // in LDS (in `stage`, the row-max buffer, free at this point), then per sample the eight taps from there and the
 // arithmetic of FlipHeatMap::at (same operations, same operands: bit-equal).  The separable form of the
@@ -1423,8 +1435,9 @@ struct FlipPrepArgs {
   float *ao, *af, *to, *tf;             // (planes, h2, w2) each; those an instance does not write may be null
 };
 
-// FLIP: also the mirror image's maps (A_f, T_f); TAGS: also the tag maps (T_o, T_f)
-template <bool FLIP, bool TAGS>
+// FLIP: also the mirror image's maps (A_f, T_f); TAGS: also the tag maps (T_o, T_f); AGS: the j == 0 planes also write
+// the image's shared tag plane rs(P[:, J]) to `to` at plane plane0 / J + n (the expression of T_o[:, 0])
+template <bool FLIP, bool TAGS, bool AGS = false>
 __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
   const int plane = blockIdx.y, n = plane / a.J, j = plane - n * a.J, q = a.perm[j];
   const int npix = a.h2 * a.w2;
@@ -1442,6 +1455,9 @@ __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
     const float ph = taps_nc(P + (size_t)j * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
     a.ao[o] = (ph + R[i]) / 2.f;
     if (TAGS) a.to[o] = taps_nc(P + (size_t)(a.J + j) * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+    if (AGS && j == 0)
+      a.to[(size_t)(a.plane0 / a.J + n) * npix + i] =
+          taps_nc(P + (size_t)a.J * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
     if (FLIP) {
       const float* Pf = a.pf + (size_t)n * a.pf_st;
       const float* Rf = a.rf + (size_t)n * a.rf_st + (size_t)q * npix;
@@ -1462,6 +1478,10 @@ __global__ void __launch_bounds__(256) flip_prep_kernel(const FlipPrepArgs a) { 
 // multi-scale test, step 1 for one scale (and one sub-batch of its images): A_o [, A_f] [, T_o [, T_f]] of the scale
 template <bool FLIP, bool TAGS>
 __global__ void __launch_bounds__(256) ms_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, TAGS>(a); }
+
+// AGS multi-scale test, step 1 for the smallest scale: A_o [, A_f] of the scale and the images' shared tag planes
+template <bool FLIP>
+__global__ void __launch_bounds__(256) ags_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, false, true>(a); }
 
 }  // namespace rtpe
 
@@ -1696,6 +1716,16 @@ static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, 
   return RTPE_OK;
 }
 
+// AGS (multi_scale_inference(..., ags=True)): per scale A_o and, with flip, A_f as above, no T_o / T_f; then ONE tag
+// plane per image at the refined size of the smallest scale S-1, (N, h2[S-1], w2[S-1]), at offset `to` (`tf` unused)
+static int ms_ags_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, MsLayout* L) {
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, L);     // the checks, and the heat maps' offsets
+  if (rc != RTPE_OK) return rc;
+  L->tf = L->to;                                                // the end of the heat maps
+  L->total = L->to + (size_t)N * h2[S - 1] * w2[S - 1];
+  return RTPE_OK;
+}
+
 static NcAxes nc_axes(int sh, int sw, int oh, int ow) {
   NcAxes a;
   a.sh = sh; a.sw = sw; a.oh = oh; a.ow = ow;
@@ -1739,13 +1769,15 @@ extern "C" int rtpe_ms_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t
   return RTPE_OK;
 }
 
-extern "C" int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride, const float* refined,
-                            int64_t refined_img_stride, const float* preds_f, int64_t preds_f_img_stride,
-                            const float* refined_f, int64_t refined_f_img_stride, int32_t n0, int32_t n, int32_t N,
-                            int32_t J, const int32_t* flip_index, int32_t S, const int32_t* h2, const int32_t* w2,
-                            int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream) {
+// rtpe_ms_prep / rtpe_ms_ags_prep: the same checks and arguments; `ags` picks the layout and the kernels
+static int ms_prep_impl(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride, const float* refined,
+                        int64_t refined_img_stride, const float* preds_f, int64_t preds_f_img_stride,
+                        const float* refined_f, int64_t refined_f_img_stride, int32_t n0, int32_t n, int32_t N,
+                        int32_t J, const int32_t* flip_index, int32_t S, const int32_t* h2, const int32_t* w2,
+                        int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream,
+                        bool ags) {
   MsLayout L;
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
+  const int rc = ags ? ms_ags_layout(N, J, S, h2, w2, base, flip, &L) : ms_layout(N, J, S, h2, w2, base, flip, &L);
   if (rc != RTPE_OK) return rc;
   RTPE_REQUIRE(preds && refined && maps && (!flip || (preds_f && refined_f && flip_index)), "ms_prep: null argument");
   RTPE_REQUIRE(scale >= 0 && scale < S, "ms_prep: scale %d of %d", scale, S);
@@ -1777,18 +1809,31 @@ extern "C" int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t 
   a.plane0 = n0 * J;
   a.ao = maps + L.ao[scale];
   a.af = flip ? maps + L.af[scale] : nullptr;
-  const bool tags = scale == base;
-  a.to = tags ? maps + L.to : nullptr;
+  // AGS: no per-joint tag maps; the smallest scale (the last of the loop) also writes the shared tag planes
+  const bool tags = !ags && scale == base, ags_tag = ags && scale == S - 1;
+  a.to = tags || ags_tag ? maps + L.to : nullptr;
   a.tf = tags && flip ? maps + L.tf : nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int npix = hs * ws;
   const dim3 grid((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024, n * J);
-  if (flip && tags) hipLaunchKernelGGL((ms_prep_kernel<true, true>), grid, dim3(256), 0, s, a);
+  if (ags_tag && flip) hipLaunchKernelGGL((ags_prep_kernel<true>), grid, dim3(256), 0, s, a);
+  else if (ags_tag) hipLaunchKernelGGL((ags_prep_kernel<false>), grid, dim3(256), 0, s, a);
+  else if (flip && tags) hipLaunchKernelGGL((ms_prep_kernel<true, true>), grid, dim3(256), 0, s, a);
   else if (flip) hipLaunchKernelGGL((ms_prep_kernel<true, false>), grid, dim3(256), 0, s, a);
   else if (tags) hipLaunchKernelGGL((ms_prep_kernel<false, true>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((ms_prep_kernel<false, false>), grid, dim3(256), 0, s, a);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
+}
+
+extern "C" int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride, const float* refined,
+                            int64_t refined_img_stride, const float* preds_f, int64_t preds_f_img_stride,
+                            const float* refined_f, int64_t refined_f_img_stride, int32_t n0, int32_t n, int32_t N,
+                            int32_t J, const int32_t* flip_index, int32_t S, const int32_t* h2, const int32_t* w2,
+                            int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream) {
+  return ms_prep_impl(preds, h4, w4, preds_img_stride, refined, refined_img_stride, preds_f, preds_f_img_stride,
+                      refined_f, refined_f_img_stride, n0, n, N, J, flip_index, S, h2, w2, base, flip, scale, maps,
+                      maps_bytes, stream, false);
 }
 
 extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
@@ -1825,5 +1870,78 @@ extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, in
   if (P <= 0) return RTPE_OK;
   return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N,
                            J, oh, ow, 1 + flip, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
+                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+}
+
+// ---------------------------------------------------------------------------
+// AGS multi-scale test: multi_scale_inference(..., ags=True) for a whole batch.  Heat maps as above; the tag of every
+// joint of image n is ONE plane, rs_(oh,ow)(rs_(h2,w2)(P_L[n, J])) of the smallest scale L = S-1 (D = 1), stored at
+// the refined size of that scale (ms_ags_layout) and projected on the fly.
+// ---------------------------------------------------------------------------
+static AgsTag ms_ags_tag(const float* maps, const MsLayout& L, int S, int J, const int32_t* h2, const int32_t* w2,
+                         int oh, int ow) {
+  AgsTag t;
+  t.p = maps + L.to;
+  t.J = J;
+  t.a = nc_axes(h2[S - 1], w2[S - 1], oh, ow);
+  return t;
+}
+
+extern "C" int rtpe_ms_ags_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                                      int32_t base, int32_t flip, size_t* bytes) {
+  RTPE_REQUIRE(bytes, "ms_ags_maps_bytes: null argument");
+  MsLayout L;
+  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  *bytes = L.total * sizeof(float);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_ms_ags_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                                const float* refined, int64_t refined_img_stride, const float* preds_f,
+                                int64_t preds_f_img_stride, const float* refined_f, int64_t refined_f_img_stride,
+                                int32_t n0, int32_t n, int32_t N, int32_t J, const int32_t* flip_index, int32_t S,
+                                const int32_t* h2, const int32_t* w2, int32_t base, int32_t flip, int32_t scale,
+                                float* maps, size_t maps_bytes, void* stream) {
+  return ms_prep_impl(preds, h4, w4, preds_img_stride, refined, refined_img_stride, preds_f, preds_f_img_stride,
+                      refined_f, refined_f_img_stride, n0, n, N, J, flip_index, S, h2, w2, base, flip, scale, maps,
+                      maps_bytes, stream, true);
+}
+
+extern "C" int rtpe_topk_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K,
+                                int32_t nms_ksize, int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k,
+                                size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  MsLayout L;
+  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(maps && val_k && ind_k && tag_k && scratch, "topk_ms_ags: null argument");
+  RTPE_REQUIRE(oh > 0 && ow > 0 && K > 0, "topk_ms_ags: bad shape");
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "topk_ms_ags: maps buffer too small (%zu < %zu bytes)",
+               maps_bytes, L.total * sizeof(float));
+  // tag_shared_joints = 0: AgsTag maps the plane to its image
+  return topk_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_ags_tag(maps, L, S, J, h2, w2, oh, ow), N * J, 0, 1,
+                  oh, ow, K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes,
+                  reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                         const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                         size_t maps_bytes, const float* ans_in, float* ans_out,
+                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
+                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                         void* scratch, size_t scratch_bytes, void* stream) {
+  MsLayout L;
+  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && oh > 0 && ow > 0,
+               "adjust_refine_ms_ags: bad argument");
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "adjust_refine_ms_ags: maps buffer too small (%zu < %zu bytes)",
+               maps_bytes, L.total * sizeof(float));
+  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
+               "adjust_refine_ms_ags: topk_val and topk_ind go together (K > 0)");
+  if (P <= 0) return RTPE_OK;
+  return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_ags_tag(maps, L, S, J, h2, w2, oh, ow), N, J,
+                           oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
                            scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
 }

@@ -134,6 +134,19 @@ _SIGS = {
                                         c_int32, c_int32, c_int32, c_int32, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                         c_size_t, c_void_p]),
+    "rtpe_ms_ags_maps_bytes": (c_int32, [c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                         c_int32, POINTER(c_size_t)]),
+    "rtpe_ms_ags_prep": (c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
+                                   POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                   c_void_p]),
+    "rtpe_topk_ms_ags": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rtpe_adjust_refine_ms_ags": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
+                                            c_int32, c_int32, c_int32, c_int32, c_size_t, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                            c_size_t, c_void_p]),
     "rtpe_match_by_tag_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_double, c_double, c_int32, c_int32, c_void_p,
                                           c_int32, c_void_p, c_void_p, c_int32]),

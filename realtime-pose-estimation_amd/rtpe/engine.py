@@ -141,23 +141,31 @@ class TeacherPipeline:
     ``__call__`` and ``stream()`` then take one input tensor per scale - the same images warped at every scale - in
     descending scale order, run every scale's forward(s) in sub-batches of at most ``max_forward_pixels`` input
     pixels (``forward_plan``; the forward is batch-invariant, so the bits do not depend on it) and decode with
-    ``HeatmapParser.parse_multi_scale`` at the scale-1 input size.  People carry 4 + flip_test columns."""
+    ``HeatmapParser.parse_multi_scale`` at the scale-1 input size.  People carry 4 + flip_test columns.
+
+    ``ags=True`` (needs ``scale_factors``; ``(1,)`` for the single-scale protocol): the AGS branch of
+    ``multi_scale_inference(..., ags=True)`` - one tag map per image, channel 0 of the un-mirrored tag maps of the
+    smallest scale, shared by all joints; any parser is accepted (its ``tag_per_joint`` is not read).  People carry 4
+    columns, with or without flip."""
 
     def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
-                 max_forward_pixels=MAX_FORWARD_PIXELS):
+                 max_forward_pixels=MAX_FORWARD_PIXELS, ags=False):
+        if ags and scale_factors is None:       # (before any GPU work)
+            raise ValueError("TeacherPipeline: ags=True needs scale_factors (use (1,) for the single-scale protocol)")
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.model = model.to(self.device).eval()
         self.parser = parser or HeatmapParser(num_joints=NUM_HEATMAPS, **HM_PARSER_PARAMS)
         self.flip_test = bool(flip_test)
         self.flip_index = None if flip_index is None else [int(q) for q in flip_index]
-        if self.flip_test and not self.parser.tag_per_joint:
+        self.ags = bool(ags)
+        if self.flip_test and not self.parser.tag_per_joint and not self.ags:
             raise ValueError("TeacherPipeline: the flip test needs a parser with tag_per_joint=True")
         self.scale_factors = None
         self.max_forward_pixels = int(max_forward_pixels)
         if scale_factors is not None:
             from .inference import check_scale_factors
             self.scale_factors = check_scale_factors(scale_factors)
-            if not self.parser.tag_per_joint:
+            if not self.parser.tag_per_joint and not self.ags:
                 raise ValueError("TeacherPipeline: the multi-scale test needs a parser with tag_per_joint=True")
 
     def _ms_inputs(self, images):
@@ -176,7 +184,7 @@ class TeacherPipeline:
         base = self.scale_factors.index(1)
         hw = tuple(out_hw) if out_hw is not None else tuple(xs[base].shape[2:])
         return self.parser.ms_begin(xs[0].shape[0], [(x.shape[2] // 2, x.shape[3] // 2) for x in xs], hw,
-                                    self.scale_factors, self.flip_test, self.flip_index, self.device)
+                                    self.scale_factors, self.flip_test, self.flip_index, self.device, self.ags)
 
     def _ms_forwards(self, xs, fwd, on_outputs):
         """every scale's forward (and that of the mirror image) in sub-batches, in scale order, on the current stream;

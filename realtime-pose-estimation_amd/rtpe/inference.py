@@ -164,16 +164,22 @@ def group_by_input_size(sizes):
 
 
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
-                        device="cuda"):
+                        device="cuda", ags=False):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
     flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
     warped to its network input size, images of one size are batched (``batch_size`` at a time) through
     ``TeacherPipeline(flip_test=True).stream`` - both forwards on the GPU, the decode from the network outputs
     (``HeatmapParser.parse_flip``) - and the keypoints are mapped back with ``get_final_preds``.  Returns
     ``[(final_results, scores)]`` in input order, each bit-identical to the first two items the per-image call
-    returns (the forward is batch-invariant)."""
+    returns (the forward is batch-invariant).
+
+    ``ags=True``: the drop-in for ``multi_scale_inference(model, parser, img, input_size, (1,), True, True,
+    ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there)."""
     from .engine import TeacherPipeline
     from .third_party import transforms
+    if ags:
+        return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
+                                           device=device, ags=True)
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
     if batch_size < 1:
@@ -233,7 +239,8 @@ def multi_scale_input_sizes(image, input_size, scale_factors):
 
 
 def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
-                                adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda"):
+                                adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda",
+                                ags=False):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
     project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
     sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
@@ -242,19 +249,26 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     (``HeatmapParser.parse_multi_scale``) - and the keypoints are mapped back with ``get_final_preds`` and the
     centre / scale of the smallest-scale warp (what the per-image loop's last iteration leaves).  Returns
     ``[(final_results, scores)]`` in input order, each bit-identical to the first two items the per-image call
-    returns.  The scales and every input size are checked before any GPU work."""
+    returns.  The scales and every input size are checked before any GPU work.
+
+    ``ags=True``: the drop-in for the per-image call with ``ags=True``, its quirks included: the decode adjusts and
+    refines whatever ``adjust`` / ``refine`` say (the pipeline always does both), and ``parser.tag_per_joint`` is set to
+    False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
     from .third_party import transforms
     scales = check_scale_factors(scale_factors)
-    if not parser.tag_per_joint:
+    if not ags and not parser.tag_per_joint:
         raise ValueError("multi_scale_batch_inference: needs a parser with tag_per_joint=True")
     if batch_size < 1:
         raise ValueError("multi_scale_batch_inference: batch_size must be positive")
     images = list(images)
     sizes = [multi_scale_input_sizes(img, input_size, scales) for img in images]
     lo, base = min(scales), scales.index(1)
+    if ags:
+        parser.tag_per_joint = False                                    # as multi_scale_inference(..., ags=True)
     pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
-                           max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels)
+                           max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels,
+                           ags=ags)
     out = [None] * len(images)
     for key, idx in group_by_input_size(sizes):
         w, h = key[base]

@@ -1,0 +1,159 @@
+"""Throughput of the batched AGS test (one tag map per image, shared by all joints) beside the per-joint tag decode of
+the same protocols, on one GPU.
+
+In one process: seeded synthetic W0 weights, resident synthetic batches (batch 32, 640 x 640 at scale 1), then for
+the single-scale + flip protocol and the multi-scale + flip protocol (default scales (2, 1, 0.5)):
+  * img/s of TeacherPipeline.stream with ags=False and ags=True (and of the parse_flip pipeline, flip_test=True
+    without scale_factors, the non-AGS single-scale path of flip_test_inference); both pipelines warmed up first, then
+    timed in the order A B B A ... (--repeats runs each), the median reported beside every run;
+  * per batch, every step alone: the GPU time of the decode's device phases (prep, top-k, adjust + refine; the host
+    matching is not counted) and the bytes of the maps buffer.
+Prints one JSON line.  Needs a GPU; there is no fallback.
+
+    python tools/ags_bench.py [--steps 6] [--warmup 2] [--repeats 4] [--decode-reps 5]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "realtime-pose-estimation_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--size", type=int, default=640)
+    ap.add_argument("--scales", type=str, default="2,1,0.5")
+    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--decode-reps", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=4, help="timed runs per pipeline, interleaved A B B A ...")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ags_bench: no GPU (the AGS test runs on the HIP path only)")
+    import __graft_entry__ as entry
+    entry.build()
+    from oracle import synth
+    from rtpe import _native as nat
+    from rtpe import engine, inference
+    from rtpe.helpers import build_hrnet_w48_teacher
+    torch.set_num_threads(nat.host_threads(8))
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    with open(os.path.join(ROOT, "tests", "golden", "w48_shapes.json")) as f:
+        shapes = {k: tuple(v) for k, v in json.load(f)["shapes"].items()}
+    sd = synth.make_state_dict(shapes, 0, "W0")
+    model = build_hrnet_w48_teacher({"1." + k: v for k, v in sd.items()}).to(dev)
+    B, S = args.batch, args.size
+    scales = inference.check_scale_factors([float(v) if "." in v else int(v) for v in args.scales.split(",")])
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    protocols = {"single": (1,), "multi": scales}
+    data = {name: [[torch.randn(B, 3, int(S * s), int(S * s), generator=g, device=dev) for s in sc] for _ in range(2)]
+            for name, sc in protocols.items()}
+
+    def rate(pipe, batches, steps):
+        people = 0
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for res in pipe.stream((batches[k % len(batches)] for k in range(steps)), (S, S)):
+            people = sum(len(p) if p.ndim == 3 else 0 for p, _ in res)
+        torch.cuda.synchronize(dev)
+        return B * steps / (time.perf_counter() - t0), people
+
+    L = nat.lib()
+
+    def timed(fn, *a):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(*a)
+        e1.record()
+        return out, (e0, e1)
+
+    spans = []
+
+    class Timed:                        # the library with device events around the adjust / refine entries
+        def __getattr__(self, name):
+            fn = getattr(L, name)
+            if not name.startswith("rtpe_adjust_refine"):
+                return fn
+
+            def call(*a):
+                rc, ev = timed(fn, *a)
+                spans.append(ev)
+                return rc
+            return call
+
+    def decode_times(pipe, batches):
+        """one batch at a time, every step alone: the device time of prep / top-k / adjust + refine, and the maps"""
+        P = pipe.parser
+        prep_ms, topk_ms, refine_ms, maps_bytes = [], [], [], 0
+        with torch.no_grad():
+            for r in range(args.decode_reps + 1):
+                batch = batches[r % 2]
+                st = pipe._ms_begin(batch, (S, S))
+                maps_bytes = st["maps"].numel() * 4
+                pr = []
+
+                def on_outputs(i, n0, outs):
+                    pr.append(timed(P.ms_prep, st, i, outs, n0)[1])
+                pipe._ms_forwards(batch, model, on_outputs)
+                _, tk = timed(P.ms_topk, st)
+                real, nat._lib = nat._lib, Timed()
+                spans.clear()
+                try:
+                    P.lowres_match(st)
+                    P.lowres_finish(st)
+                finally:
+                    nat._lib = real
+                torch.cuda.synchronize(dev)
+                if r == 0:
+                    continue
+                prep_ms.append(sum(a.elapsed_time(b) for a, b in pr))
+                topk_ms.append(tk[0].elapsed_time(tk[1]))
+                refine_ms.append(sum(a.elapsed_time(b) for a, b in spans))
+        med = lambda v: round(float(np.median(v)), 3)      # noqa: E731
+        return {"prep": med(prep_ms), "topk": med(topk_ms), "adjust_refine": med(refine_ms),
+                "total": med(np.array(prep_ms) + np.array(topk_ms) + np.array(refine_ms))}, maps_bytes
+
+    out = {"metric": "ags_test_throughput", "batch": B, "size": S, "flip": True, "steps": args.steps, "repeats": args.repeats,
+           "weights": "W0", "device": torch.cuda.get_device_name(dev)}
+    flip = engine.TeacherPipeline(model, device=dev, flip_test=True)
+    xs1 = [b[0] for b in data["single"]]
+    rate(flip, xs1, args.warmup)
+    out["parse_flip_img_s"], people_flip = rate(flip, xs1, max(args.steps, 10))
+    out["parse_flip_img_s"] = round(out["parse_flip_img_s"], 1)
+    people = {"parse_flip": people_flip}
+    for name, sc in protocols.items():
+        steps = max(args.steps, 10) if len(sc) == 1 else args.steps
+        res = {"scales": list(sc)}
+        pipes = {key: engine.TeacherPipeline(model, device=dev, flip_test=True, scale_factors=sc, ags=key == "ags")
+                 for key in ("per_joint_tags", "ags")}
+        for pipe in pipes.values():
+            rate(pipe, data[name], args.warmup)
+        runs = {key: [] for key in pipes}
+        for r in range(args.repeats):
+            for key in (("per_joint_tags", "ags") if r % 2 == 0 else ("ags", "per_joint_tags")):
+                v, people[name + "_" + key] = rate(pipes[key], data[name], steps)
+                runs[key].append(round(v, 1))
+        for key, pipe in pipes.items():
+            times, nbytes = decode_times(pipe, data[name])
+            res[key] = {"img_s": round(float(np.median(runs[key])), 1), "img_s_runs": runs[key],
+                        "decode_gpu_ms_per_batch": times, "maps_bytes": nbytes}
+        res["ags_over_per_joint_tags"] = round(res["ags"]["img_s"] / res["per_joint_tags"]["img_s"], 4)
+        res["maps_bytes_saved"] = res["per_joint_tags"]["maps_bytes"] - res["ags"]["maps_bytes"]
+        out[name] = res
+    out["people_last_batch"] = people
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
