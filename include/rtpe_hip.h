@@ -613,6 +613,55 @@ int rtpe_match_by_tag_batch(const float* tag_k, const int32_t* ind_k, const floa
                             int32_t ignore_too_much, float* ans, int32_t max_people_total,
                             int32_t* person_img, int32_t* counts, int32_t n_threads);
 
+/* match_by_tag for a batch of N images ON THE DEVICE (csrc/match_dev.hip): the grouping of
+ * rtpe_match_by_tag_batch, bit for bit, with nothing passing through the host.  tag_k (N,J,K,D) f32, ind_k (N,J,K)
+ * i32, val_k (N,J,K) f32 as the top-k entries write them (device memory, or pinned host memory the device
+ * addresses).  Outputs, device-visible as well: ans (cap rows of (J,3+D) f32) - the people of all images, image after
+ * image, those of an image in insertion order; person_img[i] = image of row i (ascending); counts[n] = people of image
+ * n; *total = their sum.  Rows beyond *total are not written.  cap >= N*J*K (every candidate founds at most one
+ * person).  Limits: K <= 64, 1 <= max_num_people <= 64, J <= 32, D <= 32 and an LDS need (a function of J, K, D,
+ * max_num_people) of at most 64 KiB - beyond them RTPE_E_INVALID, never another matcher.  Asynchronous on `stream`;
+ * scratch: rtpe_match_by_tag_dev_scratch_bytes(N, J, K, D) bytes of device memory. */
+int rtpe_match_by_tag_dev_scratch_bytes(int32_t N, int32_t J, int32_t K, int32_t D, size_t* bytes);
+int rtpe_match_by_tag_dev(const float* tag_k, const int32_t* ind_k, const float* val_k,
+                          int32_t N, int32_t J, int32_t K, int32_t D, int32_t w,
+                          int32_t max_num_people, double detection_threshold,
+                          double tag_threshold, int32_t use_detection_val,
+                          int32_t ignore_too_much, float* ans, int32_t cap,
+                          int32_t* person_img, int32_t* counts, int32_t* total,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
+/* The adjust + refine entries of the four pipeline kinds with the number of people READ ON THE DEVICE: the
+ * arguments of the entry without the suffix, plus P_dev (not null; device-visible, e.g. `total` of
+ * rtpe_match_by_tag_dev enqueued earlier on the same stream).  P is then the CAPACITY of ans_in, ans_out,
+ * person_img and scores (and what rtpe_adjust_refine_scratch_bytes is asked for); rows, scores and person_img
+ * entries at and beyond *P_dev are neither read nor written.  The first *P_dev rows get the bits the plain entry
+ * gives when called with P = *P_dev. */
+int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                    const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                    int32_t N, int32_t J, int32_t oh, int32_t ow,
+                                    const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                                    int32_t do_adjust, int32_t do_refine, float* scores,
+                                    const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                    void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
+int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
+                              int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
+                              int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                              const float* topk_val, const int32_t* topk_ind, int32_t K,
+                              void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
+int rtpe_adjust_refine_ms_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                            int32_t base, int32_t flip, int32_t oh, int32_t ow, size_t maps_bytes,
+                            const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                            int32_t do_adjust, int32_t do_refine, float* scores,
+                            const float* topk_val, const int32_t* topk_ind, int32_t K,
+                            void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
+int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                size_t maps_bytes, const float* ans_in, float* ans_out,
+                                const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
+                                float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -959,8 +959,9 @@ template <class Map>
 __global__ void __launch_bounds__(64) adjust_prepare_kernel(Map m, int J, int h, int w, int D,
                                                             const float* ans_in, float* ans_out,
                                                             const int* person_img, int do_adjust,
-                                                            float* scores, float* mean_tag) {
+                                                            float* scores, float* mean_tag, const int* P_dev) {
   const int p = blockIdx.x, j = threadIdx.x;
+  if (P_dev != nullptr && p >= *P_dev) return;               // P_dev: the grid covers the capacity, the people end here
   const int row_len = 3 + D;
   const float* kp = ans_in + (size_t)p * J * row_len;
   const int img = person_img ? person_img[p] : 0;
@@ -1125,10 +1126,11 @@ template <class TagMap>
 __global__ void __launch_bounds__(256) refine_shortcut_kernel(TagMap tm, int J, int w, int D, const float* ans_in,
                                                               const int* person_img, int P, const float* mean_tag,
                                                               const u64* plane_key, u64* best_key,
-                                                              unsigned char* need_scan) {
+                                                              unsigned char* need_scan, const int* P_dev) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P * J) return;
   const int p = i / J, j = i - p * J;
+  if (P_dev != nullptr && p >= *P_dev) return;
   const int row_len = 3 + D;
   need_scan[i] = 0;
   if (ans_in[(size_t)i * row_len + 2] != 0.f) return;       // only missing joints are refined
@@ -1162,7 +1164,7 @@ template <class Map, class TagMap, bool kD1>
 __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int J, int h, int w, int D,
                                                           const float* ans_in, const int* person_img, int P,
                                                           const float* mean_tag, u64* best_key,
-                                                          const unsigned char* need_scan) {
+                                                          const unsigned char* need_scan, const int* P_dev) {
   __shared__ int lo_hi[2];
   __shared__ int n_need;
   __shared__ int need[512];
@@ -1171,6 +1173,7 @@ __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int 
   const int plane = blockIdx.y, img = plane / J, j = plane - img * J;
   const int row_len = 3 + D;
   if (threadIdx.x == 0) {
+    if (P_dev != nullptr) P = *P_dev;        // P was the capacity: the rows beyond the people were never written
     int lo = 0, hi = P;                      // persons are sorted by image: [lo, hi) = this image
     if (person_img) {
       int a = 0, b = P;
@@ -1295,10 +1298,12 @@ __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int 
 template <class Map>
 __global__ void __launch_bounds__(256) refine_finalize_kernel(Map m, int J, int h, int w, int D,
                                                               const float* ans_in, float* ans_out,
-                                                              const int* person_img, int P, const u64* best_key) {
+                                                              const int* person_img, int P, const u64* best_key,
+                                                              const int* P_dev) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P * J) return;
   const int p = i / J, j = i - p * J;
+  if (P_dev != nullptr && p >= *P_dev) return;
   const int row_len = 3 + D;
   if (ans_in[(size_t)i * row_len + 2] != 0.f) return;
   const u64 key = best_key[i];
@@ -1327,12 +1332,16 @@ template <class Map, class TagMap>
 static int adjust_refine_run(const Map& m, const TagMap& tm, int n_img, int J, int h, int w, int D,
                              const float* ans_in, float* ans_out, const int* person_img, int P, int do_adjust,
                              int do_refine, float* scores, void* scratch, size_t scratch_bytes, hipStream_t s,
-                             const float* topk_val = nullptr, const int* topk_ind = nullptr, int topk_k = 0) {
+                             const float* topk_val = nullptr, const int* topk_ind = nullptr, int topk_k = 0,
+                             const int32_t* P_dev = nullptr) {
+  // P_dev (device-visible): the number of people is read on the device and P is the capacity of the buffers - the
+  // grids, the best_key memset and the offsets inside the scratch buffer are sized by P as ever, the kernels that
+  // index people return at once for p >= *P_dev.  Null: P people, the launches as they always were.
   RTPE_REQUIRE(scratch && scratch_bytes >= refine_scratch(P, J, D), "adjust_refine: scratch too small");
   u64* best_key = reinterpret_cast<u64*>(scratch);
   float* mean_tag = reinterpret_cast<float*>(best_key + (size_t)P * J);
   hipLaunchKernelGGL((adjust_prepare_kernel<Map>), dim3(P), dim3(64), 0, s, m, J, h, w, D, ans_in, ans_out,
-                     person_img, do_adjust, scores, mean_tag);
+                     person_img, do_adjust, scores, mean_tag, P_dev);
   RTPE_HIP_CHECK(hipGetLastError());
   if (!do_refine) return RTPE_OK;
   RTPE_HIP_CHECK(hipMemsetAsync(best_key, 0, (size_t)P * J * sizeof(u64), s));
@@ -1353,18 +1362,18 @@ static int adjust_refine_run(const Map& m, const TagMap& tm, int n_img, int J, i
                        plane_key, 24 * 1024 / 4, known);
     RTPE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((refine_shortcut_kernel<TagMap>), dim3((P * J + 255) / 256), dim3(256), 0, s, tm, J, w, D, ans_in,
-                       person_img, P, mean_tag, plane_key, best_key, need_scan);
+                       person_img, P, mean_tag, plane_key, best_key, need_scan, P_dev);
     RTPE_HIP_CHECK(hipGetLastError());
   }
   if (D == 1)
     hipLaunchKernelGGL((refine_scan_kernel<Map, TagMap, true>), dim3(kRefineStripes, n_img * J), dim3(256), 0, s,
-                       m, tm, J, h, w, D, ans_in, person_img, P, mean_tag, best_key, need_scan);
+                       m, tm, J, h, w, D, ans_in, person_img, P, mean_tag, best_key, need_scan, P_dev);
   else
     hipLaunchKernelGGL((refine_scan_kernel<Map, TagMap, false>), dim3(kRefineStripes, n_img * J), dim3(256), 0, s,
-                       m, tm, J, h, w, D, ans_in, person_img, P, mean_tag, best_key, need_scan);
+                       m, tm, J, h, w, D, ans_in, person_img, P, mean_tag, best_key, need_scan, P_dev);
   RTPE_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL((refine_finalize_kernel<Map>), dim3((P * J + 255) / 256), dim3(256), 0, s, m, J, h, w, D,
-                     ans_in, ans_out, person_img, P, best_key);
+                     ans_in, ans_out, person_img, P, best_key, P_dev);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
@@ -1575,6 +1584,22 @@ extern "C" int rtpe_adjust_refine_fused(const float* hm, int32_t hh, int32_t hw,
                            scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int adjust_refine_fused_topk_impl(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                             const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
+                                             int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
+                                             const int32_t* person_img, int32_t P, int32_t do_adjust,
+                                             int32_t do_refine, float* scores, const float* topk_val,
+                                             const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
+                                             void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(hm && tg && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
+               topk_val && topk_ind && K > 0, "adjust_refine_fused_topk: bad argument");
+  if (P <= 0) return RTPE_OK;
+  BilinearMap m = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
+  BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
+  return adjust_refine_run(m, tm, N, J, oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores,
+                           scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+}
+
 extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
                                              const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
                                              int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
@@ -1582,13 +1607,25 @@ extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_
                                              int32_t do_refine, float* scores, const float* topk_val,
                                              const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
                                              void* stream) {
-  RTPE_REQUIRE(hm && tg && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
-               topk_val && topk_ind && K > 0, "adjust_refine_fused_topk: bad argument");
-  if (P <= 0) return RTPE_OK;
-  BilinearMap m = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
-  BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
-  return adjust_refine_run(m, tm, N, J, oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores,
-                           scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+  return adjust_refine_fused_topk_impl(hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow, ans_in,
+                                       ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                                       scratch, scratch_bytes, stream, nullptr);
+}
+
+// rtpe_adjust_refine_fused_topk with the number of people read on the device: P is the capacity of ans_in /
+// ans_out / person_img / scores and of the scratch buffer, *P_dev (device-visible, written by an earlier
+// command of the stream) the number of people.  The same for the other three pipeline kinds below.
+extern "C" int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                             const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
+                                             int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
+                                             const int32_t* person_img, int32_t P, int32_t do_adjust,
+                                             int32_t do_refine, float* scores, const float* topk_val,
+                                             const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
+                                             void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_n: P_dev is null");
+  return adjust_refine_fused_topk_impl(hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow, ans_in,
+                                       ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                                       scratch, scratch_bytes, stream, P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -1664,11 +1701,11 @@ extern "C" int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_
                   K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes, s);
 }
 
-extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
+static int adjust_refine_flip_impl(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
                                        int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
                                        int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
                                        const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                       size_t scratch_bytes, void* stream) {
+                                       size_t scratch_bytes, void* stream, const int32_t* P_dev) {
   RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
                    h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && N * J <= 65535,
                "adjust_refine_flip: bad argument (1 <= J <= %d)", kMaxJ);
@@ -1677,7 +1714,26 @@ extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2
   if (P <= 0) return RTPE_OK;
   return adjust_refine_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N, J, oh, ow,
                            2, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch, scratch_bytes,
-                           reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+                           reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+}
+
+extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
+                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                       size_t scratch_bytes, void* stream) {
+  return adjust_refine_flip_impl(maps, h2, w2, N, J, oh, ow, ans_in, ans_out, person_img, P, do_adjust, do_refine,
+                                 scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream, nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
+                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                       size_t scratch_bytes, void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_flip_n: P_dev is null");
+  return adjust_refine_flip_impl(maps, h2, w2, N, J, oh, ow, ans_in, ans_out, person_img, P, do_adjust, do_refine,
+                                 scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream, P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -1852,12 +1908,12 @@ extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, 
                   reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+static int adjust_refine_ms_impl(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                      const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
                                      size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
                                      int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
                                      const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream) {
+                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
   MsLayout L;
   const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
   if (rc != RTPE_OK) return rc;
@@ -1870,7 +1926,30 @@ extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, in
   if (P <= 0) return RTPE_OK;
   return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N,
                            J, oh, ow, 1 + flip, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
-                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+}
+
+extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                     size_t scratch_bytes, void* stream) {
+  return adjust_refine_ms_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img, P,
+                               do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream,
+                               nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_ms_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_n: P_dev is null");
+  return adjust_refine_ms_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img, P,
+                               do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream,
+                               P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -1925,12 +2004,12 @@ extern "C" int rtpe_topk_ms_ags(const float* maps, int32_t N, int32_t J, int32_t
                   reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+static int adjust_refine_ms_ags_impl(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                          const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
                                          size_t maps_bytes, const float* ans_in, float* ans_out,
                                          const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
                                          float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                         void* scratch, size_t scratch_bytes, void* stream) {
+                                         void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev) {
   MsLayout L;
   const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
   if (rc != RTPE_OK) return rc;
@@ -1943,5 +2022,28 @@ extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J
   if (P <= 0) return RTPE_OK;
   return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_ags_tag(maps, L, S, J, h2, w2, oh, ow), N, J,
                            oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
-                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K);
+                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+}
+
+extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                         const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                         size_t maps_bytes, const float* ans_in, float* ans_out,
+                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
+                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                         void* scratch, size_t scratch_bytes, void* stream) {
+  return adjust_refine_ms_ags_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img,
+                                   P, do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes,
+                                   stream, nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                         const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                         size_t maps_bytes, const float* ans_in, float* ans_out,
+                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
+                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                         void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_ags_n: P_dev is null");
+  return adjust_refine_ms_ags_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img,
+                                   P, do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes,
+                                   stream, P_dev);
 }

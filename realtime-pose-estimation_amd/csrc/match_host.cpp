@@ -2,8 +2,11 @@
 // (rtpe/third_party/group.py:26-97 of the reference) with the Kuhn-Munkres
 // assignment that the reference gets from the PyPI package `munkres`
 // (group.py:14,19-23).  Sequential by construction (joint j depends on the
-// people built from joints < j), tiny (<= 30 x 30 per joint), so it stays on the
-// host - in C++ instead of numpy + pure-Python Munkres.
+// people built from joints < j), tiny (<= 30 x 30 per joint) - in C++ instead of
+// numpy + pure-Python Munkres.  This is the DEFAULT matcher of the decode and the
+// SPECIFICATION of the device kernel (match_dev.hip, HeatmapParser(match_on=
+// "device")), which restates match_image() below for one wavefront per image and
+// is tested against it bit for bit: a change here is a change there.
 //
 // The arithmetic follows numpy's: rows are float64 (int64 locations, float32
 // values and tags promoted), tag means are float32 with numpy's reduction

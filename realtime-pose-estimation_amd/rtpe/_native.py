@@ -150,7 +150,15 @@ _SIGS = {
     "rtpe_match_by_tag_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_double, c_double, c_int32, c_int32, c_void_p,
                                           c_int32, c_void_p, c_void_p, c_int32]),
+    "rtpe_match_by_tag_dev_scratch_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_match_by_tag_dev": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_int32, c_double, c_double, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+# adjust + refine with the number of people read on the device: the plain entry's arguments + P_dev
+for _name in ("rtpe_adjust_refine_fused_topk", "rtpe_adjust_refine_flip", "rtpe_adjust_refine_ms",
+              "rtpe_adjust_refine_ms_ags"):
+    _SIGS[_name + "_n"] = (c_int32, _SIGS[_name][1] + [c_void_p])
 
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -146,15 +146,23 @@ class TeacherPipeline:
     ``ags=True`` (needs ``scale_factors``; ``(1,)`` for the single-scale protocol): the AGS branch of
     ``multi_scale_inference(..., ags=True)`` - one tag map per image, channel 0 of the un-mirrored tag maps of the
     smallest scale, shared by all joints; any parser is accepted (its ``tag_per_joint`` is not read).  People carry 4
-    columns, with or without flip."""
+    columns, with or without flip.
+
+    ``match_on``: ``"host"`` / ``"device"`` sets the parser's ``match_on`` (where the candidates are grouped into
+    people, ``HeatmapParser``); None leaves the parser as it is.  With ``"device"`` the ``lowres_match`` call of
+    ``stream()`` blocks on nothing; the order of the loop and the two-step delay of the results stay."""
 
     def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
-                 max_forward_pixels=MAX_FORWARD_PIXELS, ags=False):
+                 max_forward_pixels=MAX_FORWARD_PIXELS, ags=False, match_on=None):
         if ags and scale_factors is None:       # (before any GPU work)
             raise ValueError("TeacherPipeline: ags=True needs scale_factors (use (1,) for the single-scale protocol)")
+        if match_on not in (None, "host", "device"):
+            raise ValueError("TeacherPipeline: match_on must be None, 'host' or 'device', not %r" % (match_on,))
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.model = model.to(self.device).eval()
         self.parser = parser or HeatmapParser(num_joints=NUM_HEATMAPS, **HM_PARSER_PARAMS)
+        if match_on is not None:                # None: the parser as it is
+            self.parser.match_on = match_on
         self.flip_test = bool(flip_test)
         self.flip_index = None if flip_index is None else [int(q) for q in flip_index]
         self.ags = bool(ags)

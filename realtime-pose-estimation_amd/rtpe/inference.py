@@ -163,8 +163,15 @@ def group_by_input_size(sizes):
     return list(groups.items())
 
 
+def _match_kw(match_on):
+    """the ``match_on`` keyword of ``TeacherPipeline``, checked before any GPU work; absent when None"""
+    if match_on not in (None, "host", "device"):
+        raise ValueError("match_on must be None, 'host' or 'device', not %r" % (match_on,))
+    return {} if match_on is None else {"match_on": match_on}
+
+
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
-                        device="cuda", ags=False):
+                        device="cuda", ags=False, match_on=None):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
     flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
     warped to its network input size, images of one size are batched (``batch_size`` at a time) through
@@ -174,19 +181,22 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     returns (the forward is batch-invariant).
 
     ``ags=True``: the drop-in for ``multi_scale_inference(model, parser, img, input_size, (1,), True, True,
-    ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there)."""
+    ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there).
+
+    ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``: where the candidates are grouped into
+    people; None leaves the parser as it is)."""
     from .engine import TeacherPipeline
     from .third_party import transforms
     if ags:
         return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
-                                           device=device, ags=True)
+                                           device=device, ags=True, **_match_kw(match_on))
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
     if batch_size < 1:
         raise ValueError("flip_test_inference: batch_size must be positive")
     images = list(images)
     sizes = [transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0] for img in images]
-    pipe = TeacherPipeline(model, parser, device=device, flip_test=True)
+    pipe = TeacherPipeline(model, parser, device=device, flip_test=True, **_match_kw(match_on))
     out = [None] * len(images)
     for (w, h), idx in group_by_input_size(sizes):
         chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
@@ -240,7 +250,7 @@ def multi_scale_input_sizes(image, input_size, scale_factors):
 
 def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
                                 adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda",
-                                ags=False):
+                                ags=False, match_on=None):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
     project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
     sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
@@ -253,7 +263,9 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
 
     ``ags=True``: the drop-in for the per-image call with ``ags=True``, its quirks included: the decode adjusts and
     refines whatever ``adjust`` / ``refine`` say (the pipeline always does both), and ``parser.tag_per_joint`` is set to
-    False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``."""
+    False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``.
+
+    ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is)."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
     from .third_party import transforms
     scales = check_scale_factors(scale_factors)
@@ -268,7 +280,7 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
         parser.tag_per_joint = False                                    # as multi_scale_inference(..., ags=True)
     pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
                            max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels,
-                           ags=ags)
+                           ags=ags, **_match_kw(match_on))
     out = [None] * len(images)
     for key, idx in group_by_input_size(sizes):
         w, h = key[base]
