@@ -1538,17 +1538,6 @@ extern "C" int rtpe_topk(const float* det, const float* tag, int32_t planes, int
                   scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int rtpe_topk_fused(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
-                               int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J, int32_t oh,
-                               int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
-                               int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
-  RTPE_REQUIRE(hm && tg && val_k && ind_k && tag_k && scratch && N > 0 && J > 0, "topk_fused: bad argument");
-  BilinearMap m = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
-  BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
-  return topk_run(m, tm, N * J, 0, 1, oh, ow, K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes,
-                  reinterpret_cast<hipStream_t>(stream));
-}
-
 extern "C" int rtpe_adjust_refine_scratch_bytes(int32_t P, int32_t J, int32_t D, size_t* bytes) {
   RTPE_REQUIRE(bytes && P >= 0 && J > 0 && D > 0, "adjust_refine_scratch_bytes: bad argument");
   *bytes = refine_scratch(P, J, D);
@@ -1569,35 +1558,116 @@ extern "C" int rtpe_adjust_refine(const float* det, const float* tag, int32_t N,
                            scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---------------------------------------------------------------------------
+// The batch decodes.  Every kind runs the same device stages over its own samplers: [prepare the maps,] fused NMS +
+// top-k + tag gather (decode_topk), then - after the grouping - adjust + refine (decode_adjust_refine).  A kind is a
+// host struct that holds the leading arguments of its entries, "where the maps of the batch are" (N, J, oh, ow among
+// them), and knows two things: check(who) - RTPE_OK or the refusal, the entry's name `who` first in the message - and
+// with_maps(f) - build the samplers and return f(Map, TagMap, D).  The entries build a kind and call a stage.
+// ---------------------------------------------------------------------------
+struct TopkTables {         // the candidate tables a top-k writes: (N,J,K), (N,J,K), (N,J,K,D)
+  float* val_k;
+  int32_t* ind_k;
+  float* tag_k;
+};
+
+struct RefineTail {         // the ending every adjust + refine entry of the batch decodes shares
+  const float* ans_in;
+  float* ans_out;
+  const int32_t* person_img;
+  int32_t P, do_adjust, do_refine;
+  float* scores;
+  const float* topk_val;    // the top-k table of the same maps (the arg-max shortcut's plane maxima) or null, null, 0
+  const int32_t* topk_ind;
+  int32_t K;
+  void* scratch;
+  size_t scratch_bytes;
+  void* stream;
+};
+
+// what decode_topk refuses before it launches (rtpe_topk_flip asks first: its prepare kernel goes before the top-k)
+template <class Src>
+static int topk_check(const char* who, Src& src, int K, const TopkTables& t, const void* scratch) {
+  const int rc = src.check(who);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(t.val_k && t.ind_k && t.tag_k && scratch, "%s: null argument", who);
+  RTPE_REQUIRE(src.oh > 0 && src.ow > 0 && K > 0, "%s: bad shape", who);
+  return RTPE_OK;
+}
+
+template <class Src>
+static int decode_topk(const char* who, Src src, int K, int ksize, int pad, const TopkTables& t, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  const int rc = topk_check(who, src, K, t, scratch);
+  if (rc != RTPE_OK) return rc;
+  // tag_shared_joints = 0: every kind's tag sampler takes the (image * J + joint) plane index
+  return src.with_maps([&](const auto& m, const auto& tm, int D) {
+    return topk_run(m, tm, src.N * src.J, 0, D, src.oh, src.ow, K, ksize, pad, t.val_k, t.ind_k, t.tag_k, scratch,
+                    scratch_bytes, reinterpret_cast<hipStream_t>(stream));
+  });
+}
+
+// P_dev null: t.P people.  Not null (the _n entries): the number of people is read on the device and t.P is the
+// capacity of ans_in / ans_out / person_img / scores and of the scratch buffer (adjust_refine_run).
+// need_topk: the entry has no form without the top-k table
+template <class Src>
+static int decode_adjust_refine(const char* who, Src src, const RefineTail& t, const int32_t* P_dev,
+                                bool need_topk = false) {
+  const int rc = src.check(who);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(((t.ans_in && t.ans_out && t.ans_in != t.ans_out) || t.P == 0) && src.J <= kMaxJ,
+               "%s: bad argument (ans_in and ans_out: two buffers; J <= %d)", who, kMaxJ);
+  RTPE_REQUIRE((t.topk_val == nullptr) == (t.topk_ind == nullptr) && (t.topk_val == nullptr || t.K > 0) &&
+                   (t.topk_val != nullptr || !need_topk),
+               "%s: topk_val and topk_ind go together (K > 0)%s", who, need_topk ? " and are required" : "");
+  if (t.P <= 0) return RTPE_OK;
+  return src.with_maps([&](const auto& m, const auto& tm, int D) {
+    return adjust_refine_run(m, tm, src.N, src.J, src.oh, src.ow, D, t.ans_in, t.ans_out, t.person_img, t.P,
+                             t.do_adjust, t.do_refine, t.scores, t.scratch, t.scratch_bytes,
+                             reinterpret_cast<hipStream_t>(t.stream), t.topk_val, t.topk_ind, t.K, P_dev);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// the network outputs as they are: refined heat maps and per-joint tag maps, align_corners=True to (oh, ow), D = 1
+// ---------------------------------------------------------------------------
+struct NetSrc {
+  const float* hm;
+  int32_t hh, hw;
+  int64_t hm_img_stride;
+  const float* tg;
+  int32_t th, tw;
+  int64_t tg_img_stride;
+  int32_t N, J, oh, ow;
+  int check(const char* who) const {
+    RTPE_REQUIRE(hm && tg && N > 0 && J > 0, "%s: bad argument", who);
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    return f(make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow),
+             BilinearTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)}, 1);
+  }
+};
+
+extern "C" int rtpe_topk_fused(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
+                               int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J, int32_t oh,
+                               int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
+                               int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_fused", NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow}, K,
+                     nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
 extern "C" int rtpe_adjust_refine_fused(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
                                         const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
                                         int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
                                         const int32_t* person_img, int32_t P, int32_t do_adjust,
                                         int32_t do_refine, float* scores, void* scratch, size_t scratch_bytes,
                                         void* stream) {
-  RTPE_REQUIRE(hm && tg && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ,
-               "adjust_refine_fused: bad argument");
-  if (P <= 0) return RTPE_OK;
-  BilinearMap m = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
-  BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
-  return adjust_refine_run(m, tm, N, J, oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores,
-                           scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
-}
-
-static int adjust_refine_fused_topk_impl(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                             const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
-                                             int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
-                                             const int32_t* person_img, int32_t P, int32_t do_adjust,
-                                             int32_t do_refine, float* scores, const float* topk_val,
-                                             const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                             void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(hm && tg && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
-               topk_val && topk_ind && K > 0, "adjust_refine_fused_topk: bad argument");
-  if (P <= 0) return RTPE_OK;
-  BilinearMap m = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
-  BilinearTag tm{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)};
-  return adjust_refine_run(m, tm, N, J, oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores,
-                           scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+  return decode_adjust_refine("adjust_refine_fused",
+                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, nullptr, nullptr, 0,
+                               scratch, scratch_bytes, stream}, nullptr);
 }
 
 extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
@@ -1607,9 +1677,10 @@ extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_
                                              int32_t do_refine, float* scores, const float* topk_val,
                                              const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
                                              void* stream) {
-  return adjust_refine_fused_topk_impl(hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow, ans_in,
-                                       ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                                       scratch, scratch_bytes, stream, nullptr);
+  return decode_adjust_refine("adjust_refine_fused_topk",
+                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr, true);
 }
 
 // rtpe_adjust_refine_fused_topk with the number of people read on the device: P is the capacity of ans_in /
@@ -1623,33 +1694,76 @@ extern "C" int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int3
                                              const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
                                              void* stream, const int32_t* P_dev) {
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_n: P_dev is null");
-  return adjust_refine_fused_topk_impl(hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow, ans_in,
-                                       ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                                       scratch, scratch_bytes, stream, P_dev);
+  return decode_adjust_refine("adjust_refine_fused_topk_n",
+                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev, true);
+}
+
+// ---------------------------------------------------------------------------
+// The prepare kernels' arguments (flip test and multi-scale test): the checks of the network outputs of the images
+// and, with `flip`, of their mirror images, and the FlipPrepArgs they make - all but plane0 and the output maps.
+// (h2, w2): the refined size of the scale.  J <= kMaxJ is the caller's check.
+// ---------------------------------------------------------------------------
+static int fill_prep(const char* who, const float* preds, int h4, int w4, int64_t preds_st, const float* refined,
+                     int h2, int w2, int64_t refined_st, const float* preds_f, int64_t preds_f_st,
+                     const float* refined_f, int64_t refined_f_st, int J, const int32_t* flip_index, bool flip,
+                     FlipPrepArgs* a) {
+  RTPE_REQUIRE(preds && refined && (!flip || (preds_f && refined_f && flip_index)), "%s: null argument", who);
+  RTPE_REQUIRE(h4 > 0 && w4 > 0, "%s: bad shape", who);
+  RTPE_REQUIRE(preds_st >= (int64_t)2 * J * h4 * w4 && refined_st >= (int64_t)J * h2 * w2 &&
+                   (!flip || (preds_f_st >= (int64_t)2 * J * h4 * w4 && refined_f_st >= (int64_t)J * h2 * w2)),
+               "%s: an image stride is shorter than the image", who);
+  memset(a, 0, sizeof(*a));
+  unsigned seen = 0;
+  for (int j = 0; flip && j < J; ++j) {
+    const int q = flip_index[j];
+    RTPE_REQUIRE(q >= 0 && q < J && !(seen & (1u << q)), "%s: flip_index is not a permutation of 0..%d", who, J - 1);
+    seen |= 1u << q;
+    a->perm[j] = q;
+  }
+  a->p = preds; a->r = refined; a->pf = preds_f; a->rf = refined_f;
+  a->p_st = preds_st; a->r_st = refined_st; a->pf_st = preds_f_st; a->rf_st = refined_f_st;
+  a->J = J; a->h4 = h4; a->w4 = w4; a->h2 = h2; a->w2 = w2;
+  a->sy = (float)h4 / (float)h2;
+  a->sx = (float)w4 / (float)w2;
+  return RTPE_OK;
+}
+
+static dim3 prep_grid(int npix, int planes) {
+  return dim3((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024, planes);
+}
+
+static NcAxes nc_axes(int sh, int sw, int oh, int ow) {
+  NcAxes a;
+  a.sh = sh; a.sw = sw; a.oh = oh; a.ow = ow;
+  a.sy = (float)sh / (float)oh;
+  a.sx = (float)sw / (float)ow;
+  a.ident = sh == oh && sw == ow;
+  return a;
 }
 
 // ---------------------------------------------------------------------------
 // flip test (single scale): rtpe/inference.py multi_scale_inference(scale_factors=(1,), flip_test=True,
-// project2image=True) for a whole batch, the projected maps never built
+// project2image=True) for a whole batch, the projected maps never built.  The maps buffer: A_o, A_f, T_o, T_f of
+// flip_prep_kernel, (N*J, h2, w2) each; D = 2
 // ---------------------------------------------------------------------------
-static FlipHeatMap flip_heat(const float* maps, int N, int J, int h2, int w2, int oh, int ow) {
-  const size_t n = (size_t)N * J * h2 * w2;
-  FlipHeatMap m;
-  m.ao = maps; m.af = maps + n;
-  m.a.sh = h2; m.a.sw = w2; m.a.oh = oh; m.a.ow = ow;
-  m.a.sy = (float)h2 / (float)oh;
-  m.a.sx = (float)w2 / (float)ow;
-  m.a.ident = h2 == oh && w2 == ow;
-  return m;
-}
-
-static FlipTag flip_tag(const float* maps, int N, int J, int h2, int w2, int oh, int ow) {
-  const size_t n = (size_t)N * J * h2 * w2;
-  FlipTag t;
-  t.to = maps + 2 * n; t.tf = maps + 3 * n;
-  t.a = flip_heat(maps, N, J, h2, w2, oh, ow).a;
-  return t;
-}
+struct FlipSrc {
+  const float* maps;
+  int32_t h2, w2, N, J, oh, ow;
+  size_t plane_floats() const { return (size_t)N * J * h2 * w2; }
+  int check(const char* who) const {
+    RTPE_REQUIRE(maps && N > 0 && J > 0 && J <= kMaxJ && h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && N * J <= 65535,
+                 "%s: bad argument (1 <= J <= %d, at most 65535 planes per call)", who, kMaxJ);
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    const size_t n = plane_floats();
+    const NcAxes a = nc_axes(h2, w2, oh, ow);
+    return f(FlipHeatMap{maps, maps + n, a}, FlipTag{maps + 2 * n, maps + 3 * n, a}, 2);
+  }
+};
 
 extern "C" int rtpe_flip_maps_bytes(int32_t N, int32_t J, int32_t h2, int32_t w2, size_t* bytes) {
   RTPE_REQUIRE(bytes && N > 0 && J > 0 && h2 > 0 && w2 > 0, "flip_maps_bytes: bad argument");
@@ -1664,57 +1778,24 @@ extern "C" int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_
                               int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
                               int32_t* ind_k, float* tag_k, float* maps, size_t maps_bytes, void* scratch,
                               size_t scratch_bytes, void* stream) {
-  RTPE_REQUIRE(preds && refined && preds_f && refined_f && flip_index && val_k && ind_k && tag_k && maps && scratch,
-               "topk_flip: null argument");
-  RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "topk_flip: N=%d J=%d (1 <= J <= %d)", N, J, kMaxJ);
-  RTPE_REQUIRE(h4 > 0 && w4 > 0 && h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && K > 0 && (int64_t)h2 * w2 < 0x7fffffff,
-               "topk_flip: bad shape");
-  RTPE_REQUIRE(N * J <= 65535, "topk_flip: at most 65535 planes per call");
-  RTPE_REQUIRE(preds_img_stride >= (int64_t)2 * J * h4 * w4 && preds_f_img_stride >= (int64_t)2 * J * h4 * w4 &&
-                   refined_img_stride >= (int64_t)J * h2 * w2 && refined_f_img_stride >= (int64_t)J * h2 * w2,
-               "topk_flip: an image stride is shorter than the image");
-  size_t need = 0;
-  rtpe_flip_maps_bytes(N, J, h2, w2, &need);
-  RTPE_REQUIRE(maps_bytes >= need, "topk_flip: maps buffer too small (%zu < %zu bytes)", maps_bytes, need);
+  FlipSrc src{maps, h2, w2, N, J, oh, ow};
+  const TopkTables tables{val_k, ind_k, tag_k};
+  int rc = topk_check("topk_flip", src, K, tables, scratch);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE((int64_t)h2 * w2 < 0x7fffffff, "topk_flip: bad shape");
+  const size_t n = src.plane_floats();
+  RTPE_REQUIRE(maps_bytes >= 4 * n * sizeof(float), "topk_flip: maps buffer too small (%zu < %zu bytes)", maps_bytes,
+               4 * n * sizeof(float));
   FlipPrepArgs a;
-  memset(&a, 0, sizeof(a));
-  unsigned seen = 0;
-  for (int j = 0; j < J; ++j) {
-    const int q = flip_index[j];
-    RTPE_REQUIRE(q >= 0 && q < J && !(seen & (1u << q)), "topk_flip: flip_index is not a permutation of 0..%d", J - 1);
-    seen |= 1u << q;
-    a.perm[j] = q;
-  }
-  a.p = preds; a.r = refined; a.pf = preds_f; a.rf = refined_f;
-  a.p_st = preds_img_stride; a.r_st = refined_img_stride; a.pf_st = preds_f_img_stride; a.rf_st = refined_f_img_stride;
-  a.J = J; a.h4 = h4; a.w4 = w4; a.h2 = h2; a.w2 = w2;
-  a.sy = (float)h4 / (float)h2;
-  a.sx = (float)w4 / (float)w2;
-  const size_t n = (size_t)N * J * h2 * w2;
+  rc = fill_prep("topk_flip", preds, h4, w4, preds_img_stride, refined, h2, w2, refined_img_stride, preds_f,
+                 preds_f_img_stride, refined_f, refined_f_img_stride, J, flip_index, true, &a);
+  if (rc != RTPE_OK) return rc;
   a.ao = maps; a.af = maps + n; a.to = maps + 2 * n; a.tf = maps + 3 * n;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int npix = h2 * w2;
-  const int bx = (npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024;
-  hipLaunchKernelGGL(flip_prep_kernel, dim3(bx, N * J), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(flip_prep_kernel, prep_grid(h2 * w2, N * J), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     a);
   RTPE_HIP_CHECK(hipGetLastError());
-  return topk_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N * J, 0, 2, oh, ow,
-                  K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes, s);
-}
-
-static int adjust_refine_flip_impl(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
-                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                       size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && N > 0 && J > 0 && J <= kMaxJ &&
-                   h2 > 0 && w2 > 0 && oh > 0 && ow > 0 && N * J <= 65535,
-               "adjust_refine_flip: bad argument (1 <= J <= %d)", kMaxJ);
-  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
-               "adjust_refine_flip: topk_val and topk_ind go together (K > 0)");
-  if (P <= 0) return RTPE_OK;
-  return adjust_refine_run(flip_heat(maps, N, J, h2, w2, oh, ow), flip_tag(maps, N, J, h2, w2, oh, ow), N, J, oh, ow,
-                           2, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch, scratch_bytes,
-                           reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+  // (repeats topk_check, which passed above: nothing is refused here that was not refused before the launch)
+  return decode_topk("topk_flip", src, K, nms_ksize, nms_pad, tables, scratch, scratch_bytes, stream);
 }
 
 extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
@@ -1722,8 +1803,9 @@ extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2
                                        int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
                                        const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
                                        size_t scratch_bytes, void* stream) {
-  return adjust_refine_flip_impl(maps, h2, w2, N, J, oh, ow, ans_in, ans_out, person_img, P, do_adjust, do_refine,
-                                 scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream, nullptr);
+  return decode_adjust_refine("adjust_refine_flip", FlipSrc{maps, h2, w2, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr);
 }
 
 extern "C" int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
@@ -1732,21 +1814,26 @@ extern "C" int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t 
                                        const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
                                        size_t scratch_bytes, void* stream, const int32_t* P_dev) {
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_flip_n: P_dev is null");
-  return adjust_refine_flip_impl(maps, h2, w2, N, J, oh, ow, ans_in, ans_out, person_img, P, do_adjust, do_refine,
-                                 scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream, P_dev);
+  return decode_adjust_refine("adjust_refine_flip_n", FlipSrc{maps, h2, w2, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev);
 }
 
 // ---------------------------------------------------------------------------
 // multi-scale test: rtpe/inference.py multi_scale_inference(scale_factors, flip_test, project2image=True) for a whole
 // batch, the maps at the projection size never built.  The maps buffer, in floats: per scale i (the loop order,
 // descending) A_o^i then, with flip, A_f^i, each (N*J, h2_i, w2_i); then T_o and, with flip, T_f of the scale-1 entry
-// `base`, (N*J, h2_base, w2_base) each.
+// `base`, (N*J, h2_base, w2_base) each (D = 1 + flip).
+// AGS (multi_scale_inference(..., ags=True)): the heat maps as above, no T_o / T_f; the tag of every joint of image n
+// is ONE plane, rs_(oh,ow)(rs_(h2,w2)(P_L[n, J])) of the smallest scale L = S-1 (D = 1), stored at the refined size of
+// that scale, (N, h2[S-1], w2[S-1]), at offset `to` (`tf` unused) and projected on the fly.
 // ---------------------------------------------------------------------------
 struct MsLayout {
   size_t ao[kMaxScales], af[kMaxScales], to, tf, total;   // float offsets into the maps buffer; total floats
 };
 
-static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, MsLayout* L) {
+static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, bool ags,
+                     MsLayout* L) {
   RTPE_REQUIRE(h2 && w2, "ms: null size array");
   RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "ms: N=%d J=%d (1 <= J <= %d)", N, J, kMaxJ);
   RTPE_REQUIRE((int64_t)N * J <= 65535, "ms: at most 65535 planes per call");
@@ -1763,66 +1850,66 @@ static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, 
     L->af[i] = o;
     if (flip) o += n;
   }
-  const size_t nb = (size_t)N * J * h2[base] * w2[base];
+  const size_t nb = ags ? (size_t)N * h2[S - 1] * w2[S - 1] : (size_t)N * J * h2[base] * w2[base];
   L->to = o;
   o += nb;
-  L->tf = o;
-  if (flip) o += nb;
+  L->tf = ags ? L->to : o;
+  if (flip && !ags) o += nb;
   L->total = o;
   return RTPE_OK;
 }
 
-// AGS (multi_scale_inference(..., ags=True)): per scale A_o and, with flip, A_f as above, no T_o / T_f; then ONE tag
-// plane per image at the refined size of the smallest scale S-1, (N, h2[S-1], w2[S-1]), at offset `to` (`tf` unused)
-static int ms_ags_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, MsLayout* L) {
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, L);     // the checks, and the heat maps' offsets
-  if (rc != RTPE_OK) return rc;
-  L->tf = L->to;                                                // the end of the heat maps
-  L->total = L->to + (size_t)N * h2[S - 1] * w2[S - 1];
-  return RTPE_OK;
-}
-
-static NcAxes nc_axes(int sh, int sw, int oh, int ow) {
-  NcAxes a;
-  a.sh = sh; a.sw = sw; a.oh = oh; a.ow = ow;
-  a.sy = (float)sh / (float)oh;
-  a.sx = (float)sw / (float)ow;
-  a.ident = sh == oh && sw == ow;
-  return a;
-}
-
-static MultiScaleHeatMap ms_heat(const float* maps, const MsLayout& L, int S, const int32_t* h2, const int32_t* w2,
-                                 int flip, int oh, int ow) {
-  MultiScaleHeatMap m;
-  memset(&m, 0, sizeof(m));
-  m.S = S;
-  m.flip = flip != 0;
-  for (int i = 0; i < S; ++i) {
-    m.ao[i] = maps + L.ao[i];
-    m.af[i] = flip ? maps + L.af[i] : nullptr;
-    m.a[i] = nc_axes(h2[i], w2[i], oh, ow);
+struct MsSrc {
+  const float* maps;
+  int32_t N, J, S;
+  const int32_t *h2, *w2;
+  int32_t base, flip, oh, ow;
+  size_t maps_bytes;
+  bool ags;
+  MsLayout L;               // filled by check()
+  int check(const char* who) {
+    const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
+    if (rc != RTPE_OK) return rc;
+    RTPE_REQUIRE(maps && oh > 0 && ow > 0, "%s: bad argument", who);
+    RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "%s: maps buffer too small (%zu < %zu bytes)", who, maps_bytes,
+                 L.total * sizeof(float));
+    return RTPE_OK;
   }
-  return m;
-}
+  template <class F>
+  int with_maps(F f) const {
+    MultiScaleHeatMap m;
+    memset(&m, 0, sizeof(m));
+    m.S = S;
+    m.flip = flip != 0;
+    for (int i = 0; i < S; ++i) {
+      m.ao[i] = maps + L.ao[i];
+      m.af[i] = flip ? maps + L.af[i] : nullptr;
+      m.a[i] = nc_axes(h2[i], w2[i], oh, ow);
+    }
+    if (ags) return f(m, AgsTag{maps + L.to, J, nc_axes(h2[S - 1], w2[S - 1], oh, ow)}, 1);
+    // D = 1 + flip: FlipTag's second map is never read with D = 1
+    return f(m, FlipTag{maps + L.to, flip ? maps + L.tf : nullptr, nc_axes(h2[base], w2[base], oh, ow)}, 1 + flip);
+  }
+};
 
-// D = 1 + flip: FlipTag's second map is never read with D = 1
-static FlipTag ms_tag(const float* maps, const MsLayout& L, const int32_t* h2, const int32_t* w2, int base, int flip,
-                      int oh, int ow) {
-  FlipTag t;
-  t.to = maps + L.to;
-  t.tf = flip ? maps + L.tf : nullptr;
-  t.a = nc_axes(h2[base], w2[base], oh, ow);
-  return t;
+static int ms_maps_bytes(const char* who, int N, int J, int S, const int32_t* h2, const int32_t* w2, int base,
+                         int flip, bool ags, size_t* bytes) {
+  RTPE_REQUIRE(bytes, "%s: null argument", who);
+  MsLayout L;
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
+  if (rc != RTPE_OK) return rc;
+  *bytes = L.total * sizeof(float);
+  return RTPE_OK;
 }
 
 extern "C" int rtpe_ms_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2, int32_t base,
                                   int32_t flip, size_t* bytes) {
-  RTPE_REQUIRE(bytes, "ms_maps_bytes: null argument");
-  MsLayout L;
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  *bytes = L.total * sizeof(float);
-  return RTPE_OK;
+  return ms_maps_bytes("ms_maps_bytes", N, J, S, h2, w2, base, flip, false, bytes);
+}
+
+extern "C" int rtpe_ms_ags_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                                      int32_t base, int32_t flip, size_t* bytes) {
+  return ms_maps_bytes("ms_ags_maps_bytes", N, J, S, h2, w2, base, flip, true, bytes);
 }
 
 // rtpe_ms_prep / rtpe_ms_ags_prep: the same checks and arguments; `ags` picks the layout and the kernels
@@ -1833,35 +1920,17 @@ static int ms_prep_impl(const float* preds, int32_t h4, int32_t w4, int64_t pred
                         int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream,
                         bool ags) {
   MsLayout L;
-  const int rc = ags ? ms_ags_layout(N, J, S, h2, w2, base, flip, &L) : ms_layout(N, J, S, h2, w2, base, flip, &L);
+  int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
   if (rc != RTPE_OK) return rc;
-  RTPE_REQUIRE(preds && refined && maps && (!flip || (preds_f && refined_f && flip_index)), "ms_prep: null argument");
+  RTPE_REQUIRE(maps, "ms_prep: null argument");
   RTPE_REQUIRE(scale >= 0 && scale < S, "ms_prep: scale %d of %d", scale, S);
   RTPE_REQUIRE(n > 0 && n0 >= 0 && (int64_t)n0 + n <= N, "ms_prep: images %d..%d of %d", n0, n0 + n - 1, N);
-  RTPE_REQUIRE(h4 > 0 && w4 > 0, "ms_prep: bad shape");
   RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "ms_prep: maps buffer too small (%zu < %zu bytes)", maps_bytes,
                L.total * sizeof(float));
-  const int hs = h2[scale], ws = w2[scale];
-  RTPE_REQUIRE(preds_img_stride >= (int64_t)2 * J * h4 * w4 && refined_img_stride >= (int64_t)J * hs * ws &&
-                   (!flip || (preds_f_img_stride >= (int64_t)2 * J * h4 * w4 &&
-                              refined_f_img_stride >= (int64_t)J * hs * ws)),
-               "ms_prep: an image stride is shorter than the image");
   FlipPrepArgs a;
-  memset(&a, 0, sizeof(a));
-  if (flip) {
-    unsigned seen = 0;
-    for (int j = 0; j < J; ++j) {
-      const int q = flip_index[j];
-      RTPE_REQUIRE(q >= 0 && q < J && !(seen & (1u << q)), "ms_prep: flip_index is not a permutation of 0..%d", J - 1);
-      seen |= 1u << q;
-      a.perm[j] = q;
-    }
-  }
-  a.p = preds; a.r = refined; a.pf = preds_f; a.rf = refined_f;
-  a.p_st = preds_img_stride; a.r_st = refined_img_stride; a.pf_st = preds_f_img_stride; a.rf_st = refined_f_img_stride;
-  a.J = J; a.h4 = h4; a.w4 = w4; a.h2 = hs; a.w2 = ws;
-  a.sy = (float)h4 / (float)hs;
-  a.sx = (float)w4 / (float)ws;
+  rc = fill_prep("ms_prep", preds, h4, w4, preds_img_stride, refined, h2[scale], w2[scale], refined_img_stride,
+                 preds_f, preds_f_img_stride, refined_f, refined_f_img_stride, J, flip_index, flip != 0, &a);
+  if (rc != RTPE_OK) return rc;
   a.plane0 = n0 * J;
   a.ao = maps + L.ao[scale];
   a.af = flip ? maps + L.af[scale] : nullptr;
@@ -1870,8 +1939,7 @@ static int ms_prep_impl(const float* preds, int32_t h4, int32_t w4, int64_t pred
   a.to = tags || ags_tag ? maps + L.to : nullptr;
   a.tf = tags && flip ? maps + L.tf : nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int npix = hs * ws;
-  const dim3 grid((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024, n * J);
+  const dim3 grid = prep_grid(h2[scale] * w2[scale], n * J);
   if (ags_tag && flip) hipLaunchKernelGGL((ags_prep_kernel<true>), grid, dim3(256), 0, s, a);
   else if (ags_tag) hipLaunchKernelGGL((ags_prep_kernel<false>), grid, dim3(256), 0, s, a);
   else if (flip && tags) hipLaunchKernelGGL((ms_prep_kernel<true, true>), grid, dim3(256), 0, s, a);
@@ -1892,90 +1960,6 @@ extern "C" int rtpe_ms_prep(const float* preds, int32_t h4, int32_t w4, int64_t 
                       maps_bytes, stream, false);
 }
 
-extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
-                            int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize,
-                            int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
-                            void* scratch, size_t scratch_bytes, void* stream) {
-  MsLayout L;
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  RTPE_REQUIRE(maps && val_k && ind_k && tag_k && scratch, "topk_ms: null argument");
-  RTPE_REQUIRE(oh > 0 && ow > 0 && K > 0, "topk_ms: bad shape");
-  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "topk_ms: maps buffer too small (%zu < %zu bytes)", maps_bytes,
-               L.total * sizeof(float));
-  return topk_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N * J, 0,
-                  1 + flip, oh, ow, K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes,
-                  reinterpret_cast<hipStream_t>(stream));
-}
-
-static int adjust_refine_ms_impl(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  MsLayout L;
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && oh > 0 && ow > 0,
-               "adjust_refine_ms: bad argument");
-  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "adjust_refine_ms: maps buffer too small (%zu < %zu bytes)",
-               maps_bytes, L.total * sizeof(float));
-  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
-               "adjust_refine_ms: topk_val and topk_ind go together (K > 0)");
-  if (P <= 0) return RTPE_OK;
-  return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_tag(maps, L, h2, w2, base, flip, oh, ow), N,
-                           J, oh, ow, 1 + flip, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
-                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
-}
-
-extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream) {
-  return adjust_refine_ms_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img, P,
-                               do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream,
-                               nullptr);
-}
-
-extern "C" int rtpe_adjust_refine_ms_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_n: P_dev is null");
-  return adjust_refine_ms_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img, P,
-                               do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes, stream,
-                               P_dev);
-}
-
-// ---------------------------------------------------------------------------
-// AGS multi-scale test: multi_scale_inference(..., ags=True) for a whole batch.  Heat maps as above; the tag of every
-// joint of image n is ONE plane, rs_(oh,ow)(rs_(h2,w2)(P_L[n, J])) of the smallest scale L = S-1 (D = 1), stored at
-// the refined size of that scale (ms_ags_layout) and projected on the fly.
-// ---------------------------------------------------------------------------
-static AgsTag ms_ags_tag(const float* maps, const MsLayout& L, int S, int J, const int32_t* h2, const int32_t* w2,
-                         int oh, int ow) {
-  AgsTag t;
-  t.p = maps + L.to;
-  t.J = J;
-  t.a = nc_axes(h2[S - 1], w2[S - 1], oh, ow);
-  return t;
-}
-
-extern "C" int rtpe_ms_ags_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
-                                      int32_t base, int32_t flip, size_t* bytes) {
-  RTPE_REQUIRE(bytes, "ms_ags_maps_bytes: null argument");
-  MsLayout L;
-  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  *bytes = L.total * sizeof(float);
-  return RTPE_OK;
-}
-
 extern "C" int rtpe_ms_ags_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
                                 const float* refined, int64_t refined_img_stride, const float* preds_f,
                                 int64_t preds_f_img_stride, const float* refined_f, int64_t refined_f_img_stride,
@@ -1987,42 +1971,43 @@ extern "C" int rtpe_ms_ags_prep(const float* preds, int32_t h4, int32_t w4, int6
                       maps_bytes, stream, true);
 }
 
+extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                            int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize,
+                            int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_ms", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false}, K, nms_ksize,
+                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
 extern "C" int rtpe_topk_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                 const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K,
                                 int32_t nms_ksize, int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k,
                                 size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  MsLayout L;
-  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  RTPE_REQUIRE(maps && val_k && ind_k && tag_k && scratch, "topk_ms_ags: null argument");
-  RTPE_REQUIRE(oh > 0 && ow > 0 && K > 0, "topk_ms_ags: bad shape");
-  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "topk_ms_ags: maps buffer too small (%zu < %zu bytes)",
-               maps_bytes, L.total * sizeof(float));
-  // tag_shared_joints = 0: AgsTag maps the plane to its image
-  return topk_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_ags_tag(maps, L, S, J, h2, w2, oh, ow), N * J, 0, 1,
-                  oh, ow, K, nms_ksize, nms_pad, val_k, ind_k, tag_k, scratch, scratch_bytes,
-                  reinterpret_cast<hipStream_t>(stream));
+  return decode_topk("topk_ms_ags", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true}, K, nms_ksize,
+                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
 }
 
-static int adjust_refine_ms_ags_impl(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                         const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                         size_t maps_bytes, const float* ans_in, float* ans_out,
-                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
-                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                         void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  MsLayout L;
-  const int rc = ms_ags_layout(N, J, S, h2, w2, base, flip, &L);
-  if (rc != RTPE_OK) return rc;
-  RTPE_REQUIRE(maps && ((ans_in && ans_out && ans_in != ans_out) || P == 0) && oh > 0 && ow > 0,
-               "adjust_refine_ms_ags: bad argument");
-  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "adjust_refine_ms_ags: maps buffer too small (%zu < %zu bytes)",
-               maps_bytes, L.total * sizeof(float));
-  RTPE_REQUIRE((topk_val == nullptr) == (topk_ind == nullptr) && (topk_val == nullptr || K > 0),
-               "adjust_refine_ms_ags: topk_val and topk_ind go together (K > 0)");
-  if (P <= 0) return RTPE_OK;
-  return adjust_refine_run(ms_heat(maps, L, S, h2, w2, flip, oh, ow), ms_ags_tag(maps, L, S, J, h2, w2, oh, ow), N, J,
-                           oh, ow, 1, ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, scratch,
-                           scratch_bytes, reinterpret_cast<hipStream_t>(stream), topk_val, topk_ind, K, P_dev);
+extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                     size_t scratch_bytes, void* stream) {
+  return decode_adjust_refine("adjust_refine_ms", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_ms_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
+                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
+                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_ms_n", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev);
 }
 
 extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
@@ -2031,9 +2016,10 @@ extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J
                                          const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
                                          float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
                                          void* scratch, size_t scratch_bytes, void* stream) {
-  return adjust_refine_ms_ags_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img,
-                                   P, do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes,
-                                   stream, nullptr);
+  return decode_adjust_refine("adjust_refine_ms_ags",
+                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr);
 }
 
 extern "C" int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
@@ -2043,7 +2029,8 @@ extern "C" int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t
                                          float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
                                          void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev) {
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_ags_n: P_dev is null");
-  return adjust_refine_ms_ags_impl(maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ans_in, ans_out, person_img,
-                                   P, do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch, scratch_bytes,
-                                   stream, P_dev);
+  return decode_adjust_refine("adjust_refine_ms_ags_n",
+                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev);
 }

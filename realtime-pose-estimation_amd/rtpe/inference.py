@@ -170,6 +170,35 @@ def _match_kw(match_on):
     return {} if match_on is None else {"match_on": match_on}
 
 
+def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk):
+    """the tail of the batched drivers: images of one ``sizes`` entry form a group (``entry[base]`` is its
+    projection size ``(w, h)``), a group is cut into chunks of ``batch_size``, ``warp_chunk(warp)`` makes one item of
+    ``pipe.stream`` from ``warp(s, lo)`` - the chunk's images warped at scale ``s`` as one tensor - and the keypoints
+    are mapped back with the centre / scale the LAST warp of an image left.  Warps as lazily as the pipeline asks."""
+    from .third_party import transforms
+    out = [None] * len(images)
+    for key, idx in group_by_input_size(sizes):
+        w, h = key[base]
+        chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
+        meta = {}
+
+        def batch(c):
+            def warp(s, lo):
+                ts = []
+                for i in c:
+                    t, center, scale = transforms.warp_normalize(images[i], input_size, s, lo, device=pipe.device)
+                    ts.append(t)
+                    meta[i] = (center, scale)
+                return torch.cat(ts)
+            return warp_chunk(warp)
+        with torch.no_grad():
+            for c, res in zip(chunks, pipe.stream((batch(c) for c in chunks), out_hw=(h, w))):
+                for i, (people, scores) in zip(c, res):
+                    center, scale = meta.pop(i)
+                    out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
+    return out
+
+
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
                         device="cuda", ags=False, match_on=None):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
@@ -195,27 +224,9 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     if batch_size < 1:
         raise ValueError("flip_test_inference: batch_size must be positive")
     images = list(images)
-    sizes = [transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0] for img in images]
+    sizes = [(transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0],) for img in images]
     pipe = TeacherPipeline(model, parser, device=device, flip_test=True, **_match_kw(match_on))
-    out = [None] * len(images)
-    for (w, h), idx in group_by_input_size(sizes):
-        chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
-        meta = {}
-
-        def batches():
-            for c in chunks:
-                ts = []
-                for i in c:
-                    t, center, scale = transforms.warp_normalize(images[i], input_size, 1, 1, device=pipe.device)
-                    ts.append(t)
-                    meta[i] = (center, scale)
-                yield torch.cat(ts)
-        with torch.no_grad():
-            for c, res in zip(chunks, pipe.stream(batches(), out_hw=(h, w))):
-                for i, (people, scores) in zip(c, res):
-                    center, scale = meta.pop(i)
-                    out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
-    return out
+    return _stream_by_size(pipe, images, input_size, sizes, 0, batch_size, lambda warp: warp(1, 1))
 
 
 def check_scale_factors(scale_factors):
@@ -267,7 +278,6 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
 
     ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is)."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
-    from .third_party import transforms
     scales = check_scale_factors(scale_factors)
     if not ags and not parser.tag_per_joint:
         raise ValueError("multi_scale_batch_inference: needs a parser with tag_per_joint=True")
@@ -281,26 +291,6 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
                            max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels,
                            ags=ags, **_match_kw(match_on))
-    out = [None] * len(images)
-    for key, idx in group_by_input_size(sizes):
-        w, h = key[base]
-        chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
-        meta = {}
-
-        def batches():
-            for c in chunks:
-                per_scale = []
-                for s in scales:
-                    ts = []
-                    for i in c:
-                        t, center, scale = transforms.warp_normalize(images[i], input_size, s, lo, device=pipe.device)
-                        ts.append(t)
-                        meta[i] = (center, scale)          # the last scale is the smallest
-                    per_scale.append(torch.cat(ts))
-                yield per_scale
-        with torch.no_grad():
-            for c, res in zip(chunks, pipe.stream(batches(), out_hw=(h, w))):
-                for i, (people, scores) in zip(c, res):
-                    center, scale = meta.pop(i)
-                    out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
-    return out
+    # one tensor per scale, largest first: the last warp, whose centre / scale is kept, is the smallest scale's
+    return _stream_by_size(pipe, images, input_size, sizes, base, batch_size,
+                           lambda warp: [warp(s, lo) for s in scales])
