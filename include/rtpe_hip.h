@@ -662,7 +662,12 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
                                 float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
                                 void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
 
+/* The entries of the per-image decode size (every image of a batch decoded at its own (oh_n, ow_n)) are declared in
+ * rtpe_hip_sizes.h, included below: part of this ABI and of this revision. */
+
 #ifdef __cplusplus
 }
 #endif
+#include "rtpe_hip_sizes.h"
+
 #endif /* RTPE_HIP_H */

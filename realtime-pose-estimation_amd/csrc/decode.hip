@@ -47,11 +47,30 @@ struct Axis {               // one axis of F.interpolate(bilinear, align_corners
   }
 };
 
+// PyTorch's CPU op has a second kernel for small outputs: with out_h + out_w <= 128 (whatever the input size)
+// upsample_bilinear2d resizes through its channels-last kernel (aten/src/ATen/native/cpu/UpSampleKernel.cpp,
+// _use_vectorized_kernel_cond_2d), which takes the same taps and axis weights but multiplies the weights first,
+// w_ab = ly_a * lx_b, and sums four products - the channels in vectors of 16 as
+//     fma(w00, v00, fma(w01, v01, fma(w11, v11, w10 * v10)))
+// and the channels left over (C % 16: of the 17 heat or tag maps of one F.interpolate call, the last) as
+//     fma(w11, v11, fma(w10, v10, fma(w00, v00, w01 * v01)))
+// (the contractions of an AVX-512 build, pinned on PyTorch itself by tests/test_sizes_decode_gpu.py through the oracle).
+constexpr int kSmallOutput = 128;
+__device__ __forceinline__ float bilinear_small(float v00, float v01, float v10, float v11, float ly0, float ly1,
+                                                float lx0, float lx1, bool tail) {
+  const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;
+  if (tail) return __builtin_fmaf(w11, v11, __builtin_fmaf(w10, v10, __builtin_fmaf(w00, v00, w01 * v01)));
+  return __builtin_fmaf(w00, v00, __builtin_fmaf(w01, v01, __builtin_fmaf(w11, v11, w10 * v10)));
+}
+
 struct BilinearMap {        // low-res planes sampled at (oh, ow) resolution
   const float* p;
   int sh, sw, J;
+  int small;                // oh + ow <= kSmallOutput: the sample arithmetic of PyTorch's small-output kernel
   long long img_stride;     // elements between images; plane j of image n at n*img_stride + j*sh*sw
   Axis ay, ax;
+  // plane j of an image is channel j of the J that one F.interpolate call resizes: beyond the last full vector of 16?
+  __device__ __forceinline__ bool tail(int plane) const { return plane % J >= J - (J & 15); }
   __device__ __forceinline__ float at(int plane, int y, int x) const {
     const int n = plane / J, j = plane - n * J;
     const float* b = p + (size_t)n * img_stride + (size_t)j * sh * sw;
@@ -61,11 +80,14 @@ struct BilinearMap {        // low-res planes sampled at (oh, ow) resolution
     ax.at(x, &x0, &x1, &lx0, &lx1);
     const float v00 = b[y0 * sw + x0], v01 = b[y0 * sw + x1];
     const float v10 = b[y1 * sw + x0], v11 = b[y1 * sw + x1];
+    if (small) return bilinear_small(v00, v01, v10, v11, ly0, ly1, lx0, lx1, j >= J - (J & 15));
     const float t0 = __builtin_fmaf(v00, lx0, v01 * lx1);
     const float t1 = __builtin_fmaf(v10, lx0, v11 * lx1);
     return __builtin_fmaf(t0, ly0, t1 * ly1);
   }
 };
+
+static int small_output(int oh, int ow) { return oh + ow <= kSmallOutput; }
 
 static Axis make_axis(int n_in, int n_out) {
   Axis a;
@@ -73,6 +95,78 @@ static Axis make_axis(int n_in, int n_out) {
   a.same = n_in == n_out;
   a.scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
   return a;
+}
+
+struct BilinearTag {        // D == 1
+  BilinearMap m;
+  __device__ __forceinline__ float at(int plane, int y, int x, int) const { return m.at(plane, y, x); }
+};
+
+// ---------------------------------------------------------------------------
+// per-image decode sizes: every image n of a batch is sampled at its own (oh_n, ow_n).  The sizes and the four
+// axes that go with them come from a device-visible table of one SizeEntry per image, written on the host by
+// rtpe_decode_sizes_fill with make_axis (layout: include/rtpe_hip.h).  A kernel resolves its plane's entry once, at its
+// start (plane_view / plane_tag: the index plane / J is uniform wherever the plane comes from the grid), and runs
+// the bodies of the one-size decode on the BilinearMap it gets: per sample the arithmetic is BilinearMap::at's.
+// Flat pixel indices (the top-k table's `ind`, the arg-max keys) are y * w_enc + x with ONE width w_enc >= every
+// ow_n for the whole batch: for x < ow_n the order of the indices of an image is that of its own row-major order.
+// For every other map the three helpers are the identity: (h, w) stay the launch-wide scalars and w_enc == w.
+// ---------------------------------------------------------------------------
+struct SizeEntry {
+  int32_t oh, ow;
+  Axis hy, hx, ty, tx;      // heat map rows / columns, tag map rows / columns
+  int32_t small;            // oh + ow <= kSmallOutput (BilinearMap::small)
+  int32_t reserved;
+};
+static_assert(sizeof(SizeEntry) == 64, "SizeEntry is 64 bytes in the ABI");
+
+struct NetSizesMap {        // the refined heat maps, image n at tab[n]'s size
+  BilinearMap m;            // source planes; its two axes are not read
+  const SizeEntry* tab;
+  int w_enc;
+};
+
+struct NetSizesTag {        // the per-joint tag maps of the same images, D == 1
+  BilinearMap m;
+  const SizeEntry* tab;
+};
+
+template <class Map> struct PerImageSize { static constexpr bool value = false; };
+template <> struct PerImageSize<NetSizesMap> { static constexpr bool value = true; };
+
+// the map of `plane`'s image and, for per-image sizes, that image's (h, w)
+template <class Map>
+__device__ __forceinline__ const Map& plane_view(const Map& m, int, int*, int*) { return m; }
+__device__ __forceinline__ BilinearMap plane_view(const NetSizesMap& s, int plane, int* h, int* w) {
+  const SizeEntry* e = s.tab + plane / s.m.J;
+  BilinearMap v = s.m;
+  v.ay = e->hy;
+  v.ax = e->hx;
+  v.small = e->small;
+  *h = e->oh;
+  *w = e->ow;
+  return v;
+}
+template <class TagMap>
+__device__ __forceinline__ const TagMap& plane_tag(const TagMap& t, int) { return t; }
+__device__ __forceinline__ BilinearTag plane_tag(const NetSizesTag& s, int plane) {
+  const SizeEntry* e = s.tab + plane / s.m.J;
+  BilinearTag v{s.m};
+  v.m.ay = e->ty;
+  v.m.ax = e->tx;
+  v.m.small = e->small;
+  return v;
+}
+// the width that flat indices are formed and split with
+template <class Map>
+__host__ __device__ __forceinline__ int enc_width(const Map&, int w) { return w; }
+__host__ __device__ __forceinline__ int enc_width(const NetSizesMap& s, int) { return s.w_enc; }
+// idx = y * w + x of the image's own width -> the batch's encoding
+template <class Map>
+__device__ __forceinline__ unsigned enc_index(const Map&, unsigned idx, int) { return idx; }
+__device__ __forceinline__ unsigned enc_index(const NetSizesMap& s, unsigned idx, int w) {
+  const unsigned y = idx / (unsigned)w;
+  return y * (unsigned)s.w_enc + (idx - y * (unsigned)w);
 }
 
 __device__ __forceinline__ unsigned order_bits(float v) {   // monotone float -> uint
@@ -207,6 +301,7 @@ __device__ __forceinline__ bool fill_raw<BilinearMap>(const BilinearMap& m, int 
     if (pos_flag != nullptr && *pos_flag == 0) return false;
   }
   // sample (py, px): the four taps and three multiply-adds of F.interpolate(align_corners=True), in its order
+  const bool small_tail = m.tail(plane);
   auto sample = [&](int r0, int r1, float ly0, float ly1, int c0, int c1, float lx0, float lx1) -> float {
     if (r0 < 0 || c0 < 0) return -INFINITY;               // outside the image
     float v00, v01, v10, v11;
@@ -218,11 +313,12 @@ __device__ __forceinline__ bool fill_raw<BilinearMap>(const BilinearMap& m, int 
       v00 = b[r0 * m.sw + c0]; v01 = b[r0 * m.sw + c1];
       v10 = b[r1 * m.sw + c0]; v11 = b[r1 * m.sw + c1];
     }
+    if (m.small) return bilinear_small(v00, v01, v10, v11, ly0, ly1, lx0, lx1, small_tail);
     const float t0 = __builtin_fmaf(v00, lx0, v01 * lx1);
     const float t1 = __builtin_fmaf(v10, lx0, v11 * lx1);
     return __builtin_fmaf(t0, ly0, t1 * ly1);
   };
-  if (tbuf != nullptr && staged && er <= kTRows && (PW & 3) == 0) {
+  if (tbuf != nullptr && staged && er <= kTRows && (PW & 3) == 0 && !m.small) {   // (small outputs are not separable)
     // Separable form (5x5 window path): T(r, px) = fma(v(r, c0), lx0, v(r, c1) * lx1) depends on the SOURCE row r and
     // the output column only, and every source row serves ~4 output rows (as their upper or lower row): the
     // horizontal step is done once per (source row, column), the vertical step fma(T(r0), ly0, T(r1) * ly1) takes
@@ -693,6 +789,8 @@ __global__ void __launch_bounds__(256) topk_tile_kernel(Map m, int h, int w, int
   const int tile = slot - plane_l * tiles;
   const int plane = plane_l * 8 + xcd;
   if (plane >= planes) return;                             // grid padding (whole workgroup)
+  const auto& pm = plane_view(m, plane, &h, &w);           // per-image sizes: this image's (h, w), its own tiling
+  const int we = enc_width(m, w);
   constexpr int kP = PAD >= 0 ? PAD : kMaxPad;           // the common 5x5 window needs 19 KiB of tiles, not 21.8: one more block per CU
   __shared__ __attribute__((aligned(16))) float raw[(kTH + 2 * kP) * (kTW + 2 * kP)];
   __shared__ __attribute__((aligned(16))) float rowmax[(kTH + 2 * kP) * kTW];
@@ -707,7 +805,9 @@ __global__ void __launch_bounds__(256) topk_tile_kernel(Map m, int h, int w, int
   __shared__ u64 clist[kMaxCand];
   __shared__ int ccount, any_positive;
   if (threadIdx.x == 0) { ccount = 0; any_positive = 0; }
-  if (!nms_tile(m, plane, h, w, y0, x0, pad, raw, rowmax, &taby, &tabx, &any_positive, (kTH + 2 * kP) * kTW, tbuf)) {
+  // the grid is sized for the largest image of the batch: a tile beyond this image's own leaves an empty list
+  if ((PerImageSize<Map>::value && y0 >= h) ||
+      !nms_tile(pm, plane, h, w, y0, x0, pad, raw, rowmax, &taby, &tabx, &any_positive, (kTH + 2 * kP) * kTW, tbuf)) {
     u64* outp0 = cand + ((size_t)plane * tiles + tile) * K;                 // nothing positive under this tile
     for (int r = threadIdx.x; r < K; r += 256) outp0[r] = 0;
     return;
@@ -734,7 +834,7 @@ __global__ void __launch_bounds__(256) topk_tile_kernel(Map m, int h, int w, int
         const float mx = fmaxf(mid[j], rr == 0 ? top[j] : bot[j]);
         const int y = y0 + ly + rr, x = x0 + lx + j;
         u64 key = 0;
-        if (y < h && x < w && mx == v4[j] && v4[j] > 0.f) key = make_key(v4[j], (unsigned)(y * w + x));
+        if (y < h && x < w && mx == v4[j] && v4[j] > 0.f) key = make_key(v4[j], (unsigned)(y * we + x));
         mine[rr * 4 + j] = key;
         if (key != 0) {
           const int pos = atomicAdd(&ccount, 1);
@@ -753,7 +853,7 @@ __global__ void __launch_bounds__(256) topk_tile_kernel(Map m, int h, int w, int
       float mx = rowmax[ly * kTW + lx];
       for (int d = 1; d <= 2 * pad; ++d) mx = fmaxf(mx, rowmax[(ly + d) * kTW + lx]);
       const float v = raw[(ly + pad) * PW + lx + pad];
-      if (mx == v && v > 0.f) key = make_key(v, (unsigned)(y * w + x));
+      if (mx == v && v > 0.f) key = make_key(v, (unsigned)(y * we + x));
     }
     mine[q] = key;
     if (key != 0) {                 // compact the (few) local maxima of the tile
@@ -818,6 +918,8 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(Map m, TagMap tm, int t
   u64* red = reinterpret_cast<u64*>(smem_raw);          // 4 entries
   u64* lkeys = red + 4;
   const int plane = blockIdx.x;
+  const auto& pm = plane_view(m, plane, &h, &w);
+  const int we = enc_width(m, w);
   const int n = tiles * K;
   u64* gk = cand + (size_t)plane * n;
   constexpr int kOwn = 8;
@@ -830,6 +932,7 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(Map m, TagMap tm, int t
     keys = lkeys;
   }
   const int tag_plane = tag_shared_joints > 0 ? plane / tag_shared_joints : plane;
+  const auto& pt = plane_tag(tm, tag_plane);
   int found = 0;
   if (merge_heads) {
     // every tile list is sorted (largest first, zeros behind): only the heads compete.  A thread keeps the
@@ -890,7 +993,7 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(Map m, TagMap tm, int t
     for (int base = 0; found < K && base < total_px; base += 256) {
       const int idx = base + threadIdx.x;
       bool z = false;
-      if (idx < total_px) z = nms_value_at(m, plane, h, w, pad, idx / w, idx - (idx / w) * w) == 0.f;
+      if (idx < total_px) z = nms_value_at(pm, plane, h, w, pad, idx / w, idx - (idx / w) * w) == 0.f;
       const unsigned long long mask = __ballot(z);
       if (lane == 0) wtot[wv] = __popcll(mask);
       __syncthreads();
@@ -900,7 +1003,7 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(Map m, TagMap tm, int t
       const int k = found + before;
       if (z && k < K) {
         val_k[(size_t)plane * K + k] = 0.f;
-        ind_k[(size_t)plane * K + k] = idx;
+        ind_k[(size_t)plane * K + k] = (int)enc_index(m, (unsigned)idx, w);
       }
       found = found + total < K ? found + total : K;
       __syncthreads();
@@ -912,7 +1015,7 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(Map m, TagMap tm, int t
   for (int i = threadIdx.x; i < K * D; i += 256) {
     const int k = i / D, d = i - k * D;
     const int idx = ind_k[(size_t)plane * K + k];
-    tag_k[((size_t)plane * K + k) * D + d] = tm.at(tag_plane, idx / w, idx - (idx / w) * w, d);
+    tag_k[((size_t)plane * K + k) * D + d] = pt.at(tag_plane, idx / we, idx - (idx / we) * we, d);
   }
 }
 
@@ -922,10 +1025,6 @@ struct DirectTag {          // (planes, h, w, D)
   __device__ __forceinline__ float at(int plane, int y, int x, int d) const {
     return p[(((size_t)plane * h + y) * w + x) * D + d];
   }
-};
-struct BilinearTag {        // D == 1
-  BilinearMap m;
-  __device__ __forceinline__ float at(int plane, int y, int x, int) const { return m.at(plane, y, x); }
 };
 
 // ---------------------------------------------------------------------------
@@ -965,6 +1064,7 @@ __global__ void __launch_bounds__(64) adjust_prepare_kernel(Map m, int J, int h,
   const int row_len = 3 + D;
   const float* kp = ans_in + (size_t)p * J * row_len;
   const int img = person_img ? person_img[p] : 0;
+  const auto& pm = plane_view(m, img * J, &h, &w);
   if (j < J) {
     float* out = ans_out + ((size_t)p * J + j) * row_len;
     for (int c = 0; c < row_len; ++c) out[c] = kp[j * row_len + c];
@@ -974,8 +1074,8 @@ __global__ void __launch_bounds__(64) adjust_prepare_kernel(Map m, int J, int h,
       const int col = (int)cx, row = (int)cy;
       const int cr = col + 1 < w - 1 ? col + 1 : w - 1, cl = col - 1 > 0 ? col - 1 : 0;
       const int rd = row + 1 < h - 1 ? row + 1 : h - 1, ru = row - 1 > 0 ? row - 1 : 0;
-      cx += m.at(plane, row, cr) > m.at(plane, row, cl) ? 0.25f : -0.25f;
-      cy += m.at(plane, rd, col) > m.at(plane, ru, col) ? 0.25f : -0.25f;
+      cx += pm.at(plane, row, cr) > pm.at(plane, row, cl) ? 0.25f : -0.25f;
+      cy += pm.at(plane, rd, col) > pm.at(plane, ru, col) ? 0.25f : -0.25f;
       out[0] = cx + 0.5f;
       out[1] = cy + 0.5f;
     }
@@ -1045,6 +1145,7 @@ __device__ __forceinline__ void argmax_rows<BilinearMap>(const BilinearMap& m, i
     return;
   }
   const int n = plane / m.J, j = plane - n * m.J;
+  const bool small_tail = m.tail(plane);
   const float* b = m.p + (size_t)n * m.img_stride + (size_t)j * m.sh * m.sw;
   // the source rows of the stripe are contiguous in memory: one coalesced copy into LDS, then the four
   // taps of every pixel come from there (the gather of 4-byte taps through L1 was the whole cost)
@@ -1082,9 +1183,14 @@ __device__ __forceinline__ void argmax_rows<BilinearMap>(const BilinearMap& m, i
         } else {
           v00 = b[o0 + c0[k]]; v01 = b[o0 + c1[k]]; v10 = b[o1 + c0[k]]; v11 = b[o1 + c1[k]];
         }
-        const float t0 = __builtin_fmaf(v00, lx0[k], v01 * lx1[k]);
-        const float t1 = __builtin_fmaf(v10, lx0[k], v11 * lx1[k]);
-        const float dv = __builtin_fmaf(t0, ly0, t1 * ly1);
+        float dv;
+        if (m.small) {                                        // uniform branch
+          dv = bilinear_small(v00, v01, v10, v11, ly0, ly1, lx0[k], lx1[k], small_tail);
+        } else {
+          const float t0 = __builtin_fmaf(v00, lx0[k], v01 * lx1[k]);
+          const float t1 = __builtin_fmaf(v10, lx0[k], v11 * lx1[k]);
+          dv = __builtin_fmaf(t0, ly0, t1 * ly1);
+        }
         const bool up = dv > *bv || *bi == 0xffffffffu;      // a thread's pixels come in increasing index order
         *bv = up ? dv : *bv;
         *bi = up ? (unsigned)(y * w + x) : *bi;
@@ -1100,13 +1206,14 @@ __global__ void __launch_bounds__(256) plane_argmax_kernel(Map m, int h, int w, 
   __shared__ u64 red[4];
   const int plane = blockIdx.y;
   if (known != nullptr && known[plane]) return;            // its maximum came with the top-k table
+  const auto& pm = plane_view(m, plane, &h, &w);
   const int rows = (h + gridDim.x - 1) / gridDim.x;
   const int y_begin = blockIdx.x * rows, y_end = min(h, y_begin + rows);
   if (y_begin >= y_end) return;
   float bv = -INFINITY;
   unsigned bi = 0xffffffffu;
-  argmax_rows(m, plane, w, y_begin, y_end, &bv, &bi, lds_floats > 0 ? argmax_src : nullptr, lds_floats);
-  const u64 k = block_max(bi == 0xffffffffu ? 0 : make_key(bv, bi), red);
+  argmax_rows(pm, plane, w, y_begin, y_end, &bv, &bi, lds_floats > 0 ? argmax_src : nullptr, lds_floats);
+  const u64 k = block_max(bi == 0xffffffffu ? 0 : make_key(bv, enc_index(m, bi, w)), red);
   if (threadIdx.x == 0 && k != 0) atomicMax(&plane_key[plane], k);
 }
 
@@ -1138,18 +1245,19 @@ __global__ void __launch_bounds__(256) refine_shortcut_kernel(TagMap tm, int J, 
   const u64 key = plane_key[plane];
   if (key == 0) { need_scan[i] = 1; return; }
   const int idx = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-  const int y = idx / w, x = idx - y * w;
+  const int y = idx / w, x = idx - y * w;                    // w: the width the indices are encoded with
+  const auto& pt = plane_tag(tm, plane);
   float ss;                                                  // the exact expressions of refine_scan_kernel
   if (D == 1) {
-    const float d0 = tm.at(plane, y, x, 0) - mean_tag[p];
+    const float d0 = pt.at(plane, y, x, 0) - mean_tag[p];
     ss = d0 * d0;
   } else if (D < 8) {
-    const float d0 = tm.at(plane, y, x, 0) - mean_tag[(size_t)p * D];
+    const float d0 = pt.at(plane, y, x, 0) - mean_tag[(size_t)p * D];
     ss = d0 * d0;
-    for (int d = 1; d < D; ++d) { const float dd = tm.at(plane, y, x, d) - mean_tag[(size_t)p * D + d]; ss = ss + dd * dd; }
+    for (int d = 1; d < D; ++d) { const float dd = pt.at(plane, y, x, d) - mean_tag[(size_t)p * D + d]; ss = ss + dd * dd; }
   } else {
     float sq[kMaxD];
-    for (int d = 0; d < D; ++d) { const float dd = tm.at(plane, y, x, d) - mean_tag[(size_t)p * D + d]; sq[d] = dd * dd; }
+    for (int d = 0; d < D; ++d) { const float dd = pt.at(plane, y, x, d) - mean_tag[(size_t)p * D + d]; sq[d] = dd * dd; }
     ss = pairwise8_sum(sq, D);
   }
   if (rintf(sqrtf(ss)) == 0.f) best_key[i] = key;            // score = det - 0: the key of the plane maximum
@@ -1171,6 +1279,9 @@ __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int 
   __shared__ u64 red[kRefineGroup];
   __shared__ float gmean[kRefineGroup * kMaxD];
   const int plane = blockIdx.y, img = plane / J, j = plane - img * J;
+  const auto& pm = plane_view(m, plane, &h, &w);
+  const auto& pt = plane_tag(tm, plane);
+  const int we = enc_width(m, w);
   const int row_len = 3 + D;
   if (threadIdx.x == 0) {
     if (P_dev != nullptr) P = *P_dev;        // P was the capacity: the rows beyond the people were never written
@@ -1224,9 +1335,9 @@ __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int 
         int y = y_begin + (int)(threadIdx.x / (unsigned)w), x = (int)(threadIdx.x % (unsigned)w);
         const int dy = 256 / w, dx = 256 - dy * w;          // advance of 256 pixels in (y, x)
         for (int i = threadIdx.x; i < npix; i += 256) {
-          const float dv = m.at(plane, y, x);
-          const float tv = tm.at(plane, y, x, 0);
-          const unsigned idx = (unsigned)(y * w + x);
+          const float dv = pm.at(plane, y, x);
+          const float tv = pt.at(plane, y, x, 0);
+          const unsigned idx = (unsigned)(y * we + x);
           bool slow = false;
           float kk[kRefineGroup];
 #pragma unroll
@@ -1257,10 +1368,10 @@ __global__ void __launch_bounds__(256) refine_scan_kernel(Map m, TagMap tm, int 
       } else {
         for (int i = threadIdx.x; i < npix; i += 256) {
           const int yy = i / w, x = i - yy * w, y = y_begin + yy;
-          const float dv = m.at(plane, y, x);
-          const unsigned idx = (unsigned)(y * w + x);
+          const float dv = pm.at(plane, y, x);
+          const unsigned idx = (unsigned)(y * we + x);
           float tv[kMaxD];
-          for (int d = 0; d < D; ++d) tv[d] = tm.at(plane, y, x, d);
+          for (int d = 0; d < D; ++d) tv[d] = pt.at(plane, y, x, d);
           for (int q = 0; q < gn; ++q) {
             float ss;
             if (D < 8) {
@@ -1309,15 +1420,17 @@ __global__ void __launch_bounds__(256) refine_finalize_kernel(Map m, int J, int 
   const u64 key = best_key[i];
   if (key == 0) return;
   const int plane = (person_img ? person_img[p] : 0) * J + j;
+  const auto& pm = plane_view(m, plane, &h, &w);
+  const int we = enc_width(m, w);
   const int idx = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-  const int y = idx / w, x = idx - y * w;
-  const float v = m.at(plane, y, x);
+  const int y = idx / we, x = idx - y * we;
+  const float v = pm.at(plane, y, x);
   if (v > 0.f) {
     const int xr = x + 1 < w - 1 ? x + 1 : w - 1, xl = x - 1 > 0 ? x - 1 : 0;
     const int yd = y + 1 < h - 1 ? y + 1 : h - 1, yu = y - 1 > 0 ? y - 1 : 0;
     float* out = ans_out + (size_t)i * row_len;
-    out[0] = (float)x + 0.5f + (m.at(plane, y, xr) > m.at(plane, y, xl) ? 0.25f : -0.25f);
-    out[1] = (float)y + 0.5f + (m.at(plane, yd, x) > m.at(plane, yu, x) ? 0.25f : -0.25f);
+    out[0] = (float)x + 0.5f + (pm.at(plane, y, xr) > pm.at(plane, y, xl) ? 0.25f : -0.25f);
+    out[1] = (float)y + 0.5f + (pm.at(plane, yd, x) > pm.at(plane, yu, x) ? 0.25f : -0.25f);
     out[2] = v;
   }
 }
@@ -1361,8 +1474,8 @@ static int adjust_refine_run(const Map& m, const TagMap& tm, int n_img, int J, i
     hipLaunchKernelGGL((plane_argmax_kernel<Map>), dim3(kArgmaxStripes, n_img * J), dim3(256), 24 * 1024, s, m, h, w,
                        plane_key, 24 * 1024 / 4, known);
     RTPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((refine_shortcut_kernel<TagMap>), dim3((P * J + 255) / 256), dim3(256), 0, s, tm, J, w, D, ans_in,
-                       person_img, P, mean_tag, plane_key, best_key, need_scan, P_dev);
+    hipLaunchKernelGGL((refine_shortcut_kernel<TagMap>), dim3((P * J + 255) / 256), dim3(256), 0, s, tm, J,
+                       enc_width(m, w), D, ans_in, person_img, P, mean_tag, plane_key, best_key, need_scan, P_dev);
     RTPE_HIP_CHECK(hipGetLastError());
   }
   if (D == 1)
@@ -1384,6 +1497,7 @@ static int adjust_refine_run(const Map& m, const TagMap& tm, int n_img, int J, i
 static BilinearMap make_bilinear(const float* p, int sh, int sw, long long img_stride, int J, int oh, int ow) {
   BilinearMap m;
   m.p = p; m.sh = sh; m.sw = sw; m.J = J; m.img_stride = img_stride;
+  m.small = small_output(oh, ow);
   m.ay = make_axis(sh, oh);
   m.ax = make_axis(sw, ow);
   return m;
@@ -1500,6 +1614,7 @@ extern "C" int rtpe_bilinear_upsample(const float* src, int32_t planes, int32_t 
                                       int32_t oh, int32_t ow, void* stream) {
   RTPE_REQUIRE(src && dst && planes > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "bilinear: bad argument");
   BilinearMap m = make_bilinear(src, h, w, 0, planes, oh, ow);   // one "image" of `planes` planes
+  m.small = 0;    // (the channel of a plane within its F.interpolate call is not known here: the separable formula)
   const size_t total = (size_t)planes * oh * ow;
   size_t blocks = (total + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
@@ -1696,6 +1811,121 @@ extern "C" int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int3
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_n: P_dev is null");
   return decode_adjust_refine("adjust_refine_fused_topk_n",
                               NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev, true);
+}
+
+// ---------------------------------------------------------------------------
+// the network outputs as they are, every image decoded at its own size: NetSrc with the sizes in a table
+// (SizeEntry, rtpe_decode_sizes_fill).  (oh, ow) are the largest height and the largest width of the batch - the tile
+// grid, the scratch buffer and the stripes are sized by them - and w_enc is the width of the flat indices
+// ---------------------------------------------------------------------------
+struct NetSizesSrc {
+  const float* hm;
+  int32_t hh, hw;
+  int64_t hm_img_stride;
+  const float* tg;
+  int32_t th, tw;
+  int64_t tg_img_stride;
+  int32_t N, J;
+  const void* table;
+  size_t table_bytes;
+  int32_t oh, ow, w_enc;
+  int check(const char* who) const {
+    RTPE_REQUIRE(hm && tg && table && N > 0 && J > 0, "%s: bad argument", who);
+    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
+    RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "%s: sizes table too small (%zu < %zu bytes)", who,
+                 table_bytes, (size_t)N * sizeof(SizeEntry));
+    RTPE_REQUIRE(w_enc >= ow, "%s: w_enc=%d is below the largest width %d", who, w_enc, ow);
+    RTPE_REQUIRE((int64_t)oh * w_enc <= 0x7fffffff, "%s: y * w_enc + x exceeds 32 bits (max_oh=%d, w_enc=%d)", who, oh,
+                 w_enc);
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    const SizeEntry* tab = reinterpret_cast<const SizeEntry*>(table);
+    return f(NetSizesMap{make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow), tab, w_enc},
+             NetSizesTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow), tab}, 1);
+  }
+};
+
+extern "C" int rtpe_decode_sizes_bytes(int32_t N, size_t* bytes) {
+  RTPE_REQUIRE(bytes && N > 0, "decode_sizes_bytes: bad argument");
+  *bytes = (size_t)N * sizeof(SizeEntry);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_decode_sizes_fill(const int32_t* sizes_hw, int32_t N, int32_t hh, int32_t hw, int32_t th,
+                                      int32_t tw, void* table, size_t table_bytes, int32_t* max_oh,
+                                      int32_t* max_ow) {
+  RTPE_REQUIRE(sizes_hw && table && N > 0, "decode_sizes_fill: bad argument");
+  RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0, "decode_sizes_fill: bad shape");
+  RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "decode_sizes_fill: sizes table too small (%zu < %zu bytes)",
+               table_bytes, (size_t)N * sizeof(SizeEntry));
+  int mh = 0, mw = 0;
+  for (int n = 0; n < N; ++n) {
+    RTPE_REQUIRE(sizes_hw[2 * n] > 0 && sizes_hw[2 * n + 1] > 0, "decode_sizes_fill: image %d has size %d x %d", n,
+                 sizes_hw[2 * n], sizes_hw[2 * n + 1]);
+    mh = sizes_hw[2 * n] > mh ? sizes_hw[2 * n] : mh;
+    mw = sizes_hw[2 * n + 1] > mw ? sizes_hw[2 * n + 1] : mw;
+  }
+  SizeEntry* tab = reinterpret_cast<SizeEntry*>(table);
+  for (int n = 0; n < N; ++n) {
+    SizeEntry e;
+    memset(&e, 0, sizeof(e));
+    e.oh = sizes_hw[2 * n];
+    e.ow = sizes_hw[2 * n + 1];
+    e.hy = make_axis(hh, e.oh);
+    e.hx = make_axis(hw, e.ow);
+    e.ty = make_axis(th, e.oh);
+    e.tx = make_axis(tw, e.ow);
+    e.small = small_output(e.oh, e.ow);
+    tab[n] = e;
+  }
+  if (max_oh) *max_oh = mh;
+  if (max_ow) *max_ow = mw;
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_topk_fused_sizes(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
+                                     int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J,
+                                     const void* sizes_table, size_t table_bytes, int32_t max_oh, int32_t max_ow,
+                                     int32_t w_enc, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
+                                     int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_fused_sizes",
+                     NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table, table_bytes,
+                                 max_oh, max_ow, w_enc},
+                     K, nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rtpe_adjust_refine_fused_topk_sizes(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                   const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                   int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
+                                                   int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
+                                                   float* ans_out, const int32_t* person_img, int32_t P,
+                                                   int32_t do_adjust, int32_t do_refine, float* scores,
+                                                   const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                   void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_adjust_refine("adjust_refine_fused_topk_sizes",
+                              NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
+                                          table_bytes, max_oh, max_ow, w_enc},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr, true);
+}
+
+extern "C" int rtpe_adjust_refine_fused_topk_sizes_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                     const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                     int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
+                                                     int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
+                                                     float* ans_out, const int32_t* person_img, int32_t P,
+                                                     int32_t do_adjust, int32_t do_refine, float* scores,
+                                                     const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                     void* scratch, size_t scratch_bytes, void* stream,
+                                                     const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_sizes_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_fused_topk_sizes_n",
+                              NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
+                                          table_bytes, max_oh, max_ow, w_enc},
                               {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
                                scratch, scratch_bytes, stream}, P_dev, true);
 }

@@ -160,7 +160,22 @@ for _name in ("rtpe_adjust_refine_fused_topk", "rtpe_adjust_refine_flip", "rtpe_
               "rtpe_adjust_refine_ms_ags"):
     _SIGS[_name + "_n"] = (c_int32, _SIGS[_name][1] + [c_void_p])
 
-EXPORTS = tuple(_SIGS)
+# per-image decode size (include/rtpe_hip_sizes.h): (oh, ow) of the one-size entries ->
+# (sizes_table, table_bytes, max_oh, max_ow, w_enc)
+_SIZES = [c_void_p, c_size_t, c_int32, c_int32, c_int32]
+_SIGS_SIZES = {
+    "rtpe_decode_sizes_bytes": (c_int32, [c_int32, POINTER(c_size_t)]),
+    "rtpe_decode_sizes_fill": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                         POINTER(c_int32), POINTER(c_int32)]),
+}
+for _name in ("rtpe_topk_fused", "rtpe_adjust_refine_fused_topk"):
+    _a = _SIGS[_name][1]
+    _SIGS_SIZES[_name + "_sizes"] = (c_int32, _a[:10] + _SIZES + _a[12:])
+_SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes_n"] = (
+    c_int32, _SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes"][1] + [c_void_p])
+
+EXPORTS = tuple(_SIGS)                  # the prototypes of include/rtpe_hip.h itself
+EXPORTS_SIZES = tuple(_SIGS_SIZES)      # those of include/rtpe_hip_sizes.h, which it includes
 _lib = None
 
 
@@ -182,7 +197,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -12,7 +12,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .third_party.group import HeatmapParser
+from .third_party.group import HeatmapParser, per_image_sizes
 
 HM_PARSER_PARAMS = {"max_num_people": 30, "detection_threshold": 0.1, "tag_threshold": 1.0,
                     "use_detection_val": True, "ignore_too_much": False, "tag_per_joint": True,
@@ -205,6 +205,20 @@ class TeacherPipeline:
                     outs = outs + tuple(fwd(self.mirror(xb)))
                 on_outputs(i, n0, outs)
 
+    def _decode_hw(self, out_hw, images):
+        """``out_hw`` of one batch, checked before any GPU work: None, ``(h, w)`` or one ``(h, w)`` per image - the
+        plain protocol only: the flip and multi-scale tests decode at the projection size, one per batch"""
+        if out_hw is None:
+            return None
+        n = (images[0] if isinstance(images, (list, tuple)) else images).shape[0]
+        sizes = per_image_sizes(out_hw, n, "TeacherPipeline")
+        if sizes is None:
+            return tuple(out_hw)
+        if self.flip_test or self.scale_factors is not None:
+            raise ValueError("TeacherPipeline: per-image decode sizes are for the plain protocol only; with flip_test "
+                             "or scale_factors the decode size is the projection size of the batch")
+        return sizes
+
     @torch.no_grad()
     def forward(self, images):
         return self.model(images)
@@ -218,8 +232,10 @@ class TeacherPipeline:
     @torch.no_grad()
     def __call__(self, images, out_hw=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
-        out_hw = decode resolution (original image size), default (H, W); with ``flip_test`` the projection size.
+        out_hw = decode resolution (original image size), default (H, W) - one ``(h, w)`` for the batch or a sequence
+        of N pairs, one per image (``HeatmapParser.parse_lowres``); with ``flip_test`` the projection size.
         With ``scale_factors``: images = one tensor per scale (descending), out_hw default = the scale-1 (H, W)."""
+        out_hw = self._decode_hw(out_hw, images)
         if self.scale_factors is not None:
             xs = self._ms_inputs(images)
             st = self._ms_begin(xs, out_hw)
@@ -228,7 +244,7 @@ class TeacherPipeline:
             self.parser.lowres_match(st)
             return self.parser.lowres_finish(st)
         preds, refined = self.model(images)
-        hw = tuple(out_hw) if out_hw is not None else tuple(images.shape[2:])
+        hw = out_hw if out_hw is not None else tuple(images.shape[2:])
         if self.flip_test:
             preds_f, refined_f = self.model(self.mirror(images))
             return self.parser.parse_flip(preds, refined, preds_f, refined_f, hw, self.flip_index)
@@ -257,6 +273,9 @@ class TeacherPipeline:
         are slower than either): a per-call flag, the process-wide option is not touched.  1 = every forward on the caller's stream.  ``exclusive(k)`` true: the forward of batch k
         runs alone - it starts when the forwards in flight are done and the next one starts behind it (bench.py times the
         kernels of such a step with per-op events: a kernel's duration beside another forward is not its own).
+
+        ``out_hw``: as for ``__call__``, or a callable ``k -> (h, w) | [(h, w)] * N`` asked once per batch (before its
+        forward), so that the decode sizes can change from batch to batch.
 
         Yields one ``[(people, scores)] * N`` list per batch, in order, two steps after the batch
         was submitted.  ``on_forward(k, x)`` may replace the plain forward (bench.py records op
@@ -336,9 +355,10 @@ class TeacherPipeline:
         try:
             with torch.no_grad():
                 for k, x in enumerate(batches):
+                    hw_k = self._decode_hw(out_hw(k) if callable(out_hw) else out_hw, x)
                     if ms:
                         xs = self._ms_inputs(x)
-                        st_ms = on_decode_stream(self._ms_begin, xs, out_hw)
+                        st_ms = on_decode_stream(self._ms_begin, xs, hw_k)
                     fs = main
                     if fwd_streams is not None:
                         # forward k on stream k % n with workspace slot 1 + k % n; the input was produced on `main`
@@ -364,7 +384,7 @@ class TeacherPipeline:
                             set_workspace_slot(prev_slot)
                     else:
                         outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
-                    hw = None if ms else tuple(out_hw) if out_hw is not None else tuple(x.shape[2:])
+                    hw = None if ms else hw_k if hw_k is not None else tuple(x.shape[2:])
                     f_done = None
                     if side is not None or fs is not main:
                         f_done = torch.cuda.Event()

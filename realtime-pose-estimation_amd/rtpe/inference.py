@@ -294,3 +294,68 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     # one tensor per scale, largest first: the last warp, whose centre / scale is kept, is the smallest scale's
     return _stream_by_size(pipe, images, input_size, sizes, base, batch_size,
                            lambda warp: [warp(s, lo) for s in scales])
+
+
+class _Shape:
+    """what ``get_multi_scale_size`` reads of an image: its ``shape``"""
+
+    def __init__(self, h, w):
+        self.shape = (h, w, 3)
+
+
+def plain_plan(shapes, input_size=640, batch_size=32, max_forward_pixels=None, by_original_size=False):
+    """the batches of ``plain_inference`` for images of the given ``(h, w)`` shapes: ``[[indices]]``, images grouped
+    by their network input size only (``by_original_size``: by input size AND original size - what a decode with one
+    size per batch needs), every group cut into chunks of at most ``batch_size`` images and at most
+    ``max_forward_pixels`` input pixels (default ``engine.MAX_FORWARD_PIXELS``).  Pure host function."""
+    from .engine import MAX_FORWARD_PIXELS, forward_plan
+    from .third_party import transforms
+    if batch_size < 1:
+        raise ValueError("plain_inference: batch_size must be positive")
+    budget = int(MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels)
+    keys = []
+    for h, w in shapes:
+        size = transforms.get_multi_scale_size(_Shape(int(h), int(w)), input_size, 1.0, 1)[0]
+        keys.append((size, (int(h), int(w))) if by_original_size else (size,))
+    chunks = []
+    for key, idx in group_by_input_size(keys):
+        w, h = key[0]
+        chunks += [idx[n0:n0 + n] for n0, n in forward_plan(len(idx), (h, w), min(budget, batch_size * h * w))]
+    return chunks
+
+
+def plain_inference(model, parser, images, input_size=640, batch_size=32, max_forward_pixels=None, device="cuda",
+                    match_on=None):
+    """The batched ``validate_hhrnet.py:84-105`` over a list of (h, w, 3) uint8 images: every image is warped to its
+    network input size (``warp_normalize(img, input_size, 1, 1)``), images of one INPUT size are batched whatever
+    their original sizes - at most ``batch_size`` images and ``max_forward_pixels`` input pixels per forward
+    (``plain_plan``) - and streamed through ``TeacherPipeline``, which decodes every image at its own original
+    ``(h, w)`` (``HeatmapParser.parse_lowres`` with one size per image).  Returns ``[(people, scores)]`` in input
+    order, people in the pixel coordinates of the original image, each bit-identical to the per-image loop body::
+
+        t, _, _ = warp_normalize(img, input_size, 1, 1, device=device)
+        preds, refined = model(t)
+        parser.parse_lowres(refined, preds[:, 17:], img.shape[:2])[0]
+
+    (the forward is batch-invariant).  This protocol has no ``get_final_preds`` step.  ``match_on``: passed to
+    ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).  The batches are planned, and
+    an image beyond the pixel budget refused, before any GPU work."""
+    from .engine import TeacherPipeline
+    from .third_party import transforms
+    kw = _match_kw(match_on)
+    images = list(images)
+    shapes = [tuple(int(v) for v in img.shape[:2]) for img in images]
+    chunks = plain_plan(shapes, input_size, batch_size, max_forward_pixels)
+    out = [None] * len(images)
+    if not chunks:
+        return out
+    pipe = TeacherPipeline(model, parser, device=device, **kw)
+
+    def batch(c):
+        return torch.cat([transforms.warp_normalize(images[i], input_size, 1, 1, device=pipe.device)[0] for i in c])
+    with torch.no_grad():
+        results = pipe.stream((batch(c) for c in chunks), out_hw=lambda k: [shapes[i] for i in chunks[k]])
+        for c, res in zip(chunks, results):
+            for i, r in zip(c, res):
+                out[i] = r
+    return out

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--weights", default="W0", choices=["W0", "W1", "W2"], help="seeded weights when there is no checkpoint")
     ap.add_argument("--check", action="store_true", help="compare with the reference's CPU result in the fixture")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--batched", action="store_true",
+                    help="also run the list through rtpe.inference.plain_inference (images batched by network input size, "
+                         "each decoded at its own size) and compare with the loop's results, bit for bit")
     args = ap.parse_args()
 
     import __graft_entry__ as entry
@@ -94,6 +97,17 @@ def main():
             print("   reference (CPU, same weights and pixels): %d people, top scores %s; heat maps within %.2e"
                   % (len(ref_people), [round(float(s), 4) for s in sorted(ref_scores, reverse=True)[:3]], hm_err))
             assert hm_err <= 1e-3, "heat maps differ from the reference by more than 1e-3"
+    if args.batched:
+        from rtpe.inference import plain_inference, plain_plan
+        imgs = [img for _, img in items]
+        batched = plain_inference(hhrnet, hm_parser, imgs, INPUT_SIZE, device=args.device)
+        for (name, _), (grouped, scores), want, want_scores in zip(items, batched, all_preds, all_scores):
+            got = [x for x in grouped if x.size > 0] if getattr(grouped, "ndim", 1) == 3 else []
+            same = len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)) and \
+                np.array_equal(np.array(scores, np.float32), np.array(want_scores, np.float32))
+            print("   batched %s: %d people, %s the loop's result" % (name, len(got), "equal to" if same else "DIFFERENT from"))
+            assert same, "plain_inference differs from the per-image loop"
+        print("   %d images in %d forward(s)" % (len(imgs), len(plain_plan([i.shape[:2] for i in imgs], INPUT_SIZE))))
     return all_preds, all_scores
 
 
