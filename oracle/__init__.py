@@ -20,6 +20,10 @@ What is in here
   in this image).
 * ``synth`` - the seeded synthetic weights / images / decode maps of
   SURVEY.md section 8(d).
+* ``ties`` - decode maps with exact ties by construction and the counters
+  that prove the ties are there; with ``decode_ref``'s stable top-k the
+  yardstick for the order among equal values, which the reference's
+  ``torch.topk`` leaves undefined.
 
 Parity pin
 ----------

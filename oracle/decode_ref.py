@@ -110,11 +110,14 @@ def pairwise8_sum_f32(a):
 class HeatmapParserRef:
     def __init__(self, num_joints=17, max_num_people=30, detection_threshold=0.1,
                  tag_threshold=1.0, use_detection_val=True, ignore_too_much=False,
-                 tag_per_joint=True, nms_ksize=5, nms_padding=2):
+                 tag_per_joint=True, nms_ksize=5, nms_padding=2, stable_topk=False):
         self.params = Params(num_joints, max_num_people, detection_threshold,
                              tag_threshold, use_detection_val, ignore_too_much)
         self.tag_per_joint = tag_per_joint
         self.nms_ksize, self.nms_padding = nms_ksize, nms_padding
+        # False: torch.topk, what the reference runs (the goldens come from it).  True: the order the HIP decode
+        # declares among equal values - a stable sort, lowest flat index first (``top_k_stable``)
+        self.stable_topk = stable_topk
 
     def nms(self, det):
         """group.py:134-138: keep a pixel iff it equals its 5x5 window max"""
@@ -123,10 +126,15 @@ class HeatmapParserRef:
 
     def top_k(self, det, tag):
         """group.py:144-179.  det (N,J,h,w); tag (N,J,h,w,D) (or (N,1,h,w,D) if
-        not tag_per_joint).  Order among equal values is whatever ATen gives."""
+        not tag_per_joint).  Order among equal values is whatever ATen gives (it is not the index order, and
+        which members of a tie group at the K-th place are returned is not defined either); with
+        ``stable_topk=True`` the selection is ``top_k_stable``'s: descending value, ascending flat index."""
         det = self.nms(det)
         N, J, h, w = det.shape
-        val_k, ind = det.reshape(N, J, -1).topk(self.params.max_num_people, dim=2)
+        if self.stable_topk:
+            val_k, ind = self.top_k_stable(det)
+        else:
+            val_k, ind = det.reshape(N, J, -1).topk(self.params.max_num_people, dim=2)
         tag = tag.reshape(tag.shape[0], tag.shape[1], w * h, -1)
         if not self.tag_per_joint:
             tag = tag.expand(-1, self.params.num_joints, -1, -1)
@@ -135,6 +143,17 @@ class HeatmapParserRef:
         y = (ind / w).long()          # true division then truncation, :168-169
         return {"tag_k": tag_k.numpy(), "loc_k": torch.stack((x, y), 3).numpy(),
                 "val_k": val_k.numpy()}
+
+    def top_k_stable(self, nms):
+        """the K first entries of a stable descending sort of every NMS plane: ``np.argsort(-plane,
+        kind="stable")[:K]``, so equal values (+0 and -0 are equal) come in ascending flat index.  nms (N,J,h,w)
+        torch f32 -> (val_k (N,J,K) f32, ind (N,J,K) i64) torch tensors, as ``Tensor.topk`` returns them."""
+        N, J, h, w = nms.shape
+        K = self.params.max_num_people
+        flat = nms.reshape(N * J, h * w).numpy()
+        ind = np.stack([np.argsort(-row, kind="stable")[:K] for row in flat]).astype(np.int64)
+        val = np.take_along_axis(flat, ind, 1)
+        return torch.from_numpy(val.reshape(N, J, K)), torch.from_numpy(ind.reshape(N, J, K))
 
     def match(self, tag_k, loc_k, val_k):
         return [match_by_tag(t, l, v, self.params) for t, l, v in zip(tag_k, loc_k, val_k)]
@@ -159,32 +178,43 @@ class HeatmapParserRef:
                         people[p, j, 1] = cy + f32(0.5)
         return ans
 
+    @staticmethod
+    def refine_mean(tag, kp):
+        """group.py:214-222: the float32 mean tag of a person's detected joints.  tag (J,h,w,D), kp (J,3+D)"""
+        J, D = tag.shape[0], tag.shape[3]
+        seen = [tag[j, int(kp[j, 1]), int(kp[j, 0])] for j in range(J) if kp[j, 2] > 0]
+        seen = np.asarray(seen, f32)                       # (n, D)
+        if D == 1:
+            return np.array([pairwise8_sum_f32(seen[:, 0]) / f32(len(seen))], f32)
+        s = np.zeros(D, f32)
+        for t in seen:
+            s = (s + t).astype(f32)
+        return (s / f32(len(seen))).astype(f32)
+
+    @staticmethod
+    def refine_score(det_j, tag_j, mean):
+        """group.py:229-232: the map whose first maximum refine takes, heat value minus the rounded tag distance.
+        det_j (h,w), tag_j (h,w,D), mean (D,)"""
+        D = tag_j.shape[2]
+        d = tag_j - mean[None, None, :]
+        sq = d * d
+        if D < 8:
+            ss = sq[..., 0].copy()
+            for k in range(1, D):
+                ss = ss + sq[..., k]
+        else:
+            ss = sq.sum(axis=2)                            # numpy pairwise, as the reference
+        return det_j - np.rint(np.sqrt(ss))                # np.round == half-to-even
+
     def refine(self, det, tag, kp):
         """group.py:202-264 for one person.  det (J,h,w) f32, tag (J,h,w,D) f32,
         kp (J,3+D) f32 (modified in place and returned)."""
         if tag.ndim == 3:
             tag = tag[..., None]
         J, h, w = det.shape
-        D = tag.shape[3]
-        seen = [tag[j, int(kp[j, 1]), int(kp[j, 0])] for j in range(J) if kp[j, 2] > 0]
-        seen = np.asarray(seen, f32)                       # (n, D)
-        if D == 1:
-            mean = np.array([pairwise8_sum_f32(seen[:, 0]) / f32(len(seen))], f32)
-        else:
-            s = np.zeros(D, f32)
-            for t in seen:
-                s = (s + t).astype(f32)
-            mean = (s / f32(len(seen))).astype(f32)
+        mean = self.refine_mean(tag, kp)
         for j in range(J):
-            d = tag[j] - mean[None, None, :]
-            sq = d * d
-            if D < 8:
-                ss = sq[..., 0].copy()
-                for k in range(1, D):
-                    ss = ss + sq[..., k]
-            else:
-                ss = sq.sum(axis=2)                        # numpy pairwise, as the reference
-            score = det[j] - np.rint(np.sqrt(ss))          # np.round == half-to-even
+            score = self.refine_score(det[j], tag[j], mean)
             flat = int(np.argmax(score))                   # first maximum
             y, x = divmod(flat, w)
             val = det[j, y, x]

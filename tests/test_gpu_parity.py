@@ -1069,8 +1069,8 @@ def test_parse_lowres_other_parser_settings(nat, ksize, pad, K, thr):
 def test_parse_lowres_planes_without_a_positive_maximum(nat):
     """refine's arg-max shortcut takes the plane maximum from the top-k table; a joint whose map is nowhere
     positive (its top-k rows are padding) or that is zero everywhere (every pixel attains the maximum) must
-    still refine to the oracle's np.argmax.  (Plateaus of equal POSITIVE values are left out: the order in which
-    torch.topk returns tied candidates is not defined, here or in the reference.)"""
+    still refine to the oracle's np.argmax.  (Plateaus and other ties of equal POSITIVE values, whose order
+    torch.topk does not define, are pinned against the oracle's stable top-k in tests/test_decode_ties_gpu.py.)"""
     sets = [synth.make_lowres_maps(P, 192, 256, seed=40 + P) for P in (3, 4)]
     refined = np.concatenate([s[0] for s in sets]).copy()
     tags = np.concatenate([s[1] for s in sets])
