@@ -663,11 +663,13 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
                                 void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev);
 
 /* The entries of the per-image decode size (every image of a batch decoded at its own (oh_n, ow_n)) are declared in
- * rtpe_hip_sizes.h, included below: part of this ABI and of this revision. */
+ * rtpe_hip_sizes.h, included below: part of this ABI and of this revision.  So are those of the batched
+ * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h. */
 
 #ifdef __cplusplus
 }
 #endif
 #include "rtpe_hip_sizes.h"
+#include "rtpe_hip_warp.h"
 
 #endif /* RTPE_HIP_H */

@@ -7,7 +7,7 @@ instructions (``python -c "import __graft_entry__ as g; g.build()"``).
 import ctypes
 import os
 from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64,
-                    c_size_t, c_uint32, c_void_p)
+                    c_size_t, c_uint32, c_uint64, c_void_p)
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # RTPE_LIBRARY: another build of the same ABI (A/B measurements of two builds on one GPU box)
@@ -174,8 +174,18 @@ for _name in ("rtpe_topk_fused", "rtpe_adjust_refine_fused_topk"):
 _SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes_n"] = (
     c_int32, _SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes"][1] + [c_void_p])
 
+# batched pre-processing (include/rtpe_hip_warp.h): the job table of a chunk (host) and its launch
+_SIGS_WARP = {
+    "rtpe_warp_batch_table_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_warp_batch_table_fill": (c_int32, [POINTER(c_uint64), POINTER(c_int32), POINTER(c_float), POINTER(c_uint64),
+                                             POINTER(c_int32), c_int32, c_int32, c_void_p, c_size_t]),
+    "rtpe_warp_normalize_batch": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_float),
+                                            POINTER(c_float), c_int32, c_void_p]),
+}
+
 EXPORTS = tuple(_SIGS)                  # the prototypes of include/rtpe_hip.h itself
 EXPORTS_SIZES = tuple(_SIGS_SIZES)      # those of include/rtpe_hip_sizes.h, which it includes
+EXPORTS_WARP = tuple(_SIGS_WARP)        # those of include/rtpe_hip_warp.h, likewise
 _lib = None
 
 
@@ -197,7 +207,7 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -170,11 +170,20 @@ def _match_kw(match_on):
     return {} if match_on is None else {"match_on": match_on}
 
 
-def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk):
+def _warp_mode(warp):
+    """the ``warp`` keyword of the batched drivers, checked before any GPU work: True for ``"batch"``"""
+    if warp not in ("image", "batch"):
+        raise ValueError("warp must be 'image' or 'batch', not %r" % (warp,))
+    return warp == "batch"
+
+
+def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk, batch_scales=None):
     """the tail of the batched drivers: images of one ``sizes`` entry form a group (``entry[base]`` is its
     projection size ``(w, h)``), a group is cut into chunks of ``batch_size``, ``warp_chunk(warp)`` makes one item of
     ``pipe.stream`` from ``warp(s, lo)`` - the chunk's images warped at scale ``s`` as one tensor - and the keypoints
-    are mapped back with the centre / scale the LAST warp of an image left.  Warps as lazily as the pipeline asks."""
+    are mapped back with the centre / scale the LAST warp of an image left.  Warps as lazily as the pipeline asks.
+    ``batch_scales`` (``warp="batch"``): every ``(s, lo)`` that ``warp_chunk`` asks for, in its order; a chunk is then
+    made by ONE ``transforms.warp_normalize_batch`` call for all of them, and ``warp`` only hands its tensors out."""
     from .third_party import transforms
     out = [None] * len(images)
     for key, idx in group_by_input_size(sizes):
@@ -183,6 +192,14 @@ def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chun
         meta = {}
 
         def batch(c):
+            if batch_scales is not None:
+                ts, centers, scale_arrays = transforms.warp_normalize_batch(
+                    [images[i] for i in c], input_size, batch_scales, device=pipe.device)
+                for n, i in enumerate(c):
+                    meta[i] = (centers[n][-1], scale_arrays[n][-1])
+                by_scale = dict(zip(batch_scales, ts))
+                return warp_chunk(lambda s, lo: by_scale[(s, lo)])
+
             def warp(s, lo):
                 ts = []
                 for i in c:
@@ -200,7 +217,7 @@ def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chun
 
 
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
-                        device="cuda", ags=False, match_on=None):
+                        device="cuda", ags=False, match_on=None, warp="image"):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
     flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
     warped to its network input size, images of one size are batched (``batch_size`` at a time) through
@@ -213,12 +230,16 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there).
 
     ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``: where the candidates are grouped into
-    people; None leaves the parser as it is)."""
+    people; None leaves the parser as it is).
+
+    ``warp``: ``"image"`` warps one image at a time (``transforms.warp_normalize``), ``"batch"`` a whole chunk with
+    one upload and one launch (``transforms.warp_normalize_batch``, needs real uint8 images); same bits."""
     from .engine import TeacherPipeline
     from .third_party import transforms
+    batched = _warp_mode(warp)
     if ags:
         return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
-                                           device=device, ags=True, **_match_kw(match_on))
+                                           device=device, ags=True, warp=warp, **_match_kw(match_on))
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
     if batch_size < 1:
@@ -226,7 +247,8 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     images = list(images)
     sizes = [(transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0],) for img in images]
     pipe = TeacherPipeline(model, parser, device=device, flip_test=True, **_match_kw(match_on))
-    return _stream_by_size(pipe, images, input_size, sizes, 0, batch_size, lambda warp: warp(1, 1))
+    return _stream_by_size(pipe, images, input_size, sizes, 0, batch_size, lambda warp: warp(1, 1),
+                           [(1, 1)] if batched else None)
 
 
 def check_scale_factors(scale_factors):
@@ -261,7 +283,7 @@ def multi_scale_input_sizes(image, input_size, scale_factors):
 
 def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
                                 adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda",
-                                ags=False, match_on=None):
+                                ags=False, match_on=None, warp="image"):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
     project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
     sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
@@ -276,8 +298,12 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     refines whatever ``adjust`` / ``refine`` say (the pipeline always does both), and ``parser.tag_per_joint`` is set to
     False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``.
 
-    ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is)."""
+    ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).
+
+    ``warp``: ``"image"`` warps one image and one scale at a time, ``"batch"`` a whole chunk at every scale with one
+    upload and one launch per scale (``transforms.warp_normalize_batch``, needs real uint8 images); same bits."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
+    batched = _warp_mode(warp)
     scales = check_scale_factors(scale_factors)
     if not ags and not parser.tag_per_joint:
         raise ValueError("multi_scale_batch_inference: needs a parser with tag_per_joint=True")
@@ -293,7 +319,7 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
                            ags=ags, **_match_kw(match_on))
     # one tensor per scale, largest first: the last warp, whose centre / scale is kept, is the smallest scale's
     return _stream_by_size(pipe, images, input_size, sizes, base, batch_size,
-                           lambda warp: [warp(s, lo) for s in scales])
+                           lambda warp: [warp(s, lo) for s in scales], [(s, lo) for s in scales] if batched else None)
 
 
 class _Shape:
@@ -325,7 +351,7 @@ def plain_plan(shapes, input_size=640, batch_size=32, max_forward_pixels=None, b
 
 
 def plain_inference(model, parser, images, input_size=640, batch_size=32, max_forward_pixels=None, device="cuda",
-                    match_on=None):
+                    match_on=None, warp="image"):
     """The batched ``validate_hhrnet.py:84-105`` over a list of (h, w, 3) uint8 images: every image is warped to its
     network input size (``warp_normalize(img, input_size, 1, 1)``), images of one INPUT size are batched whatever
     their original sizes - at most ``batch_size`` images and ``max_forward_pixels`` input pixels per forward
@@ -339,10 +365,13 @@ def plain_inference(model, parser, images, input_size=640, batch_size=32, max_fo
 
     (the forward is batch-invariant).  This protocol has no ``get_final_preds`` step.  ``match_on``: passed to
     ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).  The batches are planned, and
-    an image beyond the pixel budget refused, before any GPU work."""
+    an image beyond the pixel budget refused, before any GPU work.  ``warp``: ``"image"`` makes a batch with one
+    ``warp_normalize`` call per image and a concatenation, ``"batch"`` with one ``transforms.warp_normalize_batch``
+    call (one upload, one launch; needs real uint8 images); same bits."""
     from .engine import TeacherPipeline
     from .third_party import transforms
     kw = _match_kw(match_on)
+    batched = _warp_mode(warp)
     images = list(images)
     shapes = [tuple(int(v) for v in img.shape[:2]) for img in images]
     chunks = plain_plan(shapes, input_size, batch_size, max_forward_pixels)
@@ -352,6 +381,9 @@ def plain_inference(model, parser, images, input_size=640, batch_size=32, max_fo
     pipe = TeacherPipeline(model, parser, device=device, **kw)
 
     def batch(c):
+        if batched:
+            return transforms.warp_normalize_batch([images[i] for i in c], input_size, ((1, 1),),
+                                                   device=pipe.device)[0][0]
         return torch.cat([transforms.warp_normalize(images[i], input_size, 1, 1, device=pipe.device)[0] for i in c])
     with torch.no_grad():
         results = pipe.stream((batch(c) for c in chunks), out_hw=lambda k: [shapes[i] for i in chunks[k]])

@@ -16,9 +16,18 @@ In one process: seeded synthetic W0 weights (noise maps: the decode's worst case
 --what equal   batch 32, 640 x 640, all sizes equal: TeacherPipeline.stream with the list form (A) against the tuple
     form (B), --steps batches per run, the same order and statistics.
 
+--what warp   what making the input batches costs: the seeded mix through rtpe.inference.plain_inference with
+    warp="image" (A: one upload, one allocation and one launch per image, then a concatenation) and warp="batch"
+    (B: transforms.warp_normalize_batch, one upload and one launch per batch), and the first --ms-images images of the
+    mix through multi_scale_batch_inference((2, 1, 0.5), flip_test=True) likewise (A: three uploads and launches per
+    image).  The same order, repeats and statistics; besides images/s and the CPU time of the process, the wall time
+    the host spends PRODUCING the batches (around the `next` of the generator the pipeline draws them from, no device
+    synchronisation), per batch.  The results of A and B are compared bit for bit.
+
 Prints one JSON line per --what (--out FILE also writes them).  Needs a GPU; there is no fallback.
 
-    python tools/mixed_size_bench.py [--what mix equal] [--images 256] [--repeats 4] [--out profiles/mixed_size_bench.json]
+    python tools/mixed_size_bench.py [--what mix equal warp] [--images 256] [--repeats 4] [--out profiles/mixed_size_bench.json]
+    python tools/mixed_size_bench.py --what warp --out profiles/warp_batch_bench.json
 
 GPU time of the decode kernels (a run of its own, the timing above is not taken under the profiler):
 
@@ -28,6 +37,16 @@ GPU time of the decode kernels (a run of its own, the timing above is not taken 
 
 --only FORM runs `--warmup + --steps` batches of the equal-size stream in that form and nothing else; --summarize reads
 the two *_kernel_stats.csv and writes the decode kernels of either form with calls and microseconds per call.
+
+GPU time of the two warp kernels and the number of copies (again runs of their own):
+
+    rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d DIR/image -o t -- python tools/mixed_size_bench.py --only-warp image --images 64 --ms-images 8
+    rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d DIR/batch -o t -- python tools/mixed_size_bench.py --only-warp batch --images 64 --ms-images 8
+    python tools/mixed_size_bench.py --summarize-warp DIR --csv profiles/warp_batch_kernel_stats.csv
+
+--only-warp MODE runs one pass of either protocol with that warp and nothing else; --summarize-warp writes, per mode,
+calls and microseconds per call of warp_normalize_kernel / warp_normalize_batch_kernel and of the concatenation kernel,
+and the copies by direction.
 """
 import argparse
 import csv
@@ -89,6 +108,44 @@ def summarize(args):
     print(json.dumps(out))
 
 
+WARP_KERNELS = ("warp_normalize_batch_kernel", "warp_normalize_kernel", "CatArrayBatchedCopy")
+
+
+def summarize_warp(args):
+    """DIR/image and DIR/batch -> one CSV: the warp kernels (and torch.cat's copy kernel) and the copies of either mode"""
+    rows = []
+    for mode in ("image", "batch"):
+        def one(pattern):
+            files = glob.glob(os.path.join(args.summarize_warp, mode, "**", pattern), recursive=True)
+            if len(files) > 1:
+                raise SystemExit("mixed_size_bench: more than one %s under %s/%s" % (pattern, args.summarize_warp, mode))
+            return files[0] if files else None
+        path = one("*kernel_stats.csv")
+        if path is None:
+            raise SystemExit("mixed_size_bench: no *kernel_stats.csv under %s/%s" % (args.summarize_warp, mode))
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                kernel = next((k for k in WARP_KERNELS if k in r["Name"]), None)
+                if kernel is not None:
+                    rows.append({"warp": mode, "kind": "kernel", "what": kernel, "calls": int(r["Calls"]),
+                                 "total_ns": int(r["TotalDurationNs"]),
+                                 "us_per_call": round(int(r["TotalDurationNs"]) / 1e3 / int(r["Calls"]), 2),
+                                 "name": r["Name"]})
+        path = one("*memory_copy_stats.csv")
+        if path is not None:
+            with open(path) as f:
+                for r in csv.DictReader(f):
+                    rows.append({"warp": mode, "kind": "copy", "what": r["Name"], "calls": int(r["Calls"]),
+                                 "total_ns": int(r["TotalDurationNs"]),
+                                 "us_per_call": round(int(r["TotalDurationNs"]) / 1e3 / int(r["Calls"]), 2), "name": ""})
+    with open(args.csv, "w", newline="") as f:
+        w = csv.DictWriter(f, ["warp", "kind", "what", "calls", "total_ns", "us_per_call", "name"])
+        w.writeheader()
+        w.writerows(rows)
+    print(json.dumps({"metric": "warp_kernel_time", "rows": [{k: r[k] for k in ("warp", "kind", "what", "calls",
+                                                                                 "us_per_call")} for r in rows]}))
+
+
 def stats(runs):
     import numpy as np
     v, cpu = [a for a, _ in runs], [b for _, b in runs]
@@ -98,7 +155,12 @@ def stats(runs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["mix"], choices=("mix", "equal"))
+    ap.add_argument("--what", nargs="+", default=["mix"], choices=("mix", "equal", "warp"))
+    ap.add_argument("--ms-images", type=int, default=32, help="images of the multi-scale leg of --what warp")
+    ap.add_argument("--only-warp", choices=("image", "batch"),
+                    help="one pass of both protocols with this warp alone (for a profiler), no timing")
+    ap.add_argument("--summarize-warp", metavar="DIR",
+                    help="DIR/image and DIR/batch: rocprofv3 --kernel-trace --memory-copy-trace --stats output")
     ap.add_argument("--images", type=int, default=256, help="images of the seeded mix")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=640)
@@ -113,6 +175,8 @@ def main():
     args = ap.parse_args()
     if args.summarize:
         return summarize(args)
+    if args.summarize_warp:
+        return summarize_warp(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -153,6 +217,87 @@ def main():
                 _, dt, cpu = timed(modes[m])
                 runs[m].append((round(n_images / dt, 1), round(cpu, 1)))
         return {m: stats(rr) for m, rr in runs.items()}
+
+    if args.only_warp or "warp" in args.what:
+        produce = []        # seconds the host spent in `next` of the batch generator, one entry per batch
+
+        class TimedPipeline(engine.TeacherPipeline):
+            """stream() draws its batches through a generator that times each `next` on the host (no device sync)"""
+
+            def stream(self, batches, *a, **kw):
+                def drawn():
+                    it = iter(batches)
+                    while True:
+                        t0 = time.perf_counter()
+                        try:
+                            x = next(it)
+                        except StopIteration:
+                            return
+                        produce.append(time.perf_counter() - t0)
+                        yield x
+                return super().stream(drawn(), *a, **kw)
+        engine.TeacherPipeline = TimedPipeline          # the drivers import the name when they are called
+        sizes = mix_sizes(args.images)
+        rng = np.random.default_rng(5)
+        images = [rng.integers(0, 256, s + (3,), dtype=np.uint8) for s in sizes]
+        ms_images = images[:args.ms_images]
+        ms_scales = (2, 1, 0.5)
+        legs = {
+            "plain": (images, lambda warp: inference.plain_inference(
+                model, parser(), images, args.size, args.batch, device=dev, match_on=args.match_on, warp=warp)),
+            "multi_scale": (ms_images, lambda warp: inference.multi_scale_batch_inference(
+                model, parser(), ms_images, args.size, ms_scales, True, batch_size=args.batch, device=dev,
+                match_on=args.match_on, warp=warp)),
+        }
+        if args.only_warp:
+            for name, (imgs, run) in legs.items():
+                run(args.only_warp)
+            torch.cuda.synchronize(dev)
+            print(json.dumps({"metric": "warp_profile_run", "warp": args.only_warp, "images": len(images),
+                              "ms_images": len(ms_images), "batches": len(produce)}))
+            return
+
+        def same_results(ra, rb):
+            def rows(r):
+                return [np.asarray(p, np.float32) for p in (r[0] if isinstance(r[0], list) else [r[0]])]
+            return all(len(rows(a)) == len(rows(b)) and all(np.array_equal(x, y) for x, y in zip(rows(a), rows(b)))
+                       and np.array_equal(np.array(a[1], np.float32), np.array(b[1], np.float32))
+                       for a, b in zip(ra, rb))
+        for name, (imgs, run) in legs.items():
+            first = {}
+            for warp in ("image", "batch"):
+                first[warp], dt, _ = timed(lambda: run(warp))
+                first[warp + "_s"] = round(dt, 2)
+            host = {"image": [], "batch": []}
+
+            def mode(warp):
+                def fn():
+                    del produce[:]
+                    res = run(warp)
+                    host[warp].append((round(sum(produce) * 1e3, 2), len(produce)))
+                    return res
+                return fn
+            res = interleave({"warp_image": mode("image"), "warp_batch": mode("batch")}, len(imgs))
+            for warp in ("image", "batch"):
+                ms_total = [h[0] for h in host[warp]]
+                n_batches = host[warp][0][1]
+                scales_per_image = len(ms_scales) if name == "multi_scale" else 1
+                res["warp_" + warp].update(
+                    batches_per_pass=n_batches, first_pass_s=first[warp + "_s"],
+                    produce_host_ms_per_pass=round(float(np.median(ms_total)), 2), produce_host_ms_per_pass_runs=ms_total,
+                    produce_host_ms_per_batch=round(float(np.median(ms_total)) / n_batches, 3),
+                    uploads_per_pass=len(imgs) * scales_per_image if warp == "image" else n_batches,
+                    warp_launches_per_pass=(len(imgs) if warp == "image" else n_batches) * scales_per_image)
+            res["speedup_img_s"] = round(res["warp_batch"]["img_s"] / res["warp_image"]["img_s"], 4)
+            res["produce_host_ratio"] = round(res["warp_image"]["produce_host_ms_per_pass"]
+                                              / max(res["warp_batch"]["produce_host_ms_per_pass"], 1e-9), 2)
+            lines.append(dict(common, metric="warp_image_against_warp_batch", protocol=name, images=len(imgs),
+                              batch=args.batch, input_size=args.size,
+                              scales=list(ms_scales) if name == "multi_scale" else [1], flip=name == "multi_scale",
+                              people=sum(len(r[0]) if isinstance(r[0], list) else (len(r[0]) if r[0].ndim == 3 else 0)
+                                         for r in first["image"]),
+                              results_bit_identical=bool(same_results(first["image"], first["batch"])), **res))
+        engine.TeacherPipeline = TimedPipeline.__mro__[1]
 
     if args.only or "equal" in args.what:
         B, S = args.batch, args.size
