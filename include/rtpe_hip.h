@@ -664,12 +664,14 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 
 /* The entries of the per-image decode size (every image of a batch decoded at its own (oh_n, ow_n)) are declared in
  * rtpe_hip_sizes.h, included below: part of this ABI and of this revision.  So are those of the batched
- * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h. */
+ * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h, and those of the
+ * shared-tag decode (the dual-head students: one tag map per image), declared in rtpe_hip_shared.h. */
 
 #ifdef __cplusplus
 }
 #endif
 #include "rtpe_hip_sizes.h"
 #include "rtpe_hip_warp.h"
+#include "rtpe_hip_shared.h"
 
 #endif /* RTPE_HIP_H */

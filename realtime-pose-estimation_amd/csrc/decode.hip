@@ -73,14 +73,17 @@ struct BilinearMap {        // low-res planes sampled at (oh, ow) resolution
   __device__ __forceinline__ bool tail(int plane) const { return plane % J >= J - (J & 15); }
   __device__ __forceinline__ float at(int plane, int y, int x) const {
     const int n = plane / J, j = plane - n * J;
-    const float* b = p + (size_t)n * img_stride + (size_t)j * sh * sw;
+    return sample(p + (size_t)n * img_stride + (size_t)j * sh * sw, y, x, j >= J - (J & 15));
+  }
+  // the sample of the source plane at b; in_tail: the plane's channel lies in the tail of the 16-wide vector
+  __device__ __forceinline__ float sample(const float* b, int y, int x, bool in_tail) const {
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
     ay.at(y, &y0, &y1, &ly0, &ly1);
     ax.at(x, &x0, &x1, &lx0, &lx1);
     const float v00 = b[y0 * sw + x0], v01 = b[y0 * sw + x1];
     const float v10 = b[y1 * sw + x0], v11 = b[y1 * sw + x1];
-    if (small) return bilinear_small(v00, v01, v10, v11, ly0, ly1, lx0, lx1, j >= J - (J & 15));
+    if (small) return bilinear_small(v00, v01, v10, v11, ly0, ly1, lx0, lx1, in_tail);
     const float t0 = __builtin_fmaf(v00, lx0, v01 * lx1);
     const float t1 = __builtin_fmaf(v10, lx0, v11 * lx1);
     return __builtin_fmaf(t0, ly0, t1 * ly1);
@@ -100,6 +103,19 @@ static Axis make_axis(int n_in, int n_out) {
 struct BilinearTag {        // D == 1
   BilinearMap m;
   __device__ __forceinline__ float at(int plane, int y, int x, int) const { return m.at(plane, y, x); }
+};
+
+// One tag plane per image, shared by all its joints (the dual-head students' det[:, J:J+1]): D == 1, (N, 1, th, tw) at
+// an image stride.  The (image * J + joint) plane index that the top-k merge (tag_shared_joints = 0) and the adjust /
+// refine kernels pass selects the image's plane here, and only here.  The sample is BilinearMap::at's on channel
+// `joint` of the plane expanded to (N, J, th, tw): the same taps and weights, and for a small output the tap order of
+// that channel (the tail of the 16-wide vector or not) - the joint decides no address, only that order.
+struct SharedBilinearTag {
+  BilinearMap m;            // p, img_stride: the shared planes; J: the joints that share one
+  __device__ __forceinline__ float at(int plane, int y, int x, int) const {
+    const int n = plane / m.J, j = plane - n * m.J;
+    return m.sample(m.p + (size_t)n * m.img_stride, y, x, j >= m.J - (m.J & 15));
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -1811,6 +1827,72 @@ extern "C" int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int3
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_n: P_dev is null");
   return decode_adjust_refine("adjust_refine_fused_topk_n",
                               NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev, true);
+}
+
+// ---------------------------------------------------------------------------
+// the outputs of a dual-head student as they are: NetSrc with ONE tag plane per image, (N, 1, th, tw) at
+// tg_img_stride, shared by the J joints (SharedBilinearTag).  Both maps may be channel slices of one (N, J + 1, h, w)
+// tensor: the strides say where an image's planes start.  Bit for bit NetSrc on the tag plane expanded to J channels.
+// ---------------------------------------------------------------------------
+struct NetSharedSrc {
+  const float* hm;
+  int32_t hh, hw;
+  int64_t hm_img_stride;
+  const float* tg;
+  int32_t th, tw;
+  int64_t tg_img_stride;
+  int32_t N, J, oh, ow;
+  int check(const char* who) const {
+    RTPE_REQUIRE(hm && tg, "%s: null argument", who);
+    RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "%s: bad argument (N=%d, J=%d; J <= %d)", who, N, J, kMaxJ);
+    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
+    RTPE_REQUIRE(hm_img_stride >= (int64_t)J * hh * hw && tg_img_stride >= (int64_t)th * tw,
+                 "%s: an image stride is below the size of an image's planes", who);
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    return f(make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow),
+             SharedBilinearTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)}, 1);
+  }
+};
+
+extern "C" int rtpe_topk_fused_shared(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
+                                      int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J, int32_t oh,
+                                      int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
+                                      int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes,
+                                      void* stream) {
+  return decode_topk("topk_fused_shared",
+                     NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow}, K, nms_ksize,
+                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rtpe_adjust_refine_fused_shared_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                    const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                    int32_t N, int32_t J, int32_t oh, int32_t ow, const float* ans_in,
+                                                    float* ans_out, const int32_t* person_img, int32_t P,
+                                                    int32_t do_adjust, int32_t do_refine, float* scores,
+                                                    const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                    void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_adjust_refine("adjust_refine_fused_shared_topk",
+                              NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr, true);
+}
+
+extern "C" int rtpe_adjust_refine_fused_shared_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                      const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                      int32_t N, int32_t J, int32_t oh, int32_t ow,
+                                                      const float* ans_in, float* ans_out, const int32_t* person_img,
+                                                      int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
+                                                      const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                      void* scratch, size_t scratch_bytes, void* stream,
+                                                      const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_shared_topk_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_fused_shared_topk_n",
+                              NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
                               {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
                                scratch, scratch_bytes, stream}, P_dev, true);
 }

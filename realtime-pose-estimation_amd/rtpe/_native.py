@@ -183,9 +183,17 @@ _SIGS_WARP = {
                                             POINTER(c_float), c_int32, c_void_p]),
 }
 
+# shared-tag decode (include/rtpe_hip_shared.h): the arguments of the entries without "_shared", `tg` one plane per image
+_SIGS_SHARED = {
+    "rtpe_topk_fused_shared": (c_int32, list(_SIGS["rtpe_topk_fused"][1])),
+    "rtpe_adjust_refine_fused_shared_topk": (c_int32, list(_SIGS["rtpe_adjust_refine_fused_topk"][1])),
+    "rtpe_adjust_refine_fused_shared_topk_n": (c_int32, list(_SIGS["rtpe_adjust_refine_fused_topk_n"][1])),
+}
+
 EXPORTS = tuple(_SIGS)                  # the prototypes of include/rtpe_hip.h itself
 EXPORTS_SIZES = tuple(_SIGS_SIZES)      # those of include/rtpe_hip_sizes.h, which it includes
 EXPORTS_WARP = tuple(_SIGS_WARP)        # those of include/rtpe_hip_warp.h, likewise
+EXPORTS_SHARED = tuple(_SIGS_SHARED)    # those of include/rtpe_hip_shared.h, likewise
 _lib = None
 
 
@@ -207,7 +215,8 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
+                list(_SIGS_SHARED.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -229,6 +229,27 @@ class TeacherPipeline:
         from .inference import resize_combine
         return resize_combine(images, images.shape[2:], flip=True)
 
+    # The two steps of ``stream()`` that depend on the model (StudentPipeline overrides them); multi-scale batches take
+    # their own path through the loop.
+    def _stream_forwards(self, k, x, on_forward):
+        """the forwards of batch k on the current stream -> the tuple of FRESH output tensors the decode reads:
+        (preds, refined), followed by those of the mirror image with flip_test (the mirrored input is made and read on
+        the same stream)"""
+        fwd = on_forward if on_forward is not None else (lambda _k, t: self.model(t))
+        preds, refined = fwd(k, x)
+        if not self.flip_test:
+            return preds, refined
+        preds_f, refined_f = fwd(k, self.mirror(x))
+        return preds, refined, preds_f, refined_f
+
+    def _stream_topk(self, outs, hw):
+        """phase 1 of the decode from the outputs of ``_stream_forwards`` (on the decode stream) -> the state that
+        ``lowres_match`` / ``lowres_finish`` take"""
+        if self.flip_test:
+            return self.parser.flip_topk(*outs, hw, self.flip_index)
+        preds, refined = outs
+        return self.parser.lowres_topk(refined, preds[:, NUM_HEATMAPS:], hw)
+
     @torch.no_grad()
     def __call__(self, images, out_hw=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
@@ -327,14 +348,7 @@ class TeacherPipeline:
         # ``on_forward`` must return FRESH output tensors for every batch (the plain forward does): the decode of
         # batch k runs on the side stream while F(k+1) runs on the main one, and nothing makes F(k+1) wait for it.
         def run_forwards(k, x):
-            """(preds, refined) of batch k, followed by those of its mirror image with flip_test (both on the current
-            stream: the mirrored input is made and read there)"""
-            fwd = on_forward if on_forward is not None else (lambda _k, t: self.model(t))
-            preds, refined = fwd(k, x)
-            if not self.flip_test:
-                return preds, refined
-            preds_f, refined_f = fwd(k, self.mirror(x))
-            return preds, refined, preds_f, refined_f
+            return self._stream_forwards(k, x, on_forward)
 
         ms = self.scale_factors is not None
 
@@ -370,7 +384,7 @@ class TeacherPipeline:
                                 if other is not fs:
                                     fs.wait_stream(other)
                         after_alone = fs if alone else None
-                        for t in (xs if ms else [x]):
+                        for t in (xs if ms else [x] if torch.is_tensor(x) else x):     # (a pair: StudentPipeline's (x, alt))
                             t.record_stream(fs)
                         # lanes off for THIS call only (a per-call flag of the ABI: nothing process-wide is touched,
                         # and nothing stays changed while the generator is suspended or if it is abandoned)
@@ -384,7 +398,8 @@ class TeacherPipeline:
                             set_workspace_slot(prev_slot)
                     else:
                         outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
-                    hw = None if ms else hw_k if hw_k is not None else tuple(x.shape[2:])
+                    hw = None if ms else hw_k if hw_k is not None else \
+                        tuple((x if torch.is_tensor(x) else x[0]).shape[2:])
                     f_done = None
                     if side is not None or fs is not main:
                         f_done = torch.cuda.Event()
@@ -397,12 +412,8 @@ class TeacherPipeline:
                         on_decode_stream(P.lowres_match, topk_done)     # host matching overlaps F(k) on the GPU
                     if ms:
                         st = on_decode_stream(P.ms_topk, st_ms, after=f_done)
-                    elif self.flip_test:
-                        st = on_decode_stream(P.flip_topk, *outs, hw, self.flip_index, after=f_done, uses=outs)
                     else:
-                        preds, refined = outs
-                        st = on_decode_stream(P.lowres_topk, refined, preds[:, NUM_HEATMAPS:], hw, after=f_done,
-                                              uses=outs)
+                        st = on_decode_stream(self._stream_topk, outs, hw, after=f_done, uses=outs)
                     if refine_done is not None:
                         yield P.lowres_finish(refine_done)
                     refine_done, topk_done = topk_done, st
@@ -430,6 +441,62 @@ class TeacherPipeline:
         if not _collectives_on(force_collective):
             return rec
         return all_gather_records(rec, equal_counts)
+
+
+class StudentPipeline(TeacherPipeline):
+    """``TeacherPipeline`` for the dual-head students (rtpe/students.py ``AttentionStudent``, ``AttentionStudentSteps``;
+    any module whose forward returns ``(att, det)`` with det (N, J + 1, h, w): J heat maps, then ONE tag map shared by
+    all joints): batched forward on the HIP executor, then EVERY image of the batch decoded straight from ``det`` with
+    ``HeatmapParser.parse_lowres_shared`` - no channel slice is copied and the tag map is never expanded.  Per image
+    the result is bit-identical to what ``eval_student`` computes for image 0 of a batch,
+    ``parse_lowres(det[:, :J].contiguous(), det[:, J:].expand(-1, J, -1, -1).contiguous(), out_hw)``.
+
+    A batch is a tensor ``x`` (N,3,H,W) or a pair ``(x, alt)``, forwarded as ``model(x, alt=alt)`` (``alt``: the image
+    in the alternative colour space; ``AttentionStudentSteps`` refuses to run without it).  ``stream()`` is
+    ``TeacherPipeline.stream`` - the same loop, order, decode stream, forward streams / workspace slots, ``out_hw``
+    callable and two-step delay; ``on_forward(k, batch)`` gets the batch as it was given and returns ``(att, det)``.
+    One decode size per batch.  ``match_on`` as for ``TeacherPipeline``; ``gather`` is inherited.
+
+    There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
+
+    def __init__(self, model, parser=None, device=None, match_on=None, flip_test=False, scale_factors=None, ags=False):
+        if flip_test or scale_factors is not None or ags:       # (before any GPU work)
+            raise ValueError("StudentPipeline: flip_test, scale_factors and ags are test protocols of the teacher; "
+                             "the students have the plain protocol only")
+        super().__init__(model, parser, device, match_on=match_on)
+
+    def _decode_hw(self, out_hw, images):
+        hw = super()._decode_hw(out_hw, images)
+        if hw is not None and len(hw) and hasattr(hw[0], "__len__"):
+            raise ValueError("StudentPipeline: one decode size (h, w) per batch; per-image sizes are for the teacher's "
+                             "plain protocol only")
+        return hw
+
+    def _forward(self, batch):
+        x, alt = (batch, None) if torch.is_tensor(batch) else batch
+        out = self.model(x) if alt is None else self.model(x, alt=alt)
+        if not isinstance(out, (list, tuple)) or len(out) != 2 or out[1].dim() != 4 or out[1].shape[1] < 2:
+            raise TypeError("StudentPipeline: the model must return (att, det) with det (N, J + 1, h, w)")
+        return out[0], out[1]
+
+    def _stream_forwards(self, k, x, on_forward):
+        att, det = on_forward(k, x) if on_forward is not None else self._forward(x)
+        return att, det
+
+    def _stream_topk(self, outs, hw):
+        det = outs[1].float()
+        J = det.shape[1] - 1
+        return self.parser.lowres_topk_shared(det[:, :J], det[:, J:], hw)
+
+    @torch.no_grad()
+    def __call__(self, images, out_hw=None, alt=None):
+        """images (N,3,H,W) on the GPU [, alt (N,3,H,W)] -> list of (people, scores) for all N images; out_hw = the
+        decode resolution (h, w), default (H, W)"""
+        hw = self._decode_hw(out_hw, images)
+        outs = self._forward(images if alt is None else (images, alt))
+        st = self._stream_topk(outs, hw if hw is not None else tuple(images.shape[2:]))
+        self.parser.lowres_match(st)
+        return self.parser.lowres_finish(st)
 
 
 def _collectives_on(force_collective=False):
