@@ -99,7 +99,10 @@ int rtpe_device_count(void);
 #define RTPE_OP_CAST 4        /* fp16 NHWC -> fp32 NHWC: tofp32 after the half-wrapped stem of
                                  the students, fp16util.py:64-68, students.py:732-733 */
 #define RTPE_OP_AVGPOOL 5     /* AvgPool2d(3, 2, 1, count_include_pad=False), fp32,
-                                 students.py:657-666                            */
+                                 students.py:657-666; the input map must have even
+                                 sides at the forward's size (the output tensor sits
+                                 one ds level down): a forward whose map has an odd
+                                 side returns RTPE_E_INVALID before any launch  */
 #define RTPE_OP_SE 6          /* SELayer gate, students.py:118-142: cin = C, cout =
                                  hidden; w_off -> fc1 w (hid,C), b1, fc2 w (C,hid),
                                  b2 (fp32); output = per-image vector tensor    */

@@ -541,6 +541,17 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
   slot_layout(h, N, H, W, &offs, &need);
   if (need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, need); return RTPE_E_NOMEM; }
   RTPE_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
+  // Shapes an op cannot take are refused here, before the first launch, so that no half-run forward is left behind.
+  // avgpool: the kernel writes ceil(Hi / 2) x ceil(Wi / 2) pixels, the output tensor holds (H >> ds) x (W >> ds): a map
+  // with an odd side (1 x 1, 2 x 1) would be written beyond its tensor
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    const rtpe_op_desc& d = h->ops[i].d;
+    if (d.kind != RTPE_OP_AVGPOOL || (only_op >= 0 && (int)i != only_op)) continue;
+    const int Hi = H >> h->tensors[d.in_t].ds_log2, Wi = W >> h->tensors[d.in_t].ds_log2;
+    const int Ho = H >> h->tensors[d.out_t].ds_log2, Wo = W >> h->tensors[d.out_t].ds_log2;
+    RTPE_REQUIRE((Hi + 1) / 2 == Ho && (Wi + 1) / 2 == Wo,
+                 "avgpool: a %d x %d map does not pool into the %d x %d output tensor", Hi, Wi, Ho, Wo);
+  }
   char* base = reinterpret_cast<char*>(ws);
   auto esz = [&](int t) -> size_t { return h->tensors[t].reserved == 4 ? 4 : 2; };
   auto tptr = [&](int t, int coff) -> _Float16* {      // element type per tensor (fp16 or fp32): byte arithmetic
