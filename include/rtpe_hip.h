@@ -140,6 +140,14 @@ int rtpe_device_count(void);
                                 Bottlenecks, pose_higher_hrnet.py:96-116; option "pair_1x1").  The program's
                                 slot assignment must keep the head's input and residual alive over the tail */
 #define RTPE_F_PAIR_TAIL 128
+#define RTPE_F_PAIR_PROJ 256 /* (added within ABI revision 4: a hint, an older library runs the op as any other conv) conv 1x1
+                                64 -> 256 + BN, no ReLU, no residual, whose output is the residual of a RTPE_F_PAIR_HEAD op
+                                and is read by no other op (the skip projection of layer1's first Bottleneck,
+                                pose_higher_hrnet.py:99-100): the pair kernel may compute it from the op's 64-channel
+                                input instead of reading it back (option "pair_proj"); the op then launches nothing and
+                                its output tensor is not written.  The program's slot assignment must keep the op's
+                                INPUT alive over the pair's tail.  As with the pair flags the executor checks the rest
+                                itself and ignores the flag on anything else */
 
 typedef struct rtpe_tensor_desc {
   int32_t channels; /* allocated channels per pixel (the NHWC row length)     */
@@ -285,7 +293,10 @@ int rtpe_hrnet_autotune_aux(rtpe_hrnet* h, const void* x, int32_t x_dtype, const
  * "conv48s2" (env RTPE_CONV48S2; added within ABI revision 4): 3x3 stride-2 convs from 48 input channels to 48 / 96 / 192 / 384
  * output channels run 1 = on persistent workgroups with register-resident weights, neighbouring ones that read the same input
  * (the first downsampling convs of a fuse layer) as ONE launch (csrc/conv48s2.hip; default), 0 = each on the launch shape chosen
- * for it.  Same bits. */
+ * for it.  Same bits.
+ * "pair_proj" (env RTPE_PAIR_PROJ; added within ABI revision 4): an op flagged RTPE_F_PAIR_PROJ is 1 = computed inside the
+ * pair kernel that consumes it, in whole forwards with "pair_1x1" on (csrc/conv_pair.hip; default; rtpe_hrnet_op_tile reports
+ * the op with no workgroups), 0 = run as a launch of its own.  Same bits. */
 int rtpe_set_option(const char* name, int32_t value);
 /* The value an option has NOW (set by rtpe_set_option, else the environment's, else the default): what the next
  * launch will use.  bench.py names the kernel it reports from this, not from the environment. */
@@ -324,7 +335,9 @@ int rtpe_hrnet_import_tuned(rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, cons
  * -(workgroups + 100000 * halo buffers) of the streaming kernel; -900001 / -900002: first /
  * second conv of a BasicBlock that runs as ONE fused kernel (conv_block.hip), launched by the
  * first; -(500000 + workgroups): the persistent 64 -> 64 3x3 kernel (conv64.hip); -600001 / -600002: the stem op / the 64 -> 64 stride-2 conv behind it when both run as
- * one kernel (stem_fused.hip, option "fused_stem"), launched at the stem op */
+ * one kernel (stem_fused.hip, option "fused_stem"), launched at the stem op; -800001 / -800002: head / tail of a 1x1 pair that
+ * runs as one kernel (conv_pair.hip), launched at the tail; out8[0] == 0 (v = -800003): an op flagged RTPE_F_PAIR_PROJ that this
+ * pair kernel computes itself at this shape - no launch of its own (option "pair_proj") */
 int rtpe_hrnet_op_tile(const rtpe_hrnet* h, int32_t op, int32_t N, int32_t H, int32_t W, int32_t* out8);
 
 /* ------------------------------------------------------------------------ *
@@ -668,7 +681,8 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 /* The entries of the per-image decode size (every image of a batch decoded at its own (oh_n, ow_n)) are declared in
  * rtpe_hip_sizes.h, included below: part of this ABI and of this revision.  So are those of the batched
  * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h, and those of the
- * shared-tag decode (the dual-head students: one tag map per image), declared in rtpe_hip_shared.h. */
+ * shared-tag decode (the dual-head students: one tag map per image), declared in rtpe_hip_shared.h, and the layer-level entry
+ * of the 1x1 pair kernel, declared in rtpe_hip_pair.h. */
 
 #ifdef __cplusplus
 }
@@ -676,5 +690,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_sizes.h"
 #include "rtpe_hip_warp.h"
 #include "rtpe_hip_shared.h"
+#include "rtpe_hip_pair.h"
 
 #endif /* RTPE_HIP_H */

@@ -38,6 +38,8 @@ struct OpState {
   int n_geom;
   int fuse;             // 1: head of a fused BasicBlock (this conv + the next run as one kernel), 2: its second conv
   int pair;             // 1: head of a 1x1 pair (conv_pair.hip: launched with the next op), 2: its tail
+  int proj_head;        // > 0: this conv is the skip projection that the 1x1 pair with head ops[proj_head] may compute itself
+  int proj_op;          // on that head: the projection's op index (else -1)
   int stem2;            // 1: the stem op whose conv1 runs together with the next op's conv2 (stem_fused.hip), 2: that conv op
   int s2g;              // n > 1: first of n neighbouring 3x3 stride-2 convs from the SAME 48-channel input that run as one launch
                         // (conv48s2.hip: the input is read once), -1: one of the others
@@ -80,10 +82,10 @@ struct rtpe_hrnet {
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 namespace rtpe {
-static int g_options[kNumOptions] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};       // -1: not set, take the environment's value
-static const char* const kOptionNames[kNumOptions] = {"block_ring", "block_pc", "direct_1x1", "lanes", "tile_dma", "pair_1x1", "fused_stem", "conv64", "head_direct", "deconv48", "conv48s2"};
-static const char* const kOptionEnv[kNumOptions] = {"RTPE_BLOCK_RING", "RTPE_BLOCK_PC", "RTPE_DIRECT_1X1", "RTPE_LANES", "RTPE_TILE_DMA", "RTPE_PAIR_1X1", "RTPE_FUSED_STEM", "RTPE_CONV64", "RTPE_HEAD_DIRECT", "RTPE_DECONV48", "RTPE_CONV48S2"};
-static const int kOptionDefault[kNumOptions] = {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+static int g_options[kNumOptions] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // -1: not set, take the environment's value
+static const char* const kOptionNames[kNumOptions] = {"block_ring", "block_pc", "direct_1x1", "lanes", "tile_dma", "pair_1x1", "fused_stem", "conv64", "head_direct", "deconv48", "conv48s2", "pair_proj"};
+static const char* const kOptionEnv[kNumOptions] = {"RTPE_BLOCK_RING", "RTPE_BLOCK_PC", "RTPE_DIRECT_1X1", "RTPE_LANES", "RTPE_TILE_DMA", "RTPE_PAIR_1X1", "RTPE_FUSED_STEM", "RTPE_CONV64", "RTPE_HEAD_DIRECT", "RTPE_DECONV48", "RTPE_CONV48S2", "RTPE_PAIR_PROJ"};
+static const int kOptionDefault[kNumOptions] = {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 int get_option(int key) {
   int v = __atomic_load_n(&g_options[key], __ATOMIC_RELAXED);
   if (v < 0) {
@@ -268,6 +270,40 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
       continue;
     a1.pair = 1;
     h->ops[i + 1].pair = 2;
+  }
+  // the skip projection of a pair's head (conv_pair.hip, PROJ): the one op p that writes the head's residual, a conv 1x1
+  // 64 -> 256 + bn of a tensor of the same map size, flagged RTPE_F_PAIR_PROJ (the program's promise that p's INPUT stays
+  // alive over the tail), whose output nobody else reads: the pair kernel computes it from p's input and p launches nothing
+  for (OpState& o : h->ops) { o.proj_head = 0; o.proj_op = -1; }
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    if (h->ops[i].pair != 1) continue;
+    const rtpe_op_desc& d1 = h->ops[i].d;
+    int pi = -1, writers = 0;
+    bool other_reader = d1.in_t == d1.res_t;
+    for (size_t k = 0; k < h->ops.size(); ++k) {
+      const rtpe_op_desc& dk = h->ops[k].d;
+      if (dk.out_t == d1.res_t) { ++writers; pi = (int)k; }
+      if (k == i) continue;
+      if ((dk.kind != RTPE_OP_FUSE && dk.in_t == d1.res_t) || dk.res_t == d1.res_t) other_reader = true;
+      for (int t = 0; t < dk.n_terms; ++t) other_reader |= dk.term_t[t] == d1.res_t;
+    }
+    if (writers != 1 || pi >= (int)i || other_reader) continue;
+    OpState& op = h->ops[pi];
+    const rtpe_op_desc& dp = op.d;
+    const int round = d1.flags & RTPE_F_ROUND_CONV;
+    if (dp.kind != RTPE_OP_CONV || op.n_geom != 1 || dp.ksize != 1 || dp.stride != 1 || dp.cin != 64 || dp.cout != 256 || dp.res_t >= 0 ||
+        dp.n_terms != 0 || dp.flags != (round | RTPE_F_PAIR_PROJ) || dp.out_coff != 0 || d1.res_coff != 0 ||
+        h->tensors[d1.res_t].channels != 256 || dp.reserved[1] > 1 || dp.reserved[2] > 0 || h->tensors[dp.in_t].reserved == 4 ||
+        h->tensors[dp.in_t].ds_log2 != h->tensors[d1.in_t].ds_log2 || dp.in_t == d1.out_t || dp.in_t == h->ops[i + 1].d.out_t ||
+        op.fuse || op.stem2 || op.pair)
+      continue;
+    // the pair reads p's input at the tail's launch: nobody may write it between p and the tail, and the tail's stream must be
+    // behind whatever p's stream waited for (the head outside any region: behind the join; or on p's own lane)
+    bool ok = d1.region == 0 || (d1.region == dp.region && d1.lane == dp.lane);
+    for (size_t k = pi; k <= i + 1 && ok; ++k) ok = h->ops[k].d.out_t != dp.in_t;
+    if (!ok) continue;
+    op.proj_head = (int)i;
+    h->ops[i].proj_op = pi;
   }
   // neighbouring downsampling convs that read the same 48-channel tensor (the first convs of a fuse layer's chains from branch 0,
   // pose_higher_hrnet.py:213-230: 48 -> 96 to branch 1, 48 -> 48 towards branches 2 and 3): one launch of conv48s2.hip reads the
@@ -479,6 +515,20 @@ extern "C" int rtpe_hrnet_plane_major_tensors(const rtpe_hrnet* h, int32_t N, in
   return RTPE_OK;
 }
 
+// the flagged skip projection ops[p] (OpState::proj_head) is computed inside its 1x1 pair in a whole forward of this shape:
+// options "pair_proj" and "pair_1x1" on, and both input views inside the 2-GiB buffer window of the pair kernel (what
+// `direct_ok` in run() asks of the head; its other conditions follow from the flags that made it a pair head)
+static bool pair_proj_runs(const rtpe_hrnet* h, size_t p, int N, int H, int W) {
+  const OpState& op = h->ops[p];
+  if (op.proj_head <= 0 || get_option(kOptPairProj) == 0 || get_option(kOptPair1x1) == 0) return false;
+  for (const rtpe_op_desc* d : {&op.d, &h->ops[op.proj_head].d}) {
+    const rtpe_tensor_desc& ti = h->tensors[d->in_t];
+    const size_t bytes = ((size_t)N * (H >> ti.ds_log2) * (W >> ti.ds_log2) * ti.channels - (size_t)d->in_coff) * 2;
+    if (bytes >= 0x80000000ull) return false;
+  }
+  return true;
+}
+
 // Per-op HIP events.  An op absorbed by the fused launch of its predecessor has none (its time is 0), and a fused
 // block that is followed at once by another one has none either: a marker packet between two kernels costs ~3 us
 // of stream time (3-4 % of this kernel), so a run of consecutive fused blocks is bracketed as a whole and its
@@ -604,6 +654,9 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
   ConvArgs pair_args;
   memset(&pair_args, 0, sizeof(pair_args));
   bool pair_pending = false;                              // the head of a 1x1 pair waits for its tail's launch
+  ConvArgs proj_args;                                     // the folded projection of a pair (option "pair_proj"): computed by the
+  memset(&proj_args, 0, sizeof(proj_args));               // pair kernel, launched at the tail of the pair whose head is proj_for
+  int proj_for = -1;
   bool stem_pending = false;                              // the fused stem kernel ran at the stem op: the next op (conv2) is done
   int s2_skip = 0;                                        // ops behind the first of a stride-2 group that its launch has done
   // argument block of op j as a plain NHWC conv (conv48s2.hip's layers: no residual, no NCHW output)
@@ -865,14 +918,23 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           }
           continue;
         }
+        if (pairs_on && o.proj_head > 0 && pair_proj_runs(h, i, N, H, W)) {   // computed by the pair kernel: nothing to launch
+          proj_args = a;
+          proj_for = o.proj_head;
+          continue;
+        }
         if (pairs_on && o.pair == 1 && direct_ok) {       // launched together with the next op (conv_pair.hip)
           pair_args = a;
           pair_pending = true;
           continue;
         }
+        RTPE_REQUIRE(proj_for != (int)i, "forward: op %zu is no 1x1 pair head at this shape, its projection was folded", i);
         if (pair_pending) {
           pair_pending = false;
-          RTPE_HP_LAUNCH(rc = conv_pair_launch(h->ops[i - 1].plan[0], pair_args, o.plan[0], a, s));
+          const bool proj = proj_for == (int)i - 1;
+          RTPE_HP_LAUNCH(rc = conv_pair_launch(h->ops[i - 1].plan[0], pair_args, o.plan[0], a, s,
+                                               proj ? &h->ops[h->ops[i - 1].proj_op].plan[0] : nullptr, proj ? &proj_args : nullptr));
+          proj_for = -1;
           continue;
         }
         RTPE_HP_LAUNCH(rc = conv_launch(o.plan[k], tile, a, s));
@@ -1161,6 +1223,62 @@ extern "C" int rtpe_basicblock_nhwc(const void* x, int32_t N, int32_t H, int32_t
   return RTPE_OK;
 }
 
+// conv 1x1 64 -> 256 + bn + residual + ReLU and the conv 1x1 256 -> 64 + bn + ReLU behind it as ONE launch of conv_pair.hip on
+// plain NHWC tensors of any pixel count (the /4 maps of a program are multiples of 64 pixels: partial tiles are reached only here).
+// The residual is `res`, or - x and the third layer given - bn(Wd . x), computed inside the kernel (`res` is then not read)
+extern "C" int rtpe_conv1x1_pair_nhwc(const void* t, const void* res, const void* x, int32_t N, int32_t H, int32_t W,
+                                      const void* w1_host, const float* alpha1, const float* beta1, const void* w2_host,
+                                      const float* alpha2, const float* beta2, const void* wd_host, const float* alphad,
+                                      const float* betad, void* y, void* u, void* stream) {
+  RTPE_REQUIRE(t && w1_host && alpha1 && beta1 && w2_host && alpha2 && beta2 && y && u && N > 0 && H > 0 && W > 0,
+               "conv1x1_pair_nhwc: null argument");
+  RTPE_REQUIRE((x != nullptr) == (wd_host != nullptr) && (x == nullptr || (alphad && betad)) && (x != nullptr || res != nullptr),
+               "conv1x1_pair_nhwc: a residual tensor, or the projection's input and layer");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int n_layers = x ? 3 : 2;
+  const int cins[3] = {64, 256, 64}, couts[3] = {256, 64, 256};
+  const void* ws[3] = {w1_host, w2_host, wd_host};
+  const float* al[3] = {alpha1, alpha2, alphad};
+  const float* be[3] = {beta1, beta2, betad};
+  ConvPlan plan[3];
+  size_t off[4] = {0, 0, 0, 0};
+  for (int k = 0; k < n_layers; ++k) {
+    plan[k] = conv_make_plan(ConvGeom{cins[k], couts[k], 1, 1, -1, 2, 1});
+    off[k + 1] = off[k] + align_up(plan[k].packed_bytes, 256) + align_up(2 * sizeof(float) * plan[k].cout_pad, 256);
+  }
+  std::vector<char> host(off[n_layers], 0);
+  for (int k = 0; k < n_layers; ++k) {
+    conv_pack_weights(ConvGeom{cins[k], couts[k], 1, 1, -1, 2, 1}, plan[k], ws[k], host.data() + off[k]);
+    float* ab = reinterpret_cast<float*>(host.data() + off[k] + align_up(plan[k].packed_bytes, 256));
+    for (int c = 0; c < couts[k]; ++c) { ab[c] = al[k][c]; ab[plan[k].cout_pad + c] = be[k][c]; }
+  }
+  char* dev = nullptr;
+  RTPE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dev), host.size()));
+  hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(dev); return hip_fail(e, "hipMemcpy", __FILE__, __LINE__); }
+  ConvArgs a[3];
+  const void* in[3] = {t, y, x};
+  void* out[3] = {y, u, const_cast<void*>(x ? y : res)};     // (the folded projection's output is a name only: never written)
+  for (int k = 0; k < n_layers; ++k) {
+    memset(&a[k], 0, sizeof(a[k]));
+    a[k].x = reinterpret_cast<const _Float16*>(in[k]); a[k].in_ld = cins[k];
+    a[k].x_bytes = (size_t)N * H * W * cins[k] * 2;
+    a[k].w = reinterpret_cast<const _Float16*>(dev + off[k]);
+    a[k].alpha = reinterpret_cast<const float*>(dev + off[k] + align_up(plan[k].packed_bytes, 256)); a[k].beta = a[k].alpha + plan[k].cout_pad;
+    a[k].y = reinterpret_cast<_Float16*>(out[k]); a[k].out_ld = couts[k]; a[k].cout_store = couts[k];
+    a[k].N = N; a[k].H_in = a[k].H_full = a[k].H_pos = H; a[k].W_in = a[k].W_full = a[k].W_pos = W; a[k].o_mul = 1;
+    a[k].relu = k < 2; a[k].round_conv = 1;
+    a[k].cin = cins[k]; a[k].cout = couts[k];
+  }
+  a[0].res = reinterpret_cast<const _Float16*>(x ? y : res); a[0].res_ld = 256;
+  int rc = conv_pair_launch(plan[0], a[0], plan[1], a[1], s, x ? &plan[2] : nullptr, x ? &a[2] : nullptr);
+  hipError_t es = hipStreamSynchronize(s);
+  hipFree(dev);
+  if (rc != RTPE_OK) return rc;
+  if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
+  return RTPE_OK;
+}
+
 extern "C" int rtpe_deconv4x4s2_nhwc(const void* x, int32_t N, int32_t H, int32_t W, int32_t cin,
                                      const void* w_host, const float* alpha_host, const float* beta_host,
                                      int32_t cout, int32_t flags, void* y, void* stream) {
@@ -1303,6 +1421,10 @@ extern "C" int rtpe_hrnet_op_tile(const rtpe_hrnet* h, int32_t op, int32_t N, in
     out8[7] = o.s2g > 1 ? -(200000 + o.s2g) : o.s2g < 0 ? -200009 : -200001;
     return RTPE_OK;
   }
+  if (pair_proj_runs(h, op, N, H, W)) {             // computed inside its 1x1 pair (conv_pair.hip, PROJ): no launch of its own
+    out8[0] = 0; out8[1] = 1; out8[2] = 8; out8[3] = 1; out8[4] = 16; out8[5] = 64; out8[6] = 1; out8[7] = -800003;
+    return RTPE_OK;
+  }
   if (o.pair && get_option(kOptPair1x1) != 0) {     // 1x1 pair (conv_pair.hip): 16-pixel tiles per wave, 8 waves
     out8[0] = o.pair == 1 ? 16 : 4; out8[1] = 1; out8[2] = 8; out8[3] = 1; out8[4] = 16; out8[5] = o.pair == 1 ? 64 : 256; out8[6] = 1;
     out8[7] = o.pair == 1 ? -800001 : -800002;
@@ -1345,6 +1467,7 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
     const OpState& o = h->ops[i];
     const rtpe_op_desc& d = o.d;
     if (o.n_geom == 0) continue;
+    if (pair_proj_runs(h, i, N, H, W)) continue;       // computed inside its 1x1 pair in these forwards: nothing to time, stays untuned
     const rtpe_tensor_desc& ti = h->tensors[d.in_t];
     const Key key = std::make_tuple(d.cin, d.cout, d.ksize, d.stride, (int)d.kind, (int)ti.ds_log2, d.res_t >= 0 ? 1 : 0,
                                     (int)(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED | RTPE_F_NO_NHWC | RTPE_F_F32)),

@@ -45,7 +45,7 @@ inline int env_int(const char* name, int dflt) {
 #endif
 
 // run-time tuning options (rtpe_set_option): every setting gives bit-identical results
-enum { kOptBlockRing = 0, kOptBlockPC = 1, kOptDirect1x1 = 2, kOptLanes = 3, kOptTileDma = 4, kOptPair1x1 = 5, kOptFusedStem = 6, kOptConv64 = 7, kOptHeadDirect = 8, kOptDeconv48 = 9, kOptConv48s2 = 10, kNumOptions = 11 };
+enum { kOptBlockRing = 0, kOptBlockPC = 1, kOptDirect1x1 = 2, kOptLanes = 3, kOptTileDma = 4, kOptPair1x1 = 5, kOptFusedStem = 6, kOptConv64 = 7, kOptHeadDirect = 8, kOptDeconv48 = 9, kOptConv48s2 = 10, kOptPairProj = 11, kNumOptions = 12 };
 int get_option(int key);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: true the first time a kernel's
@@ -227,7 +227,10 @@ int conv_stream_launch(const ConvPlan& p, const ConvTile& t, const ConvArgs& a, 
 // weights in registers; conv_direct_mb = cout tiles per wave, 0 when the layer is not one the kernel takes
 // conv 1x1 64 -> 256 + residual + ReLU and the conv 1x1 256 -> 64 + ReLU that reads its output, as one kernel (conv_pair.hip)
 bool conv_pair_supports(int cin1, int cout1, int cout2);
-int conv_pair_launch(const ConvPlan& p1, const ConvArgs& c1, const ConvPlan& p2, const ConvArgs& c2, hipStream_t s);
+// (pd, cd): the 1x1 conv 64 -> 256 + bn that computes c1's residual from a 64-channel tensor (its y is c1.res): computed inside
+// the kernel, c1.res is not read
+int conv_pair_launch(const ConvPlan& p1, const ConvArgs& c1, const ConvPlan& p2, const ConvArgs& c2, hipStream_t s,
+                     const ConvPlan* pd = nullptr, const ConvArgs* cd = nullptr);
 int conv_direct_mb(const ConvPlan& p);
 // 3x3 stride-1 64 -> 64 convs without residual on persistent workgroups with double-buffered LDS-DMA halo tiles and
 // register-resident weights (conv64.hip, ConvTile::kind == 5: 16 x 16 tiles, 8 waves)

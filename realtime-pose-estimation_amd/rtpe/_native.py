@@ -19,6 +19,7 @@ OP_STEM, OP_CONV, OP_DECONV, OP_FUSE, OP_CAST, OP_AVGPOOL, OP_SE, OP_CAM_COMBINE
 OP_AUX_PACK, OP_RESIZE, OP_GATE_MUL = 9, 10, 11
 F_RELU, F_ROUND_CONV, F_OUT_PREDS, F_OUT_REFINED, F_NO_NHWC, F_F32 = 1, 2, 4, 8, 16, 32
 F_PAIR_HEAD, F_PAIR_TAIL = 64, 128
+F_PAIR_PROJ = 256        # the skip projection that a 1x1 pair may compute itself (include/rtpe_hip.h)
 
 
 class TensorDesc(Structure):
@@ -193,7 +194,13 @@ _SIGS_SHARED = {
 EXPORTS = tuple(_SIGS)                  # the prototypes of include/rtpe_hip.h itself
 EXPORTS_SIZES = tuple(_SIGS_SIZES)      # those of include/rtpe_hip_sizes.h, which it includes
 EXPORTS_WARP = tuple(_SIGS_WARP)        # those of include/rtpe_hip_warp.h, likewise
+_SIGS_PAIR = {
+    "rtpe_conv1x1_pair_nhwc": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
 EXPORTS_SHARED = tuple(_SIGS_SHARED)    # those of include/rtpe_hip_shared.h, likewise
+EXPORTS_PAIR = tuple(_SIGS_PAIR)        # that of include/rtpe_hip_pair.h, likewise
 _lib = None
 
 
@@ -216,7 +223,7 @@ def lib():
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
-                list(_SIGS_SHARED.items()):
+                list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()
