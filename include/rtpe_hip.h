@@ -682,7 +682,8 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
  * rtpe_hip_sizes.h, included below: part of this ABI and of this revision.  So are those of the batched
  * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h, and those of the
  * shared-tag decode (the dual-head students: one tag map per image), declared in rtpe_hip_shared.h, and the layer-level entry
- * of the 1x1 pair kernel, declared in rtpe_hip_pair.h. */
+ * of the 1x1 pair kernel, declared in rtpe_hip_pair.h, and those of the device-resident keypoint records, declared in
+ * rtpe_hip_records.h. */
 
 #ifdef __cplusplus
 }
@@ -691,5 +692,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_warp.h"
 #include "rtpe_hip_shared.h"
 #include "rtpe_hip_pair.h"
+#include "rtpe_hip_records.h"
 
 #endif /* RTPE_HIP_H */

@@ -201,6 +201,13 @@ _SIGS_PAIR = {
 }
 EXPORTS_SHARED = tuple(_SIGS_SHARED)    # those of include/rtpe_hip_shared.h, likewise
 EXPORTS_PAIR = tuple(_SIGS_PAIR)        # that of include/rtpe_hip_pair.h, likewise
+# device-resident keypoint records (include/rtpe_hip_records.h)
+_SIGS_RECORDS = {
+    "rtpe_records_floats": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_pack_records": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                    c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+}
+EXPORTS_RECORDS = tuple(_SIGS_RECORDS)  # those of include/rtpe_hip_records.h, likewise
 _lib = None
 
 
@@ -223,7 +230,7 @@ def lib():
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
-                list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()):
+                list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

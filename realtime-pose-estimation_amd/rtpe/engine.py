@@ -150,7 +150,13 @@ class TeacherPipeline:
 
     ``match_on``: ``"host"`` / ``"device"`` sets the parser's ``match_on`` (where the candidates are grouped into
     people, ``HeatmapParser``); None leaves the parser as it is.  With ``"device"`` the ``lowres_match`` call of
-    ``stream()`` blocks on nothing; the order of the loop and the two-step delay of the results stay."""
+    ``stream()`` blocks on nothing; the order of the loop and the two-step delay of the results stay.
+
+    Device-resident records (``match_on="device"`` only): ``__call__(..., image_ids=...)`` and ``stream(records=...)``
+    return, per batch, the (N, RECORD_FLOATS) float32 tensor that ``pack_records`` would build from the list result -
+    written by a kernel behind adjust + refine (``HeatmapParser.lowres_match``), never read by the host; ``gather``
+    takes it as it is.  ``xform`` (N, 6): per image the float64 matrix of ``transforms.final_preds_matrix``, applied
+    to (x, y) as ``get_final_preds`` does."""
 
     def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
                  max_forward_pixels=MAX_FORWARD_PIXELS, ags=False, match_on=None):
@@ -250,28 +256,41 @@ class TeacherPipeline:
         preds, refined = outs
         return self.parser.lowres_topk(refined, preds[:, NUM_HEATMAPS:], hw)
 
+    def _records(self, images, image_ids, xform):
+        """the ``records`` argument of the parser for one batch, checked before any GPU work; None without ids"""
+        if image_ids is None:
+            if xform is not None:
+                raise ValueError("TeacherPipeline: xform goes with image_ids (the device-resident records)")
+            return None
+        x = images[0] if isinstance(images, (list, tuple)) else images
+        return self.parser.check_records(x.shape[0], (image_ids, xform))
+
     @torch.no_grad()
-    def __call__(self, images, out_hw=None):
+    def __call__(self, images, out_hw=None, image_ids=None, xform=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
         out_hw = decode resolution (original image size), default (H, W) - one ``(h, w)`` for the batch or a sequence
         of N pairs, one per image (``HeatmapParser.parse_lowres``); with ``flip_test`` the projection size.
-        With ``scale_factors``: images = one tensor per scale (descending), out_hw default = the scale-1 (H, W)."""
+        With ``scale_factors``: images = one tensor per scale (descending), out_hw default = the scale-1 (H, W).
+        With ``image_ids`` (N ints; ``match_on="device"``) [and ``xform`` (N, 6) float64]: the (N, RECORD_FLOATS)
+        record tensor on the device instead of the lists (class docstring)."""
         out_hw = self._decode_hw(out_hw, images)
+        records = self._records(images, image_ids, xform)
         if self.scale_factors is not None:
             xs = self._ms_inputs(images)
             st = self._ms_begin(xs, out_hw)
             self._ms_forwards(xs, self.model, lambda i, n0, outs: self.parser.ms_prep(st, i, outs, n0))
             self.parser.ms_topk(st)
-            self.parser.lowres_match(st)
+            self.parser.lowres_match(st, records=records)
             return self.parser.lowres_finish(st)
         preds, refined = self.model(images)
         hw = out_hw if out_hw is not None else tuple(images.shape[2:])
         if self.flip_test:
             preds_f, refined_f = self.model(self.mirror(images))
-            return self.parser.parse_flip(preds, refined, preds_f, refined_f, hw, self.flip_index)
-        return self.parser.parse_lowres(refined, preds[:, NUM_HEATMAPS:], hw)
+            return self.parser.parse_flip(preds, refined, preds_f, refined_f, hw, self.flip_index, records=records)
+        return self.parser.parse_lowres(refined, preds[:, NUM_HEATMAPS:], hw, records=records)
 
-    def stream(self, batches, out_hw=None, on_forward=None, decode_stream=None, in_flight=None, exclusive=None):
+    def stream(self, batches, out_hw=None, on_forward=None, decode_stream=None, in_flight=None, exclusive=None,
+               records=None):
         """Software-pipelined loop over an iterable of (N,3,H,W) GPU batches, in the order
         F(k) R(k-1) T(k)  (forward, adjust+refine of the previous batch, fused top-k).  The host part
         of the decode of batch k-1 (tag matching on the host cores) runs while the GPU executes F(k),
@@ -305,7 +324,14 @@ class TeacherPipeline:
         per scale; ``on_forward`` is called for every sub-batch (and its mirror image), all on the forward stream and
         workspace slot of step k; each sub-batch's maps are prepared on the decode stream as soon as its forwards are
         done (``HeatmapParser.ms_prep``) and T(k) is ``ms_topk``.  Keep the host thread pools small (``torch.set_num_threads``): a burst of idle-
-        spinning OpenMP threads can exhaust a container's CPU quota and stall the launches."""
+        spinning OpenMP threads can exhaust a container's CPU quota and stall the launches.
+
+        ``records``: a callable ``k -> (image_ids, xform | None)`` asked once per batch like ``out_hw`` (after the batch
+        was taken from ``batches``, before its forward); needs ``match_on="device"``.  The generator then yields one
+        (N, RECORD_FLOATS) record tensor per batch (class docstring) with the same two-step delay, safe to use on the
+        stream that was current when the loop started: that stream is made to wait - on the device - for the event
+        behind the record kernel.  The loop body then holds no host wait on decode work: every buffer of such a batch
+        is device memory handed out again in stream order, or a pinned block reused only when its upload is done."""
         import os
         mode = decode_stream or os.environ.get("RTPE_DECODE_STREAM", "side")
         if mode not in ("side", "same"):
@@ -352,6 +378,19 @@ class TeacherPipeline:
 
         ms = self.scale_factors is not None
 
+        def xs_of(x):
+            return x if ms or torch.is_tensor(x) else x[0]           # (a pair: StudentPipeline's (x, alt))
+
+        def match(st):
+            on_decode_stream(P.lowres_match, st, True, True, st.pop("records_arg", None))
+
+        def finish(st):
+            out = P.lowres_finish(st)
+            if records is not None and side is not None:
+                main.wait_event(st["ev2"])          # a wait on the device: the host goes on
+                out.record_stream(main)             # allocated on the decode stream, used on the caller's
+            return out
+
         def run_ms_forwards(k, xs, st):
             """every forward of multi-scale batch k on the current stream, the maps of each sub-batch prepared on the
             decode stream behind an event; returns () (the network outputs are consumed)"""
@@ -370,6 +409,10 @@ class TeacherPipeline:
             with torch.no_grad():
                 for k, x in enumerate(batches):
                     hw_k = self._decode_hw(out_hw(k) if callable(out_hw) else out_hw, x)
+                    rec_k = None
+                    if records is not None:
+                        ids_k, xf_k = records(k)
+                        rec_k = self._records(xs_of(x), ids_k, xf_k)
                     if ms:
                         xs = self._ms_inputs(x)
                         st_ms = on_decode_stream(self._ms_begin, xs, hw_k)
@@ -409,20 +452,21 @@ class TeacherPipeline:
                             for t in outs:
                                 t.record_stream(main)
                     if topk_done is not None:
-                        on_decode_stream(P.lowres_match, topk_done)     # host matching overlaps F(k) on the GPU
+                        match(topk_done)                                # host matching overlaps F(k) on the GPU
                     if ms:
                         st = on_decode_stream(P.ms_topk, st_ms, after=f_done)
                     else:
                         st = on_decode_stream(self._stream_topk, outs, hw, after=f_done, uses=outs)
+                    st["records_arg"] = rec_k
                     if refine_done is not None:
-                        yield P.lowres_finish(refine_done)
+                        yield finish(refine_done)
                     refine_done, topk_done = topk_done, st
                 if topk_done is not None:
-                    on_decode_stream(P.lowres_match, topk_done)
+                    match(topk_done)
                 if refine_done is not None:
-                    yield P.lowres_finish(refine_done)
+                    yield finish(refine_done)
                 if topk_done is not None:
-                    yield P.lowres_finish(topk_done)
+                    yield finish(topk_done)
         finally:
             # also when the consumer stops early or an exception propagates: whoever continues on the main stream
             # sees the decode as done
@@ -436,8 +480,18 @@ class TeacherPipeline:
         """all-gather of the decoded keypoints over the process group (RCCL).  ``equal_counts``:
         every rank contributes the same number of images (no count exchange, no host sync).
         ``force_collective``: issue the collective also in a process group of ONE rank (a world of one is
-        otherwise answered locally; the switch lets a single GPU exercise the RCCL calls)."""
-        rec = pack_records(image_ids, results, self.device)
+        otherwise answered locally; the switch lets a single GPU exercise the RCCL calls).  ``results`` may be the
+        record tensor of ``__call__(..., image_ids=...)`` / ``stream(records=...)`` (``image_ids`` is then None): it is
+        gathered where it lies."""
+        if torch.is_tensor(results):            # device-resident records: they carry their ids, nothing to pack
+            if image_ids is not None:
+                raise ValueError("TeacherPipeline.gather: a record tensor carries its image ids; pass image_ids=None")
+            if results.dim() != 2 or results.shape[1] != RECORD_FLOATS or results.dtype != torch.float32:
+                raise ValueError("TeacherPipeline.gather: a record tensor is (n, %d) float32, not %s %s"
+                                 % (RECORD_FLOATS, tuple(results.shape), results.dtype))
+            rec = results
+        else:
+            rec = pack_records(image_ids, results, self.device)
         if not _collectives_on(force_collective):
             return rec
         return all_gather_records(rec, equal_counts)
@@ -489,13 +543,15 @@ class StudentPipeline(TeacherPipeline):
         return self.parser.lowres_topk_shared(det[:, :J], det[:, J:], hw)
 
     @torch.no_grad()
-    def __call__(self, images, out_hw=None, alt=None):
+    def __call__(self, images, out_hw=None, alt=None, image_ids=None, xform=None):
         """images (N,3,H,W) on the GPU [, alt (N,3,H,W)] -> list of (people, scores) for all N images; out_hw = the
-        decode resolution (h, w), default (H, W)"""
+        decode resolution (h, w), default (H, W); with ``image_ids`` [and ``xform``] the record tensor, as
+        ``TeacherPipeline.__call__``"""
         hw = self._decode_hw(out_hw, images)
+        records = self._records(images, image_ids, xform)
         outs = self._forward(images if alt is None else (images, alt))
         st = self._stream_topk(outs, hw if hw is not None else tuple(images.shape[2:]))
-        self.parser.lowres_match(st)
+        self.parser.lowres_match(st, records=records)
         return self.parser.lowres_finish(st)
 
 

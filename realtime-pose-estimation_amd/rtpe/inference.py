@@ -177,15 +177,47 @@ def _warp_mode(warp):
     return warp == "batch"
 
 
-def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk, batch_scales=None):
+def _record_ids(who, image_ids, n_images, parser, match_on):
+    """``image_ids`` of the batched drivers, checked before any GPU work: None, or one id per image as a list of
+    ints (``group.check_record_ids``, the rule the parser applies to every batch).  The records are written behind the
+    device grouping, so ``match_on`` (or, with None, the parser as it is) must say "device": it is never switched
+    silently."""
+    from .third_party.group import check_record_ids
+    if image_ids is None:
+        return None
+    if (parser.match_on if match_on is None else match_on) != "device":
+        raise ValueError("%s: image_ids asks for the device-resident records, which need match_on='device'" % who)
+    return check_record_ids(image_ids, n_images, who)
+
+
+def _in_input_order(recs, order, n_images, device):
+    """the record tensors of the batches, concatenated and put into input order: ``order[r]`` is the image of row r"""
+    from .engine import RECORD_FLOATS
+    if not recs:
+        return torch.zeros((0, RECORD_FLOATS), dtype=torch.float32, device=device)
+    rec = torch.cat(recs)
+    if order == list(range(n_images)):
+        return rec
+    inv = [0] * n_images
+    for r, i in enumerate(order):
+        inv[i] = r
+    # (a pinned block of the caching host allocator and an asynchronous upload: the host does not wait here either)
+    inv = torch.tensor(inv, dtype=torch.int64).pin_memory() if rec.is_cuda else torch.tensor(inv, dtype=torch.int64)
+    return rec.index_select(0, inv.to(rec.device, non_blocking=True))
+
+
+def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk, batch_scales=None, image_ids=None):
     """the tail of the batched drivers: images of one ``sizes`` entry form a group (``entry[base]`` is its
     projection size ``(w, h)``), a group is cut into chunks of ``batch_size``, ``warp_chunk(warp)`` makes one item of
     ``pipe.stream`` from ``warp(s, lo)`` - the chunk's images warped at scale ``s`` as one tensor - and the keypoints
     are mapped back with the centre / scale the LAST warp of an image left.  Warps as lazily as the pipeline asks.
     ``batch_scales`` (``warp="batch"``): every ``(s, lo)`` that ``warp_chunk`` asks for, in its order; a chunk is then
-    made by ONE ``transforms.warp_normalize_batch`` call for all of them, and ``warp`` only hands its tensors out."""
+    made by ONE ``transforms.warp_normalize_batch`` call for all of them, and ``warp`` only hands its tensors out.
+    ``image_ids``: one id per image; the result is then ONE (len(images), RECORD_FLOATS) record tensor on the device in
+    input order, the mapping back done by the record kernel with each image's ``transforms.final_preds_matrix``."""
     from .third_party import transforms
     out = [None] * len(images)
+    recs, order = [], []
     for key, idx in group_by_input_size(sizes):
         w, h = key[base]
         chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
@@ -208,16 +240,30 @@ def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chun
                     meta[i] = (center, scale)
                 return torch.cat(ts)
             return warp_chunk(warp)
+
+        def records(k):     # asked when chunk k has been warped: the centre / scale its last warp left
+            if any(i not in meta for i in chunks[k]):
+                raise RuntimeError("warp_chunk must warp every image of a chunk before it returns: the record of an "
+                                   "image needs the centre / scale of its last warp")
+            return [image_ids[i] for i in chunks[k]], \
+                [transforms.final_preds_matrix(*meta.pop(i), [w, h]) for i in chunks[k]]
         with torch.no_grad():
+            if image_ids is not None:
+                for c, rec in zip(chunks, pipe.stream((batch(c) for c in chunks), out_hw=(h, w), records=records)):
+                    recs.append(rec)
+                    order += c
+                continue
             for c, res in zip(chunks, pipe.stream((batch(c) for c in chunks), out_hw=(h, w))):
                 for i, (people, scores) in zip(c, res):
                     center, scale = meta.pop(i)
                     out[i] = (transforms.get_final_preds([people], center, scale, [w, h]), scores)
+    if image_ids is not None:
+        return _in_input_order(recs, order, len(images), pipe.device)
     return out
 
 
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
-                        device="cuda", ags=False, match_on=None, warp="image"):
+                        device="cuda", ags=False, match_on=None, warp="image", image_ids=None):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
     flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
     warped to its network input size, images of one size are batched (``batch_size`` at a time) through
@@ -233,22 +279,29 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     people; None leaves the parser as it is).
 
     ``warp``: ``"image"`` warps one image at a time (``transforms.warp_normalize``), ``"batch"`` a whole chunk with
-    one upload and one launch (``transforms.warp_normalize_batch``, needs real uint8 images); same bits."""
+    one upload and one launch (``transforms.warp_normalize_batch``, needs real uint8 images); same bits.
+
+    ``image_ids`` (one int per image; needs ``match_on="device"``, given here or set on the parser): the result is one
+    ``(len(images), engine.RECORD_FLOATS)`` float32 tensor on the device in input order - ``engine.pack_records`` of
+    the list result, ``get_final_preds`` included, written by the record kernel; the host reads no keypoint."""
     from .engine import TeacherPipeline
     from .third_party import transforms
     batched = _warp_mode(warp)
     if ags:
         return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
-                                           device=device, ags=True, warp=warp, **_match_kw(match_on))
+                                           device=device, ags=True, warp=warp, image_ids=image_ids,
+                                           **_match_kw(match_on))
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
     if batch_size < 1:
         raise ValueError("flip_test_inference: batch_size must be positive")
     images = list(images)
+    kw = _match_kw(match_on)
+    image_ids = _record_ids("flip_test_inference", image_ids, len(images), parser, match_on)
     sizes = [(transforms.get_multi_scale_size(img, input_size, 1.0, 1)[0],) for img in images]
-    pipe = TeacherPipeline(model, parser, device=device, flip_test=True, **_match_kw(match_on))
+    pipe = TeacherPipeline(model, parser, device=device, flip_test=True, **kw)
     return _stream_by_size(pipe, images, input_size, sizes, 0, batch_size, lambda warp: warp(1, 1),
-                           [(1, 1)] if batched else None)
+                           [(1, 1)] if batched else None, image_ids)
 
 
 def check_scale_factors(scale_factors):
@@ -283,7 +336,7 @@ def multi_scale_input_sizes(image, input_size, scale_factors):
 
 def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
                                 adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda",
-                                ags=False, match_on=None, warp="image"):
+                                ags=False, match_on=None, warp="image", image_ids=None):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
     project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
     sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
@@ -301,25 +354,30 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).
 
     ``warp``: ``"image"`` warps one image and one scale at a time, ``"batch"`` a whole chunk at every scale with one
-    upload and one launch per scale (``transforms.warp_normalize_batch``, needs real uint8 images); same bits."""
+    upload and one launch per scale (``transforms.warp_normalize_batch``, needs real uint8 images); same bits.
+
+    ``image_ids``: as for ``flip_test_inference`` - one record tensor on the device in input order."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
     batched = _warp_mode(warp)
+    kw = _match_kw(match_on)
     scales = check_scale_factors(scale_factors)
     if not ags and not parser.tag_per_joint:
         raise ValueError("multi_scale_batch_inference: needs a parser with tag_per_joint=True")
     if batch_size < 1:
         raise ValueError("multi_scale_batch_inference: batch_size must be positive")
     images = list(images)
+    image_ids = _record_ids("multi_scale_batch_inference", image_ids, len(images), parser, match_on)
     sizes = [multi_scale_input_sizes(img, input_size, scales) for img in images]
     lo, base = min(scales), scales.index(1)
     if ags:
         parser.tag_per_joint = False                                    # as multi_scale_inference(..., ags=True)
     pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
                            max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels,
-                           ags=ags, **_match_kw(match_on))
+                           ags=ags, **kw)
     # one tensor per scale, largest first: the last warp, whose centre / scale is kept, is the smallest scale's
     return _stream_by_size(pipe, images, input_size, sizes, base, batch_size,
-                           lambda warp: [warp(s, lo) for s in scales], [(s, lo) for s in scales] if batched else None)
+                           lambda warp: [warp(s, lo) for s in scales], [(s, lo) for s in scales] if batched else None,
+                           image_ids)
 
 
 class _Shape:
@@ -351,7 +409,7 @@ def plain_plan(shapes, input_size=640, batch_size=32, max_forward_pixels=None, b
 
 
 def plain_inference(model, parser, images, input_size=640, batch_size=32, max_forward_pixels=None, device="cuda",
-                    match_on=None, warp="image"):
+                    match_on=None, warp="image", image_ids=None):
     """The batched ``validate_hhrnet.py:84-105`` over a list of (h, w, 3) uint8 images: every image is warped to its
     network input size (``warp_normalize(img, input_size, 1, 1)``), images of one INPUT size are batched whatever
     their original sizes - at most ``batch_size`` images and ``max_forward_pixels`` input pixels per forward
@@ -367,17 +425,22 @@ def plain_inference(model, parser, images, input_size=640, batch_size=32, max_fo
     ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).  The batches are planned, and
     an image beyond the pixel budget refused, before any GPU work.  ``warp``: ``"image"`` makes a batch with one
     ``warp_normalize`` call per image and a concatenation, ``"batch"`` with one ``transforms.warp_normalize_batch``
-    call (one upload, one launch; needs real uint8 images); same bits."""
+    call (one upload, one launch; needs real uint8 images); same bits.
+
+    ``image_ids`` (one int per image; needs ``match_on="device"``, given here or set on the parser): the result is one
+    ``(len(images), engine.RECORD_FLOATS)`` float32 tensor on the device in input order, ``engine.pack_records`` of the
+    list result (no transform: the people are in the original image's pixel coordinates already)."""
     from .engine import TeacherPipeline
     from .third_party import transforms
     kw = _match_kw(match_on)
     batched = _warp_mode(warp)
     images = list(images)
+    image_ids = _record_ids("plain_inference", image_ids, len(images), parser, match_on)
     shapes = [tuple(int(v) for v in img.shape[:2]) for img in images]
     chunks = plain_plan(shapes, input_size, batch_size, max_forward_pixels)
     out = [None] * len(images)
     if not chunks:
-        return out
+        return out if image_ids is None else _in_input_order([], [], 0, device)
     pipe = TeacherPipeline(model, parser, device=device, **kw)
 
     def batch(c):
@@ -386,6 +449,10 @@ def plain_inference(model, parser, images, input_size=640, batch_size=32, max_fo
                                                    device=pipe.device)[0][0]
         return torch.cat([transforms.warp_normalize(images[i], input_size, 1, 1, device=pipe.device)[0] for i in c])
     with torch.no_grad():
+        if image_ids is not None:
+            recs = list(pipe.stream((batch(c) for c in chunks), out_hw=lambda k: [shapes[i] for i in chunks[k]],
+                                    records=lambda k: ([image_ids[i] for i in chunks[k]], None)))
+            return _in_input_order(recs, [i for c in chunks for i in c], len(images), pipe.device)
         results = pipe.stream((batch(c) for c in chunks), out_hw=lambda k: [shapes[i] for i in chunks[k]])
         for c, res in zip(chunks, results):
             for i, r in zip(c, res):
