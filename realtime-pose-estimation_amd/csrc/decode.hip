@@ -14,6 +14,7 @@
 //     | ~index) so one unsigned 64-bit max does both.
 #include "rtpe_common.h"
 #include "resize_nc.h"          // align_corners=False bilinear of the flip-test chain (aggregate.hip's arithmetic)
+#include "tag_mean.h"           // launch_mean_plane (tag_mean.hip): the averaged-tag test's shared planes
 
 namespace rtpe {
 
@@ -1575,8 +1576,9 @@ struct FlipPrepArgs {
 };
 
 // FLIP: also the mirror image's maps (A_f, T_f); TAGS: also the tag maps (T_o, T_f); AGS: the j == 0 planes also write
-// the image's shared tag plane rs(P[:, J]) to `to` at plane plane0 / J + n (the expression of T_o[:, 0])
-template <bool FLIP, bool TAGS, bool AGS = false>
+// the image's shared tag plane rs(P[:, J]) to `to` at plane plane0 / J + n (the expression of T_o[:, 0]); TF = false:
+// TAGS without T_f (the averaged-tag test reads the un-mirrored tag maps only)
+template <bool FLIP, bool TAGS, bool AGS = false, bool TF = TAGS>
 __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
   const int plane = blockIdx.y, n = plane / a.J, j = plane - n * a.J, q = a.perm[j];
   const int npix = a.h2 * a.w2;
@@ -1606,7 +1608,7 @@ __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
       axis_nc(a.sx, a.w4, a.w2, xs, &f0, &f1, &lf0, &lf1);
       const float fh = taps_nc(Pf + (size_t)q * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
       a.af[o] = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
-      if (TAGS)
+      if (TF)
         a.tf[o] = taps_nc(Pf + (size_t)(a.J + q) * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
     }
   }
@@ -1621,6 +1623,11 @@ __global__ void __launch_bounds__(256) ms_prep_kernel(const FlipPrepArgs a) { pr
 // AGS multi-scale test, step 1 for the smallest scale: A_o [, A_f] of the scale and the images' shared tag planes
 template <bool FLIP>
 __global__ void __launch_bounds__(256) ags_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, false, true>(a); }
+
+// averaged-tag multi-scale test, step 1 for the smallest scale: A_o [, A_f] and the J un-mirrored tag maps T_o of the
+// scale (tag_mean.hip's mean_plane_kernel reduces them behind this kernel)
+template <bool FLIP>
+__global__ void __launch_bounds__(256) mean_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, true, false, false>(a); }
 
 }  // namespace rtpe
 
@@ -2139,13 +2146,18 @@ extern "C" int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t 
 // AGS (multi_scale_inference(..., ags=True)): the heat maps as above, no T_o / T_f; the tag of every joint of image n
 // is ONE plane, rs_(oh,ow)(rs_(h2,w2)(P_L[n, J])) of the smallest scale L = S-1 (D = 1), stored at the refined size of
 // that scale, (N, h2[S-1], w2[S-1]), at offset `to` (`tf` unused) and projected on the fly.
+// Averaged tag (multi_scale_inference(..., ags="mean"), include/rtpe_hip_tagmean.h): the heat maps as above; at `to`
+// the J un-mirrored tag maps of the smallest scale, (N*J, h2[S-1], w2[S-1]); at `mean` the shared tag planes M at the
+// decode size, (N, oh, ow), which mean_plane_kernel writes and the decode reads through AgsTag as an identity copy.
 // ---------------------------------------------------------------------------
+enum { kTagPerJoint = 0, kTagFirst = 1, kTagMean = 2 };     // the `ags` of the functions below
 struct MsLayout {
   size_t ao[kMaxScales], af[kMaxScales], to, tf, total;   // float offsets into the maps buffer; total floats
+  size_t mean;                                            // kTagMean only: the shared tag planes M
 };
 
-static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, bool ags,
-                     MsLayout* L) {
+static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, int ags,
+                     MsLayout* L, int oh = 0, int ow = 0) {
   RTPE_REQUIRE(h2 && w2, "ms: null size array");
   RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "ms: N=%d J=%d (1 <= J <= %d)", N, J, kMaxJ);
   RTPE_REQUIRE((int64_t)N * J <= 65535, "ms: at most 65535 planes per call");
@@ -2162,6 +2174,14 @@ static int ms_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, 
     L->af[i] = o;
     if (flip) o += n;
   }
+  if (ags == kTagMean) {
+    RTPE_REQUIRE(oh > 0 && ow > 0 && (int64_t)oh * ow < 0x7fffffff, "ms: bad decode size %d x %d", oh, ow);
+    L->to = L->tf = o;                                    // (no T_f: `tf` is never used)
+    o += (size_t)N * J * h2[S - 1] * w2[S - 1];
+    L->mean = o;
+    L->total = o + (size_t)N * oh * ow;
+    return RTPE_OK;
+  }
   const size_t nb = ags ? (size_t)N * h2[S - 1] * w2[S - 1] : (size_t)N * J * h2[base] * w2[base];
   L->to = o;
   o += nb;
@@ -2177,10 +2197,10 @@ struct MsSrc {
   const int32_t *h2, *w2;
   int32_t base, flip, oh, ow;
   size_t maps_bytes;
-  bool ags;
+  int ags;                  // kTagPerJoint / kTagFirst / kTagMean
   MsLayout L;               // filled by check()
   int check(const char* who) {
-    const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
+    const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L, oh, ow);
     if (rc != RTPE_OK) return rc;
     RTPE_REQUIRE(maps && oh > 0 && ow > 0, "%s: bad argument", who);
     RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "%s: maps buffer too small (%zu < %zu bytes)", who, maps_bytes,
@@ -2198,6 +2218,7 @@ struct MsSrc {
       m.af[i] = flip ? maps + L.af[i] : nullptr;
       m.a[i] = nc_axes(h2[i], w2[i], oh, ow);
     }
+    if (ags == kTagMean) return f(m, AgsTag{maps + L.mean, J, nc_axes(oh, ow, oh, ow)}, 1);     // (an identity copy)
     if (ags) return f(m, AgsTag{maps + L.to, J, nc_axes(h2[S - 1], w2[S - 1], oh, ow)}, 1);
     // D = 1 + flip: FlipTag's second map is never read with D = 1
     return f(m, FlipTag{maps + L.to, flip ? maps + L.tf : nullptr, nc_axes(h2[base], w2[base], oh, ow)}, 1 + flip);
@@ -2205,10 +2226,10 @@ struct MsSrc {
 };
 
 static int ms_maps_bytes(const char* who, int N, int J, int S, const int32_t* h2, const int32_t* w2, int base,
-                         int flip, bool ags, size_t* bytes) {
+                         int flip, int ags, size_t* bytes, int oh = 0, int ow = 0) {
   RTPE_REQUIRE(bytes, "%s: null argument", who);
   MsLayout L;
-  const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L, oh, ow);
   if (rc != RTPE_OK) return rc;
   *bytes = L.total * sizeof(float);
   return RTPE_OK;
@@ -2224,15 +2245,21 @@ extern "C" int rtpe_ms_ags_maps_bytes(int32_t N, int32_t J, int32_t S, const int
   return ms_maps_bytes("ms_ags_maps_bytes", N, J, S, h2, w2, base, flip, true, bytes);
 }
 
-// rtpe_ms_prep / rtpe_ms_ags_prep: the same checks and arguments; `ags` picks the layout and the kernels
+extern "C" int rtpe_ms_mean_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                                       int32_t base, int32_t flip, int32_t oh, int32_t ow, size_t* bytes) {
+  return ms_maps_bytes("ms_mean_maps_bytes", N, J, S, h2, w2, base, flip, kTagMean, bytes, oh, ow);
+}
+
+// rtpe_ms_prep / rtpe_ms_ags_prep / rtpe_ms_mean_prep: the same checks and arguments; `ags` picks the layout and the
+// kernels ((oh, ow): the averaged-tag layout only)
 static int ms_prep_impl(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride, const float* refined,
                         int64_t refined_img_stride, const float* preds_f, int64_t preds_f_img_stride,
                         const float* refined_f, int64_t refined_f_img_stride, int32_t n0, int32_t n, int32_t N,
                         int32_t J, const int32_t* flip_index, int32_t S, const int32_t* h2, const int32_t* w2,
                         int32_t base, int32_t flip, int32_t scale, float* maps, size_t maps_bytes, void* stream,
-                        bool ags) {
+                        int ags, int oh = 0, int ow = 0) {
   MsLayout L;
-  int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L);
+  int rc = ms_layout(N, J, S, h2, w2, base, flip, ags, &L, oh, ow);
   if (rc != RTPE_OK) return rc;
   RTPE_REQUIRE(maps, "ms_prep: null argument");
   RTPE_REQUIRE(scale >= 0 && scale < S, "ms_prep: scale %d of %d", scale, S);
@@ -2247,18 +2274,23 @@ static int ms_prep_impl(const float* preds, int32_t h4, int32_t w4, int64_t pred
   a.ao = maps + L.ao[scale];
   a.af = flip ? maps + L.af[scale] : nullptr;
   // AGS: no per-joint tag maps; the smallest scale (the last of the loop) also writes the shared tag planes
-  const bool tags = !ags && scale == base, ags_tag = ags && scale == S - 1;
-  a.to = tags || ags_tag ? maps + L.to : nullptr;
+  // averaged tag: the smallest scale writes its un-mirrored per-joint tag maps, and M goes behind it
+  const bool tags = !ags && scale == base, ags_tag = ags == kTagFirst && scale == S - 1;
+  const bool mean_tag = ags == kTagMean && scale == S - 1;
+  a.to = tags || ags_tag || mean_tag ? maps + L.to : nullptr;
   a.tf = tags && flip ? maps + L.tf : nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid = prep_grid(h2[scale] * w2[scale], n * J);
-  if (ags_tag && flip) hipLaunchKernelGGL((ags_prep_kernel<true>), grid, dim3(256), 0, s, a);
+  if (mean_tag && flip) hipLaunchKernelGGL((mean_prep_kernel<true>), grid, dim3(256), 0, s, a);
+  else if (mean_tag) hipLaunchKernelGGL((mean_prep_kernel<false>), grid, dim3(256), 0, s, a);
+  else if (ags_tag && flip) hipLaunchKernelGGL((ags_prep_kernel<true>), grid, dim3(256), 0, s, a);
   else if (ags_tag) hipLaunchKernelGGL((ags_prep_kernel<false>), grid, dim3(256), 0, s, a);
   else if (flip && tags) hipLaunchKernelGGL((ms_prep_kernel<true, true>), grid, dim3(256), 0, s, a);
   else if (flip) hipLaunchKernelGGL((ms_prep_kernel<true, false>), grid, dim3(256), 0, s, a);
   else if (tags) hipLaunchKernelGGL((ms_prep_kernel<false, true>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((ms_prep_kernel<false, false>), grid, dim3(256), 0, s, a);
   RTPE_HIP_CHECK(hipGetLastError());
+  if (mean_tag) return launch_mean_plane(maps + L.to, J, h2[scale], w2[scale], maps + L.mean, n0, n, oh, ow, s);
   return RTPE_OK;
 }
 
@@ -2343,6 +2375,52 @@ extern "C" int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_ags_n: P_dev is null");
   return decode_adjust_refine("adjust_refine_ms_ags_n",
                               MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev);
+}
+
+// averaged tag (include/rtpe_hip_tagmean.h): the `_ags` entries with the layout that holds T and M
+extern "C" int rtpe_ms_mean_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                                 const float* refined, int64_t refined_img_stride, const float* preds_f,
+                                 int64_t preds_f_img_stride, const float* refined_f, int64_t refined_f_img_stride,
+                                 int32_t n0, int32_t n, int32_t N, int32_t J, const int32_t* flip_index, int32_t S,
+                                 const int32_t* h2, const int32_t* w2, int32_t base, int32_t flip, int32_t scale,
+                                 int32_t oh, int32_t ow, float* maps, size_t maps_bytes, void* stream) {
+  return ms_prep_impl(preds, h4, w4, preds_img_stride, refined, refined_img_stride, preds_f, preds_f_img_stride,
+                      refined_f, refined_f_img_stride, n0, n, N, J, flip_index, S, h2, w2, base, flip, scale, maps,
+                      maps_bytes, stream, kTagMean, oh, ow);
+}
+
+extern "C" int rtpe_topk_ms_mean(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                 const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K,
+                                 int32_t nms_ksize, int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k,
+                                 size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_ms_mean", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean}, K,
+                     nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rtpe_adjust_refine_ms_mean(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                          const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                          size_t maps_bytes, const float* ans_in, float* ans_out,
+                                          const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
+                                          float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                          void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_adjust_refine("adjust_refine_ms_mean",
+                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_ms_mean_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                            const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                            size_t maps_bytes, const float* ans_in, float* ans_out,
+                                            const int32_t* person_img, int32_t P, int32_t do_adjust,
+                                            int32_t do_refine, float* scores, const float* topk_val,
+                                            const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
+                                            void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_mean_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_ms_mean_n",
+                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean},
                               {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
                                scratch, scratch_bytes, stream}, P_dev);
 }

@@ -208,6 +208,20 @@ _SIGS_RECORDS = {
                                     c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
 }
 EXPORTS_RECORDS = tuple(_SIGS_RECORDS)  # those of include/rtpe_hip_records.h, likewise
+# averaged-tag test (include/rtpe_hip_tagmean.h): the channel mean, and the `_ags` entries of the multi-scale decode
+# with the decode size (oh, ow) added where the maps buffer is sized or checked
+_SIGS_TAGMEAN = {
+    "rtpe_channel_mean": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p,
+                                    c_void_p]),
+    "rtpe_ms_mean_maps_bytes": (c_int32, _SIGS["rtpe_ms_ags_maps_bytes"][1][:7] + [c_int32, c_int32,
+                                                                                   POINTER(c_size_t)]),
+    "rtpe_ms_mean_prep": (c_int32, _SIGS["rtpe_ms_ags_prep"][1][:21] + [c_int32, c_int32] +
+                          _SIGS["rtpe_ms_ags_prep"][1][21:]),
+    "rtpe_topk_ms_mean": (c_int32, list(_SIGS["rtpe_topk_ms_ags"][1])),
+    "rtpe_adjust_refine_ms_mean": (c_int32, list(_SIGS["rtpe_adjust_refine_ms_ags"][1])),
+    "rtpe_adjust_refine_ms_mean_n": (c_int32, list(_SIGS["rtpe_adjust_refine_ms_ags_n"][1])),
+}
+EXPORTS_TAGMEAN = tuple(_SIGS_TAGMEAN)  # those of include/rtpe_hip_tagmean.h, likewise
 _lib = None
 
 
@@ -230,7 +244,8 @@ def lib():
         except OSError as e:  # pragma: no cover
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
-                list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()):
+                list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
+                list(_SIGS_TAGMEAN.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

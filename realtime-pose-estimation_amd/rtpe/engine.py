@@ -146,7 +146,8 @@ class TeacherPipeline:
     ``ags=True`` (needs ``scale_factors``; ``(1,)`` for the single-scale protocol): the AGS branch of
     ``multi_scale_inference(..., ags=True)`` - one tag map per image, channel 0 of the un-mirrored tag maps of the
     smallest scale, shared by all joints; any parser is accepted (its ``tag_per_joint`` is not read).  People carry 4
-    columns, with or without flip.
+    columns, with or without flip.  ``ags="mean"``: the averaged-tag test instead - that one tag map is the mean of
+    the joints' tag maps (``HeatmapParser.parse_multi_scale``); ``"first"`` is ``True``, any other string a ValueError.
 
     ``match_on``: ``"host"`` / ``"device"`` sets the parser's ``match_on`` (where the candidates are grouped into
     people, ``HeatmapParser``); None leaves the parser as it is.  With ``"device"`` the ``lowres_match`` call of
@@ -160,7 +161,9 @@ class TeacherPipeline:
 
     def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
                  max_forward_pixels=MAX_FORWARD_PIXELS, ags=False, match_on=None):
-        if ags and scale_factors is None:       # (before any GPU work)
+        from .third_party.group import ags_mode
+        ags = ags_mode(ags, "TeacherPipeline")  # False, True or "mean" (before any GPU work)
+        if ags and scale_factors is None:
             raise ValueError("TeacherPipeline: ags=True needs scale_factors (use (1,) for the single-scale protocol)")
         if match_on not in (None, "host", "device"):
             raise ValueError("TeacherPipeline: match_on must be None, 'host' or 'device', not %r" % (match_on,))
@@ -171,7 +174,7 @@ class TeacherPipeline:
             self.parser.match_on = match_on
         self.flip_test = bool(flip_test)
         self.flip_index = None if flip_index is None else [int(q) for q in flip_index]
-        self.ags = bool(ags)
+        self.ags = ags
         if self.flip_test and not self.parser.tag_per_joint and not self.ags:
             raise ValueError("TeacherPipeline: the flip test needs a parser with tag_per_joint=True")
         self.scale_factors = None

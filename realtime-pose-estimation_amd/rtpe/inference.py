@@ -47,6 +47,15 @@ def resize_combine(src, size, channels=None, flip=False, out=None, accumulate=Fa
     return out
 
 
+def channel_mean(t):
+    """``t.mean(dim=1)`` of a float32 (N,C,h,w) GPU tensor -> (N,h,w), bit-equal to PyTorch-CPU's op in its
+    vectorised order (channels in blocks of 16, one true division) for every pixel: the tag map of the averaged-tag
+    test.  One HIP kernel (csrc/tag_mean.hip); a channel slice is read where it is.  C <= 272: beyond that the CPU op
+    takes an order that is not pinned, and the call is a ValueError."""
+    from .third_party.group import channel_mean as op
+    return op(t)
+
+
 def get_multi_stage_outputs(model, image, with_flip=False, project2image=False, size_projected=None,
                             num_joints=17, with_heatmaps=(True, True), with_heatmaps_loss=(True, True),
                             with_ae=(True, False), with_ae_loss=(True, False), tag_per_joint=True,
@@ -127,8 +136,14 @@ def multi_scale_inference(model, parser, image, input_size=640, scale_factors=(1
     the grouping sees ONE tag map for all joints - channel 0 of the first (un-mirrored) tag map of the LAST scale of
     the loop, a (1,1,h,w,1) tensor - with ``parser.tag_per_joint = False`` (the script sets the attribute on the
     caller's parser and leaves it set; so does this) and ``adjust = refine = True`` whatever the arguments say.
-    ``tags`` in the result is then that tensor."""
+    ``tags`` in the result is then that tensor.
+
+    ``ags="mean"`` (``"first"`` is ``True``; any other string is a ValueError) is the per-image body of
+    legacy/valid_ae_avg.py:189-195 instead: the ONE tag map is ``tags[0].mean(dim=1)`` of the last scale of the loop -
+    ``channel_mean``, PyTorch-CPU's float order - and otherwise everything is as with ``ags=True``."""
     from .third_party import transforms
+    from .third_party.group import ags_mode
+    ags = ags_mode(ags, "multi_scale_inference")                        # (before any GPU work)
     scale_factors = list(scale_factors)
     base_size, center, scale = transforms.get_multi_scale_size(image, input_size, 1.0, min(scale_factors))
     final_heatmaps, tags_list = None, []
@@ -136,7 +151,7 @@ def multi_scale_inference(model, parser, image, input_size=640, scale_factors=(1
         for s in sorted(scale_factors, reverse=True):
             t, center, scale = transforms.warp_normalize(image, input_size, s, min(scale_factors), device=device)
             _, heatmaps, tags = get_multi_stage_outputs(model, t, flip_test, project2image, base_size, **stage_kw)
-            ags_map = tags[0][:, 0].unsqueeze(-1).unsqueeze(0)          # valid_ae1dim.py:177
+            ags_map = tags[0] if ags == "mean" else tags[0][:, 0].unsqueeze(-1).unsqueeze(0)    # valid_ae1dim.py:177
             final_heatmaps, tags_list = aggregate_results(s, final_heatmaps, tags_list, heatmaps, tags, scale_factors,
                                                           flip_test, project2image)
         if len(scale_factors) != 1:
@@ -144,6 +159,8 @@ def multi_scale_inference(model, parser, image, input_size=640, scale_factors=(1
         tags = torch.cat(tags_list, dim=4)
         if ags:
             parser.tag_per_joint = False                                # valid_ae1dim.py:196
+            if ags == "mean":                                           # valid_ae_avg.py:189-195, the last scale's maps
+                ags_map = channel_mean(ags_map).unsqueeze(-1).unsqueeze(0)
             tags = ags_map.contiguous()
             grouped, scores = parser.parse(final_heatmaps, tags, True, True)
         else:
@@ -273,7 +290,8 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     returns (the forward is batch-invariant).
 
     ``ags=True``: the drop-in for ``multi_scale_inference(model, parser, img, input_size, (1,), True, True,
-    ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there).
+    ags=True)`` instead (``multi_scale_batch_inference`` with ``scale_factors=(1,)``, see there); ``ags="mean"``
+    likewise for the averaged-tag test.
 
     ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``: where the candidates are grouped into
     people; None leaves the parser as it is).
@@ -286,10 +304,12 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
     the list result, ``get_final_preds`` included, written by the record kernel; the host reads no keypoint."""
     from .engine import TeacherPipeline
     from .third_party import transforms
+    from .third_party.group import ags_mode
     batched = _warp_mode(warp)
+    ags = ags_mode(ags, "flip_test_inference")
     if ags:
         return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
-                                           device=device, ags=True, warp=warp, image_ids=image_ids,
+                                           device=device, ags=ags, warp=warp, image_ids=image_ids,
                                            **_match_kw(match_on))
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
@@ -349,7 +369,9 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
 
     ``ags=True``: the drop-in for the per-image call with ``ags=True``, its quirks included: the decode adjusts and
     refines whatever ``adjust`` / ``refine`` say (the pipeline always does both), and ``parser.tag_per_joint`` is set to
-    False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``.
+    False and left so (any parser is accepted); the decode is ``TeacherPipeline(..., ags=True)``.  ``ags="mean"``: the
+    same for the averaged-tag test, ``multi_scale_inference(..., ags="mean")`` (``"first"`` is ``True``; any other
+    string is a ValueError before any GPU work).
 
     ``match_on``: passed to ``TeacherPipeline`` (``"host"`` / ``"device"``; None leaves the parser as it is).
 
@@ -358,6 +380,8 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
 
     ``image_ids``: as for ``flip_test_inference`` - one record tensor on the device in input order."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
+    from .third_party.group import ags_mode
+    ags = ags_mode(ags, "multi_scale_batch_inference")
     batched = _warp_mode(warp)
     kw = _match_kw(match_on)
     scales = check_scale_factors(scale_factors)

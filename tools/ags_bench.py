@@ -8,9 +8,12 @@ the single-scale + flip protocol and the multi-scale + flip protocol (default sc
     timed in the order A B B A ... (--repeats runs each), the median reported beside every run;
   * per batch, every step alone: the GPU time of the decode's device phases (prep, top-k, adjust + refine; the host
     matching is not counted) and the bytes of the maps buffer.
+``--mode mean``: the averaged-tag test instead - ags="mean" (the shared tag map is the mean of the joints' tag maps)
+against ags=True in the same process, the same way: both warmed up, A B B A, medians, every run and its range, the
+decode's device phases (the prep of the smallest scale includes the kernel that writes the mean planes) and the bytes.
 Prints one JSON line.  Needs a GPU; there is no fallback.
 
-    python tools/ags_bench.py [--steps 6] [--warmup 2] [--repeats 4] [--decode-reps 5]
+    python tools/ags_bench.py [--mode ags|mean] [--steps 6] [--warmup 2] [--repeats 4] [--decode-reps 5]
 """
 import argparse
 import json
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--decode-reps", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=4, help="timed runs per pipeline, interleaved A B B A ...")
+    ap.add_argument("--mode", choices=("ags", "mean"), default="ags",
+                    help="ags: ags=True against the per-joint tag decode; mean: ags='mean' against ags=True")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ags_bench: no GPU (the AGS test runs on the HIP path only)")
@@ -124,32 +129,43 @@ def main():
         return {"prep": med(prep_ms), "topk": med(topk_ms), "adjust_refine": med(refine_ms),
                 "total": med(np.array(prep_ms) + np.array(topk_ms) + np.array(refine_ms))}, maps_bytes
 
-    out = {"metric": "ags_test_throughput", "batch": B, "size": S, "flip": True, "steps": args.steps, "repeats": args.repeats,
-           "weights": "W0", "device": torch.cuda.get_device_name(dev)}
-    flip = engine.TeacherPipeline(model, device=dev, flip_test=True)
-    xs1 = [b[0] for b in data["single"]]
-    rate(flip, xs1, args.warmup)
-    out["parse_flip_img_s"], people_flip = rate(flip, xs1, max(args.steps, 10))
-    out["parse_flip_img_s"] = round(out["parse_flip_img_s"], 1)
-    people = {"parse_flip": people_flip}
+    # (key, the pipeline's ags): the baseline first
+    variants = (("per_joint_tags", False), ("ags", True)) if args.mode == "ags" else (("ags", True), ("mean", "mean"))
+    (base_key, _), (new_key, _) = variants
+    out = {"metric": "ags_test_throughput" if args.mode == "ags" else "tag_mean_throughput", "batch": B, "size": S,
+           "flip": True, "steps": args.steps, "repeats": args.repeats, "weights": "W0",
+           "device": torch.cuda.get_device_name(dev)}
+    people = {}
+    if args.mode == "ags":
+        flip = engine.TeacherPipeline(model, device=dev, flip_test=True)
+        xs1 = [b[0] for b in data["single"]]
+        rate(flip, xs1, args.warmup)
+        out["parse_flip_img_s"], people["parse_flip"] = rate(flip, xs1, max(args.steps, 10))
+        out["parse_flip_img_s"] = round(out["parse_flip_img_s"], 1)
     for name, sc in protocols.items():
         steps = max(args.steps, 10) if len(sc) == 1 else args.steps
         res = {"scales": list(sc)}
-        pipes = {key: engine.TeacherPipeline(model, device=dev, flip_test=True, scale_factors=sc, ags=key == "ags")
-                 for key in ("per_joint_tags", "ags")}
+        pipes = {key: engine.TeacherPipeline(model, device=dev, flip_test=True, scale_factors=sc, ags=ags)
+                 for key, ags in variants}
         for pipe in pipes.values():
             rate(pipe, data[name], args.warmup)
         runs = {key: [] for key in pipes}
         for r in range(args.repeats):
-            for key in (("per_joint_tags", "ags") if r % 2 == 0 else ("ags", "per_joint_tags")):
+            for key in ((base_key, new_key) if r % 2 == 0 else (new_key, base_key)):
                 v, people[name + "_" + key] = rate(pipes[key], data[name], steps)
                 runs[key].append(round(v, 1))
         for key, pipe in pipes.items():
             times, nbytes = decode_times(pipe, data[name])
             res[key] = {"img_s": round(float(np.median(runs[key])), 1), "img_s_runs": runs[key],
+                        "img_s_range": [min(runs[key]), max(runs[key])],
                         "decode_gpu_ms_per_batch": times, "maps_bytes": nbytes}
-        res["ags_over_per_joint_tags"] = round(res["ags"]["img_s"] / res["per_joint_tags"]["img_s"], 4)
-        res["maps_bytes_saved"] = res["per_joint_tags"]["maps_bytes"] - res["ags"]["maps_bytes"]
+        res["%s_over_%s" % (new_key, base_key)] = round(res[new_key]["img_s"] / res[base_key]["img_s"], 4)
+        if args.mode == "ags":
+            res["maps_bytes_saved"] = res[base_key]["maps_bytes"] - res[new_key]["maps_bytes"]
+        else:       # (the averaged tag keeps the J tag maps of the smallest scale and a plane at the decode size: more)
+            res["maps_bytes_mean_minus_ags"] = res[new_key]["maps_bytes"] - res[base_key]["maps_bytes"]
+        lo, hi = res[base_key]["img_s_range"]
+        res["%s_within_the_range_of_%s" % (new_key, base_key)] = bool(lo <= res[new_key]["img_s"] <= hi)
         out[name] = res
     out["people_last_batch"] = people
     print(json.dumps(out))
