@@ -329,15 +329,26 @@ int rtpe_hrnet_tuned_ints(const rtpe_hrnet* h, int32_t* count);
 int rtpe_hrnet_export_tuned(const rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, int32_t* out, int32_t n);
 int rtpe_hrnet_import_tuned(rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, const int32_t* in, int32_t n);
 
-/* kernel variant of conv op i for (N,H,W): out8 = {cout tiles/wave, pixel
- * tiles/wave, waves, tile_h, tile_w, channel chunk, cout blocks, v} with
- * v > 0: LDS bytes of the one-workgroup-per-tile kernel; v <= -100000:
- * -(workgroups + 100000 * halo buffers) of the streaming kernel; -900001 / -900002: first /
- * second conv of a BasicBlock that runs as ONE fused kernel (conv_block.hip), launched by the
- * first; -(500000 + workgroups): the persistent 64 -> 64 3x3 kernel (conv64.hip); -600001 / -600002: the stem op / the 64 -> 64 stride-2 conv behind it when both run as
- * one kernel (stem_fused.hip, option "fused_stem"), launched at the stem op; -800001 / -800002: head / tail of a 1x1 pair that
- * runs as one kernel (conv_pair.hip), launched at the tail; out8[0] == 0 (v = -800003): an op flagged RTPE_F_PAIR_PROJ that this
- * pair kernel computes itself at this shape - no launch of its own (option "pair_proj") */
+/* kernel variant of conv op i for (N,H,W): the executor's own routing decision (the pass every forward runs, with the
+ * options as they are now and the shape's tuned launch shapes) for a forward that binds a workspace and fp32 `preds` and
+ * `refined` buffers - nominal, 256-byte aligned addresses stand in for them and nothing is dereferenced.  (The one thing a
+ * forward can bind differently: an output buffer that is not 16-byte aligned takes the head off the direct scheme, -400001.)
+ * out8 = {cout tiles/wave, pixel tiles/wave, waves, tile_h, tile_w, channel chunk, cout blocks, v} with
+ * v > 0: LDS bytes of the one-workgroup-per-tile kernel (a transposed conv: the shape of class 0);
+ * v <= -100000: -(workgroups + 100000 * halo buffers) of the streaming kernel (2 or 3 halo buffers), unless v is one of:
+ * -(500000 + workgroups): the persistent 64 -> 64 3x3 kernel (conv64.hip);
+ * -(700000 + cout tiles per wave): the direct 1x1 kernel (conv_direct.hip);
+ * -400001: a head on the direct scheme with an NCHW epilogue (conv_direct.hip, option "head_direct");
+ * -300001: the four classes of a transposed conv on one persistent kernel (deconv48.hip, option "deconv48");
+ * -200001: a 3x3 stride-2 conv from 48 channels on the persistent kernel (conv48s2.hip, option "conv48s2"), a launch of its
+ * own; -20000n (n = 2, 3): the first of n such convs from one input that run as ONE launch; -200009: one of the others;
+ * -900001 / -900002: first / second conv of a BasicBlock that runs as ONE fused kernel (conv_block.hip) at this map size,
+ * launched by the first (a map the kernel does not take: the launch shapes of the two convs);
+ * -600001 / -600002: the stem op / the 64 -> 64 stride-2 conv behind it when both run as one kernel (stem_fused.hip,
+ * option "fused_stem"), launched at the stem op;
+ * -800001 / -800002: head / tail of a 1x1 pair that runs as one kernel (conv_pair.hip), launched at the tail;
+ * out8[0] == 0 (v = -800003): an op flagged RTPE_F_PAIR_PROJ that this pair kernel computes itself at this shape - no launch
+ * of its own (option "pair_proj").  All zero: no conv (the stem op on a kernel of its own included). */
 int rtpe_hrnet_op_tile(const rtpe_hrnet* h, int32_t op, int32_t N, int32_t H, int32_t W, int32_t* out8);
 
 /* ------------------------------------------------------------------------ *

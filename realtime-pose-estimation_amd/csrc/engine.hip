@@ -49,12 +49,39 @@ struct OpState {
 
 using namespace rtpe;
 
+// ---- routing: which launch computes each op of one forward ------------------------------------------------------------
+// route_ops() decides it in one pass over the ops, from the options as they are at that moment; run() launches what the routes
+// say, rtpe_hrnet_op_tile reports them, the per-op times and the autotuner read them.  A new fused launch is one more kind
+// here: its conditions in route_ops(), its launch in run()'s switch, its mark in route_label().
+enum {
+  kRouteNone = 0,                                        // no conv (an elementwise / student op)
+  kRouteTile, kRouteStream, kRouteDirect, kRouteConv64,  // conv_launch on tile[k], one launch per parity class: ConvTile::kind 0 / 2 / 4 / 5
+  kRouteHead,                                            // conv_direct.hip's head kernel (option "head_direct")
+  kRouteS2,                                              // conv48s2.hip, a launch of its own (option "conv48s2")
+  kRouteS2Group,                                         // conv48s2.hip, this op and the by - 1 behind it as one launch
+  kRouteDeconvMerged, kRouteDeconv48,                    // the 4 classes of a transposed conv as one grid on tile[0] / on deconv48.hip
+  kRoutePairHead, kRoutePairTail, kRoutePairProj,        // conv_pair.hip: ONE launch at the tail; by = the tail (head, projection) / the head (tail)
+  kRouteBlock,                                           // conv_block.hip: this conv and the next one
+  kRouteStemFused, kRouteStemConv1, kRouteStemPlain,     // stem_fused.hip with the next op / its conv1 code alone ("fused_stem" = 2) / the VALU kernel
+  kRouteDoneBy                                           // computed by the launch at op `by` (a block's second conv, the stem's conv2, a group's others)
+};
+
+struct Route {
+  int how, by;
+  ConvTile tile[4];     // conv ops: the launch shape of every parity class, after the rules that override a tuned or default one
+};
+
+struct rtpe_record {    // rtpe_hrnet_forward_record: the events of one forward and the routes that say which of them exist
+  std::vector<hipEvent_t> ev;
+  std::vector<Route> routes;
+};
+
 struct rtpe_hrnet {
   int device;
   std::vector<OpState> ops;
   // autotuned launch shapes: (N, H, W) -> one ConvTile per (op, parity class); nt == 0 = not tuned
   std::map<std::tuple<int, int, int>, std::vector<ConvTile>> tuned;
-  std::map<int, std::vector<hipEvent_t>> records;   // per-op events of rtpe_hrnet_forward_record, by slot
+  std::map<int, rtpe_record> records;                // rtpe_hrnet_forward_record, by slot
   std::vector<rtpe_tensor_desc> tensors;
   // tensors that MAY be kept plane-major ([C/48][N][H][W][48] instead of NHWC): C >= 96 and every op that
   // touches them is a 3x3 stride-1 conv the streaming kernel runs (the inner tensors of a BasicBlock chain).
@@ -307,7 +334,7 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
   }
   // neighbouring downsampling convs that read the same 48-channel tensor (the first convs of a fuse layer's chains from branch 0,
   // pose_higher_hrnet.py:213-230: 48 -> 96 to branch 1, 48 -> 48 towards branches 2 and 3): one launch of conv48s2.hip reads the
-  // input once for all of them.  Static conditions here, the launch's own (sizes, layouts, option) in run()
+  // input once for all of them.  Static conditions here, the launch's own (sizes, layouts, option) in route_ops()
   for (OpState& o : h->ops) o.s2g = 0;
   {
     auto s2_static = [&](const OpState& o) {
@@ -445,7 +472,7 @@ extern "C" int rtpe_hrnet_destroy(rtpe_hrnet* h) {
   if (!h) return RTPE_OK;
   DeviceGuard guard(h->device);
   for (auto& kv : h->records)
-    for (auto& e : kv.second) hipEventDestroy(e);
+    for (auto& e : kv.second.ev) hipEventDestroy(e);
   for (auto& e : h->op_event) if (e) hipEventDestroy(e);
   if (h->fork_event) hipEventDestroy(h->fork_event);
   for (int l = 1; l < 4; ++l) if (h->lane_stream[l]) hipStreamDestroy(h->lane_stream[l]);
@@ -475,15 +502,6 @@ extern "C" int rtpe_hrnet_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_
   return RTPE_OK;
 }
 
-// a fused BasicBlock pair (OpState::fuse) runs as one kernel at this map size (conv_block.hip: 48 channels, from 6 x 16 maps up).
-// (A fused kernel for the 96-channel branch was built and measured in round 5 - slower than the two streaming launches:
-// profiles/r05_block96_ablation.txt, tools/experiments/conv_block96.hip.)
-static bool fused_block_runs(const rtpe_hrnet* h, const rtpe_op_desc& d, int N, int H, int W) {
-  const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-  (void)N;
-  return conv_block_supports(d.cin, d.cout, H >> ti.ds_log2, W >> ti.ds_log2);
-}
-
 // plane-major tensors of one run: the candidates all of whose ops run on the streaming kernel with the launch
 // shapes in force (tiny maps fall back to the generic kernel, which only knows NHWC)
 static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W, const std::vector<ConvTile>* tuned) {
@@ -504,55 +522,310 @@ static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W,
   return plane;
 }
 
+// the kernel-selecting options, read once per forward
+struct RouteOpts {
+  int fused_stem = get_option(kOptFusedStem), pair_1x1 = get_option(kOptPair1x1), pair_proj = get_option(kOptPairProj),
+      conv64 = get_option(kOptConv64), head_direct = get_option(kOptHeadDirect), deconv48 = get_option(kOptDeconv48),
+      conv48s2 = get_option(kOptConv48s2);
+};
+
+// what a forward binds: shape, buffers, tuned launch shapes, plane-major tensors.  (rtpe_hrnet_op_tile binds nominal buffers:
+// the routes depend on their being there and on their alignment only, nothing is dereferenced before a launch)
+struct Fwd {
+  const rtpe_hrnet* h;
+  int N, H, W;
+  char* base;
+  void *preds, *refined;
+  int out_dtype;
+  std::vector<size_t> offs;
+  size_t ws_need;
+  const std::vector<ConvTile>* tuned = nullptr;
+  std::vector<char> plane;
+  Fwd(const rtpe_hrnet* h_, int N_, int H_, int W_, void* ws, void* preds_, void* refined_, int out_dtype_)
+      : h(h_), N(N_), H(H_), W(W_), base(reinterpret_cast<char*>(ws)), preds(preds_), refined(refined_), out_dtype(out_dtype_) {
+    slot_layout(h, N, H, W, &offs, &ws_need);
+    auto it = h->tuned.find(std::make_tuple(N, H, W));
+    if (it != h->tuned.end()) tuned = &it->second;
+    plane = plane_tensors(h, N, H, W, tuned);
+  }
+  size_t esz(int t) const { return h->tensors[t].reserved == 4 ? 4 : 2; }
+  _Float16* tptr(int t, int coff) const {      // element type per tensor (fp16 or fp32): byte arithmetic
+    return reinterpret_cast<_Float16*>(base + offs[h->tensors[t].slot] + (size_t)coff * esz(t));
+  }
+  ConvTile tile(size_t i, int k, int H_pos, int W_pos) const {   // tuned, else the default
+    return tuned && (*tuned)[i * 4 + k].nt ? (*tuned)[i * 4 + k] : conv_make_tile(h->ops[i].plan[k], N, H_pos, W_pos);
+  }
+};
+
 extern "C" int rtpe_hrnet_plane_major_tensors(const rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, int32_t* count) {
   RTPE_REQUIRE(h != nullptr && count != nullptr, "plane_major_tensors: null argument");
-  const std::vector<ConvTile>* tuned = nullptr;
-  auto it = h->tuned.find(std::make_tuple((int)N, (int)H, (int)W));
-  if (it != h->tuned.end()) tuned = &it->second;
-  int n = 0;
-  for (char c : plane_tensors(h, N, H, W, tuned)) n += c;
-  *count = n;
+  const Fwd f(h, N, H, W, nullptr, nullptr, nullptr, RTPE_DTYPE_F32);
+  *count = 0;
+  for (char c : f.plane) *count += c;
   return RTPE_OK;
 }
 
-// the flagged skip projection ops[p] (OpState::proj_head) is computed inside its 1x1 pair in a whole forward of this shape:
-// options "pair_proj" and "pair_1x1" on, and both input views inside the 2-GiB buffer window of the pair kernel (what
-// `direct_ok` in run() asks of the head; its other conditions follow from the flags that made it a pair head)
-static bool pair_proj_runs(const rtpe_hrnet* h, size_t p, int N, int H, int W) {
-  const OpState& op = h->ops[p];
-  if (op.proj_head <= 0 || get_option(kOptPairProj) == 0 || get_option(kOptPair1x1) == 0) return false;
-  for (const rtpe_op_desc* d : {&op.d, &h->ops[op.proj_head].d}) {
-    const rtpe_tensor_desc& ti = h->tensors[d->in_t];
-    const size_t bytes = ((size_t)N * (H >> ti.ds_log2) * (W >> ti.ds_log2) * ti.channels - (size_t)d->in_coff) * 2;
-    if (bytes >= 0x80000000ull) return false;
+// argument block of parity class k of conv op i: pointers, sizes and flags (the launch shape's half is conv_fill_args')
+static ConvArgs conv_op_args(const Fwd& f, size_t i, int k) {
+  const rtpe_hrnet* h = f.h;
+  const OpState& o = h->ops[i];
+  const rtpe_op_desc& d = o.d;
+  const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+  const int N = f.N, Hi = f.H >> ti.ds_log2, Wi = f.W >> ti.ds_log2;
+  const bool dc = d.kind == RTPE_OP_DECONV;
+  const int Ho = dc ? Hi * 2 : Hi / d.stride, Wo = dc ? Wi * 2 : Wi / d.stride;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = f.tptr(d.in_t, d.in_coff);
+  a.in_ld = ti.channels;
+  if (f.plane[d.in_t]) { a.in_ld = 48; a.in_cs = (long long)N * Hi * Wi * 48; }
+  a.x_bytes = ((size_t)N * Hi * Wi * ti.channels - (size_t)d.in_coff) * f.esz(d.in_t);
+  a.w = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[k]);
+  a.alpha = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
+  a.beta = a.alpha + o.plan[0].cout_pad;
+  if (d.res_t >= 0) {
+    a.res = f.tptr(d.res_t, d.res_coff);
+    a.res_ld = h->tensors[d.res_t].channels;
+    if (f.plane[d.res_t]) { a.res_ld = 48; a.res_cs = (long long)N * Ho * Wo * 48; }
   }
-  return true;
+  if (!(d.flags & RTPE_F_NO_NHWC)) {
+    a.y = f.tptr(d.out_t, d.out_coff);
+    a.out_ld = h->tensors[d.out_t].channels;
+    if (f.plane[d.out_t]) { a.out_ld = 48; a.out_cs = (long long)N * Ho * Wo * 48; }
+    // zero-padded channels up to the allocated row are written too (they
+    // are exact zeros: zero weights, zero affine) so that a consumer that
+    // reads the padded view sees finite data
+    int cs = o.plan[0].cout_pad;
+    const int room = h->tensors[d.out_t].channels - d.out_coff;
+    a.cout_store = cs < room ? cs : room;
+    if (d.reserved[2] > 0 && d.reserved[2] < a.cout_store) a.cout_store = d.reserved[2];
+  }
+  if (d.flags & RTPE_F_OUT_PREDS) { a.y_nchw = f.preds; a.nchw_channels = d.cout; }
+  if (d.flags & RTPE_F_OUT_REFINED) { a.y_nchw = f.refined; a.nchw_channels = d.cout; }
+  a.nchw_f32 = f.out_dtype == RTPE_DTYPE_F32;
+  a.N = N; a.H_in = Hi; a.W_in = Wi;
+  a.H_full = Ho; a.W_full = Wo;
+  if (dc) {
+    a.H_pos = Hi; a.W_pos = Wi; a.o_mul = 2; a.oy_add = k >> 1; a.ox_add = k & 1;
+  } else {
+    a.H_pos = Ho; a.W_pos = Wo; a.o_mul = 1;
+  }
+  a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
+  a.round_conv = (d.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
+  return a;
+}
+
+static ConvArgs conv_op_args(const Fwd& f, size_t i, int k, const ConvTile& t) {
+  ConvArgs a = conv_op_args(f, i, k);
+  conv_fill_args(f.h->ops[i].geom[k], f.h->ops[i].plan[k], t, &a);
+  return a;
+}
+
+// the direct 1x1 kernel, the 1x1 pair and the persistent kernels address their input through one 2-GiB buffer window and write
+// plain NHWC rows: a larger view (batch >= 164 at 640 x 640 for the 256 -> 64 conv) or another output form takes the
+// one-workgroup-per-tile kernel, whose staging falls back per image
+static bool conv_direct_ok(const ConvArgs& a) {
+  return a.x_bytes < 0x80000000ull && a.y != nullptr && a.y_nchw == nullptr && a.o_mul == 1;
+}
+
+// The per-conv decision (the executor's ops and the single-layer entries).  First the rules that override a launch shape:
+// kind 4 needs direct_ok; kind 5 (conv64.hip) also takes no residual and no plane-major tensor (plane_io: the input or the
+// NHWC output is one) - also when a tuned or imported shape says kind 5 but option "conv64" has been switched off since
+static void conv_fix_tile(const RouteOpts& opt, const ConvPlan& p, const ConvArgs& a, bool plane_io, ConvTile* t) {
+  const bool direct_ok = conv_direct_ok(a);
+  if (t->kind == 4 && !direct_ok) *t = conv_make_tile(p, a.N, a.H_pos, a.W_pos, /*allow_direct=*/false);
+  if (t->kind == 5 && !(direct_ok && a.res == nullptr && !plane_io && opt.conv64 != 0))
+    *t = conv_make_tile(p, a.N, a.H_pos, a.W_pos, true, /*allow_conv64=*/false);
+}
+
+// ... then the kernel, for arguments filled on that shape: the heads (1x1, 48 input channels, fp32 NCHW out) and the
+// downsampling convs from 48 input channels have kernels of their own, whatever launch shape was chosen or tuned for the layer
+static int conv_pick(const RouteOpts& opt, const ConvPlan& p, const ConvTile& t, const ConvArgs& a, bool plane_io) {
+  if (opt.head_direct != 0 && conv_head_supports(p, a)) return kRouteHead;
+  if (opt.conv48s2 != 0 && !plane_io && conv48s2_supports(p, a)) return kRouteS2;
+  return t.kind == 2 ? kRouteStream : t.kind == 4 ? kRouteDirect : t.kind == 5 ? kRouteConv64 : kRouteTile;
+}
+
+// the 4 sub-pixel classes of a transposed conv run as ONE grid (conv_mfma.hip) on class 0's launch shape when that shape is a
+// one-workgroup-per-tile one and the plans of all classes agree (they differ in the tap offsets and the packed weights only;
+// RTPE_DECONV_MERGE=0: four launches)
+static bool deconv_merges(const ConvPlan* p, const ConvTile& tile0) {
+  static const int merge_deconv = env_int("RTPE_DECONV_MERGE", 1);
+  bool merge = merge_deconv && tile0.kind == 0;
+  for (int k = 1; k < 4 && merge; ++k)
+    merge = p[k].mt == p[0].mt && p[k].cc == p[0].cc && p[k].kc == p[0].kc && p[k].n_cchunks == p[0].n_cchunks &&
+            p[k].n_cb == p[0].n_cb && p[k].pstride == p[0].pstride && p[k].tapw == p[0].tapw;
+  return merge;
+}
+
+// class k's weights and offsets go into the argument block of class 0
+static void deconv_merge_class(ConvArgs* merged, const ConvArgs& a, int k) {
+  if (k == 0) { *merged = a; merged->n_cls = 4; }
+  merged->w_c[k] = a.w;
+  merged->lo_yc[k] = a.lo_y; merged->lo_xc[k] = a.lo_x;
+  merged->oy_c[k] = a.oy_add; merged->ox_c[k] = a.ox_add;
+}
+
+static ConvArgs deconv_merged_args(const Fwd& f, size_t i, const ConvTile& tile0) {
+  ConvArgs merged;
+  for (int k = 0; k < 4; ++k) deconv_merge_class(&merged, conv_op_args(f, i, k, tile0), k);
+  return merged;
+}
+
+// the four classes on one persistent kernel that shares their halo tiles (deconv48.hip, option "deconv48")
+static int deconv_pick(const RouteOpts& opt, const ConvPlan& p0, const ConvArgs& merged) {
+  return opt.deconv48 != 0 && deconv48_supports(p0, merged) ? kRouteDeconv48 : kRouteDeconvMerged;
+}
+
+static int launch_conv(int how, const ConvPlan& p, const ConvTile& t, const ConvArgs& a, hipStream_t s) {
+  switch (how) {
+    case kRouteHead: return conv_head_launch(p, a, s);
+    case kRouteS2: return conv48s2_launch(p, a, s);
+    case kRouteDeconv48: return deconv48_launch(p, a, s);
+    default: return conv_launch(p, t, a, s);
+  }
+}
+
+// args[i]: the argument block the pass built for conv op i (class 0 on its launch shape; a merged transposed conv: all four
+// classes) - what the launch that computes op i hands to the kernel.  Both outputs are indexed by op; a stride-2 group hands
+// args[i .. i + n) to its launch as one array
+static int route_ops(const Fwd& f, std::vector<Route>* routes, std::vector<ConvArgs>* args) {
+  const rtpe_hrnet* h = f.h;
+  const RouteOpts opt;
+  routes->assign(h->ops.size(), Route());
+  args->assign(h->ops.size(), ConvArgs());
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    Route& r = (*routes)[i];
+    const OpState& o = h->ops[i];
+    const rtpe_op_desc& d = o.d;
+    auto absorb = [&](size_t j) { (*routes)[j].how = kRouteDoneBy; (*routes)[j].by = (int)i; };
+    if (r.how == kRouteDoneBy) continue;
+    if (d.kind == RTPE_OP_STEM) {
+      const int fused = stem_fused_supports(f.H, f.W) ? opt.fused_stem : 0;
+      r.how = fused == 1 && o.stem2 == 1 ? kRouteStemFused : fused == 2 && !(d.flags & RTPE_F_F32) ? kRouteStemConv1 : kRouteStemPlain;
+      if (r.how == kRouteStemFused) absorb(i + 1);
+      continue;
+    }
+    if (o.n_geom == 0) continue;
+    if (d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))
+      RTPE_REQUIRE(((d.flags & RTPE_F_OUT_REFINED) ? f.refined : f.preds) != nullptr, "forward: output pointer missing");
+    const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+    const int Hi = f.H >> ti.ds_log2, Wi = f.W >> ti.ds_log2;
+    const bool dc = d.kind == RTPE_OP_DECONV;
+    // a flagged BasicBlock pair runs as one kernel from 6 x 16 maps up; a smaller map runs both convs on their own.  (A fused
+    // kernel for the 96-channel branch was built and measured in round 5 - slower than the two streaming launches:
+    // profiles/r05_block96_ablation.txt, tools/experiments/conv_block96.hip.)
+    if (o.fuse == 1 && conv_block_supports(d.cin, d.cout, Hi, Wi)) {
+      r.how = kRouteBlock;
+      absorb(i + 1);
+      continue;
+    }
+    for (int k = 0; k < o.n_geom; ++k) r.tile[k] = f.tile(i, k, dc ? Hi : Hi / d.stride, dc ? Wi : Wi / d.stride);
+    if (dc && deconv_merges(o.plan, r.tile[0])) {
+      (*args)[i] = deconv_merged_args(f, i, r.tile[0]);
+      r.how = deconv_pick(opt, o.plan[0], (*args)[i]);
+      continue;
+    }
+    // the first downsampling convs of a fuse layer's chains from one branch (OpState::s2g): one launch, the input read once
+    if (o.s2g > 1 && opt.conv48s2 != 0) {
+      bool ok = true;
+      for (int m = 0; m < o.s2g && ok; ++m) {
+        const OpState& om = h->ops[i + m];
+        Route& rm = (*routes)[i + m];
+        if (m > 0) rm.tile[0] = f.tile(i + m, 0, Hi / 2, Wi / 2);
+        (*args)[i + m] = conv_op_args(f, i + m, 0, rm.tile[0]);
+        ok = !f.plane[om.d.in_t] && !f.plane[om.d.out_t] && conv48s2_supports(om.plan[0], (*args)[i + m]);
+      }
+      if (ok) {
+        r.how = kRouteS2Group;
+        r.by = o.s2g;
+        for (int m = 1; m < o.s2g; ++m) absorb(i + m);
+        continue;
+      }
+    }
+    const bool plane_io = f.plane[d.in_t] || (!(d.flags & RTPE_F_NO_NHWC) && f.plane[d.out_t]);
+    ConvArgs& a = (*args)[i];
+    a = conv_op_args(f, i, 0);
+    for (int k = 0; k < o.n_geom; ++k) conv_fix_tile(opt, o.plan[k], k ? conv_op_args(f, i, k) : a, plane_io, &r.tile[k]);
+    conv_fill_args(o.geom[0], o.plan[0], r.tile[0], &a);
+    if (r.how == kRoutePairTail) continue;               // marked at its head
+    r.how = conv_pick(opt, o.plan[0], r.tile[0], a, plane_io);       // (the classes of an unmerged transposed conv: o_mul = 2, neither a head nor a stride-2 conv)
+    if (r.how == kRouteHead || r.how == kRouteS2 || opt.pair_1x1 == 0 || !conv_direct_ok(a)) continue;
+    // a 1x1 pair is launched at its tail.  Its flagged skip projection (OpState::proj_head) is computed there too, option
+    // "pair_proj", when both input views lie inside the window (the head's other conditions follow from the flags that made it one)
+    if (o.proj_head > 0 && opt.pair_proj != 0 && conv_direct_ok(conv_op_args(f, o.proj_head, 0))) {
+      r.how = kRoutePairProj;
+      r.by = o.proj_head + 1;
+    } else if (o.pair == 1) {
+      r.how = kRoutePairHead;
+      r.by = (int)i + 1;
+      (*routes)[i + 1].how = kRoutePairTail;
+      (*routes)[i + 1].by = (int)i;
+    }
+  }
+  for (size_t i = 0; i < h->ops.size(); ++i)              // a folded projection is computed nowhere else
+    RTPE_REQUIRE((*routes)[i].how != kRoutePairProj || (*routes)[h->ops[i].proj_head].how == kRoutePairHead,
+                 "forward: op %d is no 1x1 pair head at this shape, its projection was folded", h->ops[i].proj_head);
+  return RTPE_OK;
+}
+
+// rtpe_hrnet_op_tile's out8 for a route
+static void route_label(const rtpe_hrnet* h, const std::vector<Route>& routes, size_t i, int32_t* out8) {
+  const Route& r = routes[i];
+  const OpState& o = h->ops[i];
+  const ConvTile& t = r.tile[0];
+  const int by = r.how == kRouteDoneBy ? routes[r.by].how : kRouteNone;
+  auto set = [&](int mt, int nt, int waves, int th, int tw, int cc, int n_cb, int v) {
+    const int32_t l[8] = {mt, nt, waves, th, tw, cc, n_cb, v};
+    memcpy(out8, l, sizeof(l));
+  };
+  memset(out8, 0, 8 * sizeof(int32_t));
+  if (r.how == kRouteStemFused || by == kRouteStemFused) {            // stem_fused.hip: 8 x 16 tiles, 8 waves
+    set(4, 4, 8, 8, 16, 64, 1, by ? -600002 : -600001);
+  } else if (r.how == kRouteBlock || by == kRouteBlock) {             // conv_block.hip: 6x32 tiles, 5 + 3 pixel tiles per wave
+    set(3, by ? 3 : 5, 4, 6, 32, 48, 1, by ? -900002 : -900001);
+  } else if (r.how == kRouteS2 || r.how == kRouteS2Group || by == kRouteS2Group) {
+    // conv48s2.hip: 8 x 8 output tiles, a wave = one group of 48 output channels.  -200001: a launch of its own; -20000n
+    // (n = 2, 3): first of n convs from one input in ONE launch; -200009: one of the others
+    const int gw = o.d.cout == 48 ? 1 : o.d.cout == 96 ? 2 : 4;
+    set(3, 2, 4, 8, 8, 48, o.d.cout / (48 * gw), by ? -200009 : r.how == kRouteS2Group ? -(200000 + r.by) : -200001);
+  } else if (r.how == kRouteHead) {                                   // conv_direct.hip's head kernel: 32 pixels per wave step
+    set(o.plan[0].mt, 2, 4, 1, 32, 48, 1, -400001);
+  } else if (r.how == kRouteDeconv48) {                               // deconv48.hip: 8 x 16 input positions per tile, wave k = class k
+    set(3, 2, 4, 8, 16, 48, 1, -300001);
+  } else if (r.how == kRoutePairProj) {                               // conv_pair.hip: 16-pixel tiles per wave, 8 waves; no launch of its own
+    set(0, 1, 8, 1, 16, 64, 1, -800003);
+  } else if (r.how == kRoutePairHead || r.how == kRoutePairTail) {
+    const bool head = r.how == kRoutePairHead;
+    set(head ? 16 : 4, 1, 8, 1, 16, head ? 64 : 256, 1, head ? -800001 : -800002);
+  } else if (o.n_geom > 0) {                                          // conv_launch on the launch shape (of class 0)
+    set(t.kind == 0 && t.mrun ? t.mrun : o.plan[0].mt, t.nt, t.waves, t.th, t.tw, o.plan[0].cc, o.plan[0].n_cb,
+        t.kind == 2 ? -(t.grid + 100000 * t.n_bufs) : t.kind == 4 ? -(700000 + t.grid) : t.kind == 5 ? -(500000 + t.grid) : (int32_t)t.lds_bytes);
+  }
 }
 
 // Per-op HIP events.  An op absorbed by the fused launch of its predecessor has none (its time is 0), and a fused
 // block that is followed at once by another one has none either: a marker packet between two kernels costs ~3 us
 // of stream time (3-4 % of this kernel), so a run of consecutive fused blocks is bracketed as a whole and its
 // blocks share the interval equally - the per-launch time then agrees with the kernel trace.
-static bool op_has_event(const rtpe_hrnet* h, size_t i, bool fused_mode) {
-  if (!fused_mode) return true;
-  const std::vector<OpState>& ops = h->ops;
-  if (ops[i].fuse == 2) return false;
-  return !(ops[i].fuse == 1 && i + 2 < ops.size() && ops[i + 2].fuse == 1);
+static bool block_head(const std::vector<Route>& r, size_t i) { return i < r.size() && r[i].how == kRouteBlock; }
+static bool block_tail(const std::vector<Route>& r, size_t i) { return i > 0 && block_head(r, i - 1); }
+
+static bool op_has_event(const std::vector<Route>& r, size_t i) {
+  return !block_tail(r, i) && !(block_head(r, i) && block_head(r, i + 2));
 }
 
-template <class Events>
-static int read_op_times(const rtpe_hrnet* h, const Events& ev, bool fused_mode, float* op_ms) {
-  const std::vector<OpState>& ops = h->ops;
-  for (size_t i = 0; i < ops.size(); ++i) {
-    if (fused_mode && ops[i].fuse == 2) { op_ms[i] = 0.f; continue; }
+static int read_op_times(const std::vector<Route>& r, const std::vector<hipEvent_t>& ev, float* op_ms) {
+  for (size_t i = 0; i < r.size(); ++i) {
+    if (block_tail(r, i)) { op_ms[i] = 0.f; continue; }
     size_t first = i, last = i;
-    if (fused_mode && ops[i].fuse == 1) {
-      while (first >= 2 && ops[first - 2].fuse == 1) first -= 2;
-      while (last + 2 < ops.size() && ops[last + 2].fuse == 1) last += 2;
+    if (block_head(r, i)) {
+      while (first >= 2 && block_head(r, first - 2)) first -= 2;
+      while (block_head(r, last + 2)) last += 2;
     }
     // the interval starts at the event of the op before `first` (a run never starts behind an absorbed op; any
     // other op that follows an absorbed one starts at the event of that block's head)
-    const size_t b0 = (fused_mode && first > 0 && ops[first - 1].fuse == 2) ? first - 1 : first;
+    const size_t b0 = first > 0 && block_tail(r, first - 1) ? first - 1 : first;
     float ms;
     RTPE_HIP_CHECK(hipEventElapsedTime(&ms, ev[b0], ev[last + 1]));
     op_ms[i] = ms / (float)((last - first) / 2 + 1);
@@ -562,8 +835,7 @@ static int read_op_times(const rtpe_hrnet* h, const Events& ev, bool fused_mode,
 
 static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, void* preds, void* refined,
                int out_dtype, void* ws, size_t ws_bytes, hipStream_t s_main, float* op_ms, int n_ms,
-               int only_op = -1, int only_k = -1, const ConvTile* force = nullptr,
-               std::vector<hipEvent_t>* rec = nullptr, const void* aux = nullptr, uint32_t fwd_flags = 0) {
+               rtpe_record* rec = nullptr, const void* aux = nullptr, uint32_t fwd_flags = 0) {
   RTPE_REQUIRE(h && x && ws, "forward: null argument");
   static const int host_prof = env_int("RTPE_HOST_PROF", 0);       // host time of a forward: where it goes (stderr)
   typedef std::chrono::steady_clock hclock;
@@ -586,27 +858,27 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
   RTPE_REQUIRE(N > 0 && H % 32 == 0 && W % 32 == 0 && H >= 32 && W >= 32, "forward: N=%d H=%d W=%d", N, H, W);
   RTPE_REQUIRE(x_dtype == RTPE_DTYPE_F16 || x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
   RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F16 || out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
-  std::vector<size_t> offs;
-  size_t need;
-  slot_layout(h, N, H, W, &offs, &need);
-  if (need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, need); return RTPE_E_NOMEM; }
+  const Fwd f(h, N, H, W, ws, preds, refined, out_dtype);
+  if (f.ws_need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, f.ws_need); return RTPE_E_NOMEM; }
   RTPE_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
   // Shapes an op cannot take are refused here, before the first launch, so that no half-run forward is left behind.
   // avgpool: the kernel writes ceil(Hi / 2) x ceil(Wi / 2) pixels, the output tensor holds (H >> ds) x (W >> ds): a map
   // with an odd side (1 x 1, 2 x 1) would be written beyond its tensor
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const rtpe_op_desc& d = h->ops[i].d;
-    if (d.kind != RTPE_OP_AVGPOOL || (only_op >= 0 && (int)i != only_op)) continue;
+    if (d.kind != RTPE_OP_AVGPOOL) continue;
     const int Hi = H >> h->tensors[d.in_t].ds_log2, Wi = W >> h->tensors[d.in_t].ds_log2;
     const int Ho = H >> h->tensors[d.out_t].ds_log2, Wo = W >> h->tensors[d.out_t].ds_log2;
     RTPE_REQUIRE((Hi + 1) / 2 == Ho && (Wi + 1) / 2 == Wo,
                  "avgpool: a %d x %d map does not pool into the %d x %d output tensor", Hi, Wi, Ho, Wo);
   }
-  char* base = reinterpret_cast<char*>(ws);
-  auto esz = [&](int t) -> size_t { return h->tensors[t].reserved == 4 ? 4 : 2; };
-  auto tptr = [&](int t, int coff) -> _Float16* {      // element type per tensor (fp16 or fp32): byte arithmetic
-    return reinterpret_cast<_Float16*>(base + offs[h->tensors[t].slot] + (size_t)coff * esz(t));
-  };
+  std::vector<Route> routes;
+  std::vector<ConvArgs> args;
+  {
+    const int rc = route_ops(f, &routes, &args);
+    if (rc != RTPE_OK) return rc;
+  }
+  auto tptr = [&](int t, int coff) { return f.tptr(t, coff); };
   std::vector<hipEvent_t> ev;
   const bool timed = op_ms != nullptr;
   if (timed) {
@@ -616,26 +888,20 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
     RTPE_HIP_CHECK(hipEventRecord(ev[0], s_main));
   }
   if (rec) {                         // non-blocking recording into caller-kept events
-    if (rec->size() != h->ops.size() + 1) {
-      for (auto& e : *rec) hipEventDestroy(e);
-      rec->resize(h->ops.size() + 1);
-      for (auto& e : *rec) RTPE_HIP_CHECK(hipEventCreate(&e));
+    if (rec->ev.size() != h->ops.size() + 1) {
+      for (auto& e : rec->ev) hipEventDestroy(e);
+      rec->ev.resize(h->ops.size() + 1);
+      for (auto& e : rec->ev) RTPE_HIP_CHECK(hipEventCreate(&e));
     }
-    RTPE_HIP_CHECK(hipEventRecord((*rec)[0], s_main));
+    rec->routes = routes;
+    RTPE_HIP_CHECK(hipEventRecord(rec->ev[0], s_main));
   }
-  const std::vector<ConvTile>* tuned = nullptr;
-  {
-    auto it = h->tuned.find(std::make_tuple(N, H, W));
-    if (it != h->tuned.end()) tuned = &it->second;
-  }
-  std::vector<char> plane(h->tensors.size(), 0);
-  if (only_op < 0 && force == nullptr) plane = plane_tensors(h, N, H, W, tuned);
   // Parallel regions (the branches of a HighResolutionModule, pose_higher_hrnet.py:242-243, and the conversion convs of
   // its fuse layers are independent): with lanes on, the ops of lane k > 0 go to an internal stream that forks from the
   // caller's stream at the region's first op and joins it behind its last; an op waits for the events of the ops of
-  // other lanes whose output it reads.  Timed / recorded / single-op runs stay on one stream (one op after another).
+  // other lanes whose output it reads.  Timed / recorded runs stay on one stream (one op after another).
   bool lanes_on = false;
-  if (h->has_regions && !timed && rec == nullptr && only_op < 0 && force == nullptr && !(fwd_flags & RTPE_FWD_NO_LANES)) {
+  if (h->has_regions && !timed && rec == nullptr && !(fwd_flags & RTPE_FWD_NO_LANES)) {
     const int opt = get_option(kOptLanes);
     lanes_on = opt == 1 || (opt == 2 && (long long)N * H * W <= 4ll * 640 * 640);
   }
@@ -649,44 +915,6 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
     for (size_t l = 0; l < 4; ++l) RTPE_HIP_CHECK(hipEventCreateWithFlags(&h->op_event[h->ops.size() + l], hipEventDisableTiming));
     RTPE_HIP_CHECK(hipEventCreateWithFlags(&h->fork_event, hipEventDisableTiming));
   }
-  // 1x1 pairs run as one kernel in whole forwards only (timed / recorded ones included: the pair's time is the tail's)
-  const bool pairs_on = get_option(kOptPair1x1) != 0 && only_op < 0 && force == nullptr;
-  ConvArgs pair_args;
-  memset(&pair_args, 0, sizeof(pair_args));
-  bool pair_pending = false;                              // the head of a 1x1 pair waits for its tail's launch
-  ConvArgs proj_args;                                     // the folded projection of a pair (option "pair_proj"): computed by the
-  memset(&proj_args, 0, sizeof(proj_args));               // pair kernel, launched at the tail of the pair whose head is proj_for
-  int proj_for = -1;
-  bool stem_pending = false;                              // the fused stem kernel ran at the stem op: the next op (conv2) is done
-  int s2_skip = 0;                                        // ops behind the first of a stride-2 group that its launch has done
-  // argument block of op j as a plain NHWC conv (conv48s2.hip's layers: no residual, no NCHW output)
-  auto s2_layer_args = [&](size_t j, ConvArgs* a) {
-    const OpState& oj = h->ops[j];
-    const rtpe_op_desc& dj = oj.d;
-    const rtpe_tensor_desc& tj = h->tensors[dj.in_t];
-    const int Hj = H >> tj.ds_log2, Wj = W >> tj.ds_log2;
-    memset(a, 0, sizeof(*a));
-    a->x = tptr(dj.in_t, dj.in_coff);
-    a->in_ld = tj.channels;
-    a->x_bytes = ((size_t)N * Hj * Wj * tj.channels - (size_t)dj.in_coff) * esz(dj.in_t);
-    a->w = reinterpret_cast<const _Float16*>(h->arena + oj.w_dev_off[0]);
-    a->alpha = reinterpret_cast<const float*>(h->arena + oj.ab_dev_off);
-    a->beta = a->alpha + oj.plan[0].cout_pad;
-    a->y = tptr(dj.out_t, dj.out_coff);
-    a->out_ld = h->tensors[dj.out_t].channels;
-    const int room = h->tensors[dj.out_t].channels - dj.out_coff;
-    a->cout_store = oj.plan[0].cout_pad < room ? oj.plan[0].cout_pad : room;
-    a->N = N; a->H_in = Hj; a->W_in = Wj;
-    a->H_full = a->H_pos = Hj / dj.stride; a->W_full = a->W_pos = Wj / dj.stride;
-    a->o_mul = 1;
-    a->relu = (dj.flags & RTPE_F_RELU) ? 1 : 0;
-    a->round_conv = (dj.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
-    a->cin = dj.cin; a->cout = dj.cout;
-    a->lo_y = oj.plan[0].lo_y; a->lo_x = oj.plan[0].lo_x;
-    a->in_cs = oj.plan[0].cc; a->out_cs = oj.plan[0].mt * 16; a->res_cs = oj.plan[0].mt * 16;
-  };
-  ConvArgs s2_args[3];
-  const ConvPlan* s2_plans[3];
   int cur_region = 0;
   bool lane_used[4] = {false, false, false, false};
   auto join_lanes = [&]() -> hipError_t {
@@ -701,9 +929,9 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
     return hipSuccess;
   };
   for (size_t i = 0; i < h->ops.size(); ++i) {
-    if (only_op >= 0 && (int)i != only_op) continue;
     const OpState& o = h->ops[i];
     const rtpe_op_desc& d = o.d;
+    const Route& r = routes[i];
     int rc = RTPE_OK;
     hipStream_t s = s_main;
     if (lanes_on) {
@@ -717,307 +945,172 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
       }
       if (cur_region > 0) {
         if (d.lane > 0) { s = h->lane_stream[d.lane]; lane_used[d.lane] = true; }
-        for (int j : h->wait_ops[i]) RTPE_HIP_CHECK(hipStreamWaitEvent(s, h->op_event[j], 0));
-        if ((o.fuse == 1 || o.stem2 == 1) && i + 1 < h->ops.size())   // the block's second conv (the stem's conv2) is launched with this one
-          for (int j : h->wait_ops[i + 1]) RTPE_HIP_CHECK(hipStreamWaitEvent(s, h->op_event[j], 0));
-        for (int m = 1; m < o.s2g; ++m)                               // the other convs of a stride-2 group are launched with this one
-          for (int j : h->wait_ops[i + m]) RTPE_HIP_CHECK(hipStreamWaitEvent(s, h->op_event[j], 0));
+        // the op's own waits and those of the ops behind it that this launch computes (a block's second conv, the stem's
+        // conv2, the other convs of a stride-2 group)
+        for (size_t j = i; j == i || (j < routes.size() && routes[j].how == kRouteDoneBy && routes[j].by == (int)i); ++j)
+          for (int w : h->wait_ops[j]) RTPE_HIP_CHECK(hipStreamWaitEvent(s, h->op_event[w], 0));
       }
     }
-    const bool stem_fused_on = force == nullptr && only_op < 0 && get_option(kOptFusedStem) == 1 && stem_fused_supports(H, W);
-    if (d.kind == RTPE_OP_STEM && o.stem2 == 1 && stem_fused_on) {
-      // conv1 + bn1 + relu + conv2 + bn2 + relu in one kernel: the half-resolution map stays in LDS (stem_fused.hip)
-      const OpState& o2 = h->ops[i + 1];
-      const rtpe_op_desc& d2 = o2.d;
-      StemFusedArgs a;
-      memset(&a, 0, sizeof(a));
-      a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
-      a.w1 = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
-      a.alpha1 = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-      a.beta1 = a.alpha1 + 64;
-      a.w2 = reinterpret_cast<const _Float16*>(h->arena + o2.w_dev_off[0]);
-      a.alpha2 = reinterpret_cast<const float*>(h->arena + o2.ab_dev_off);
-      a.beta2 = a.alpha2 + o2.plan[0].cout_pad;
-      a.y = tptr(d2.out_t, d2.out_coff);
-      a.N = N; a.H = H; a.W = W; a.out_ld = h->tensors[d2.out_t].channels;
-      a.relu = (d2.flags & RTPE_F_RELU) ? 1 : 0;
-      a.round_conv = (d2.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
-      RTPE_HP_LAUNCH(rc = stem_fused_launch(a, s));
-      stem_pending = true;      // latched here: the option is process-wide and may change between this op and the next
-    } else if (d.kind == RTPE_OP_CONV && o.stem2 == 2 && stem_pending) {
-      stem_pending = false;     // done by the launch at the stem op
-    } else if (d.kind == RTPE_OP_STEM && !(d.flags & RTPE_F_F32) && get_option(kOptFusedStem) == 2 && stem_fused_supports(H, W)) {
-      // option "fused_stem" = 2: the stem op alone on the fused kernel's conv1 code (the chain on the matrix pipe),
-      // output to memory - the bit-identity test of that chain against the VALU kernel
-      StemFusedArgs a;
-      memset(&a, 0, sizeof(a));
-      a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
-      a.w1 = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
-      a.alpha1 = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-      a.beta1 = a.alpha1 + 64;
-      a.y1 = tptr(d.out_t, d.out_coff);
-      a.N = N; a.H = H; a.W = W; a.out_ld = h->tensors[d.out_t].channels;
-      RTPE_HP_LAUNCH(rc = stem_fused_launch(a, s));
-    } else if (d.kind == RTPE_OP_STEM) {
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      StemArgs a;
-      a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
-      a.w = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
-      a.alpha = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-      a.beta = a.alpha + 64;
-      a.y = tptr(d.out_t, d.out_coff);
-      a.N = N; a.H = H; a.W = W; a.out_ld = to.channels;
-      a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
-      RTPE_HP_LAUNCH(rc = stem_launch(a, s));
-    } else if (d.kind == RTPE_OP_CONV && o.fuse == 2 && force == nullptr && only_op < 0 && fused_block_runs(h, d, N, H, W)) {
-      // second conv of a fused BasicBlock: done by the launch of its head (same test as there: a map too
-      // small for the fused kernel runs both convs on their own)
-    } else if (d.kind == RTPE_OP_CONV && o.fuse == 1 && force == nullptr && only_op < 0 && fused_block_runs(h, d, N, H, W)) {
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-      const OpState& o2 = h->ops[i + 1];
-      const rtpe_tensor_desc& to = h->tensors[o2.d.out_t];
-      {
+    switch (r.how) {
+      case kRouteDoneBy: case kRoutePairHead: case kRoutePairProj:      // computed by the launch at op r.by
+        break;
+      case kRouteStemFused: case kRouteStemConv1: {
+        // conv1 + bn1 + relu + conv2 + bn2 + relu in one kernel: the half-resolution map stays in LDS (stem_fused.hip); or,
+        // option "fused_stem" = 2, the stem op alone on that kernel's conv1 code (the chain on the matrix pipe), output to
+        // memory - the bit-identity test of that chain against the VALU kernel
+        StemFusedArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
+        a.w1 = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
+        a.alpha1 = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
+        a.beta1 = a.alpha1 + 64;
+        a.N = N; a.H = H; a.W = W;
+        if (r.how == kRouteStemFused) {
+          const OpState& o2 = h->ops[i + 1];
+          const rtpe_op_desc& d2 = o2.d;
+          a.w2 = reinterpret_cast<const _Float16*>(h->arena + o2.w_dev_off[0]);
+          a.alpha2 = reinterpret_cast<const float*>(h->arena + o2.ab_dev_off);
+          a.beta2 = a.alpha2 + o2.plan[0].cout_pad;
+          a.y = tptr(d2.out_t, d2.out_coff);
+          a.out_ld = h->tensors[d2.out_t].channels;
+          a.relu = (d2.flags & RTPE_F_RELU) ? 1 : 0;
+          a.round_conv = (d2.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
+        } else {
+          a.y1 = tptr(d.out_t, d.out_coff);
+          a.out_ld = h->tensors[d.out_t].channels;
+        }
+        RTPE_HP_LAUNCH(rc = stem_fused_launch(a, s));
+        break;
+      }
+      case kRouteStemPlain: {
+        StemArgs a;
+        a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
+        a.w = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
+        a.alpha = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
+        a.beta = a.alpha + 64;
+        a.y = tptr(d.out_t, d.out_coff);
+        a.N = N; a.H = H; a.W = W; a.out_ld = h->tensors[d.out_t].channels;
+        a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
+        RTPE_HP_LAUNCH(rc = stem_launch(a, s));
+        break;
+      }
+      case kRouteBlock: {
+        const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+        const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
+        const OpState& o2 = h->ops[i + 1];
         RTPE_HP_LAUNCH(rc = conv_block_launch(tptr(d.in_t, d.in_coff), ti.channels,
                                ((size_t)N * Hi * Wi * ti.channels - (size_t)d.in_coff) * 2,
-                               tptr(o2.d.out_t, o2.d.out_coff), to.channels,
+                               tptr(o2.d.out_t, o2.d.out_coff), h->tensors[o2.d.out_t].channels,
                                reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]),
                                reinterpret_cast<const float*>(h->arena + o.ab_dev_off),
                                reinterpret_cast<const _Float16*>(h->arena + o2.w_dev_off[0]),
                                reinterpret_cast<const float*>(h->arena + o2.ab_dev_off), N, Hi, Wi, s));
+        break;
       }
-    } else if (d.kind == RTPE_OP_CONV && o.s2g < 0 && s2_skip > 0) {
-      --s2_skip;                // done by the launch at the group's first op
-    } else if (d.kind == RTPE_OP_CONV && o.s2g > 1 && force == nullptr && only_op < 0 && get_option(kOptConv48s2) != 0 && [&]() {
-                 for (int m = 0; m < o.s2g; ++m) {
-                   const OpState& om = h->ops[i + m];
-                   if (plane[om.d.in_t] || plane[om.d.out_t]) return false;
-                   s2_layer_args(i + m, &s2_args[m]);
-                   s2_plans[m] = &om.plan[0];
-                   if (!conv48s2_supports(om.plan[0], s2_args[m])) return false;
-                 }
-                 return true;
-               }()) {
-      // the first downsampling convs of a fuse layer's chains from one branch: one launch, the input read once
-      RTPE_HP_LAUNCH(rc = conv48s2_launch_group(s2_plans, s2_args, o.s2g, s));
-      s2_skip = o.s2g - 1;
-    } else if (d.kind == RTPE_OP_CONV || d.kind == RTPE_OP_DECONV) {
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-      const bool dc = d.kind == RTPE_OP_DECONV;
-      const int Ho = dc ? Hi * 2 : Hi / d.stride, Wo = dc ? Wi * 2 : Wi / d.stride;
-      ConvArgs merged;
-      ConvTile merged_tile;
-      memset(&merged, 0, sizeof(merged));
-      memset(&merged_tile, 0, sizeof(merged_tile));
-      static const int merge_deconv = env_int("RTPE_DECONV_MERGE", 1);
-      // the 4 sub-pixel classes of a transposed conv run as ONE grid (conv_mfma.hip) on class 0's launch shape
-      // when that shape is a one-workgroup-per-tile one and the plans of all classes agree (they differ in the
-      // tap offsets and the packed weights only): decided once, before any class is set up
-      ConvTile tile0;
-      memset(&tile0, 0, sizeof(tile0));
-      bool merge = false;
-      if (dc && only_k < 0 && merge_deconv) {
-        if (force) tile0 = *force;
-        else if (tuned && (*tuned)[i * 4].nt) tile0 = (*tuned)[i * 4];
-        else tile0 = conv_make_tile(o.plan[0], N, Hi, Wi);
-        merge = tile0.kind == 0;
-        for (int k = 1; k < o.n_geom && merge; ++k) {
-          const ConvPlan &p0 = o.plan[0], &pk = o.plan[k];
-          merge = pk.mt == p0.mt && pk.cc == p0.cc && pk.kc == p0.kc && pk.n_cchunks == p0.n_cchunks &&
-                  pk.n_cb == p0.n_cb && pk.pstride == p0.pstride && pk.tapw == p0.tapw;
-        }
+      case kRouteS2Group: {
+        const ConvPlan* plans[3];
+        for (int m = 0; m < r.by; ++m) plans[m] = &h->ops[i + m].plan[0];
+        RTPE_HP_LAUNCH(rc = conv48s2_launch_group(plans, &args[i], r.by, s));
+        break;
       }
-      for (int k = 0; k < o.n_geom && rc == RTPE_OK; ++k) {
-        if (only_k >= 0 && k != only_k) continue;
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = tptr(d.in_t, d.in_coff);
-        a.in_ld = ti.channels;
-        if (plane[d.in_t]) { a.in_ld = 48; a.in_cs = (long long)N * Hi * Wi * 48; }
-        a.x_bytes = ((size_t)N * Hi * Wi * ti.channels - (size_t)d.in_coff) * esz(d.in_t);
-        a.w = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[k]);
-        a.alpha = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-        a.beta = a.alpha + o.plan[0].cout_pad;
-        if (d.res_t >= 0) {
-          a.res = tptr(d.res_t, d.res_coff);
-          a.res_ld = h->tensors[d.res_t].channels;
-          if (plane[d.res_t]) { a.res_ld = 48; a.res_cs = (long long)N * Ho * Wo * 48; }
-        }
-        if (!(d.flags & RTPE_F_NO_NHWC)) {
-          a.y = tptr(d.out_t, d.out_coff);
-          a.out_ld = h->tensors[d.out_t].channels;
-          if (plane[d.out_t]) { a.out_ld = 48; a.out_cs = (long long)N * Ho * Wo * 48; }
-          // zero-padded channels up to the allocated row are written too (they
-          // are exact zeros: zero weights, zero affine) so that a consumer that
-          // reads the padded view sees finite data
-          int cs = o.plan[0].cout_pad;
-          const int room = h->tensors[d.out_t].channels - d.out_coff;
-          a.cout_store = cs < room ? cs : room;
-          if (d.reserved[2] > 0 && d.reserved[2] < a.cout_store) a.cout_store = d.reserved[2];
-        }
-        if (d.flags & RTPE_F_OUT_PREDS) { a.y_nchw = preds; a.nchw_channels = d.cout; }
-        if (d.flags & RTPE_F_OUT_REFINED) { a.y_nchw = refined; a.nchw_channels = d.cout; }
-        a.nchw_f32 = out_dtype == RTPE_DTYPE_F32;
-        if (a.y_nchw == nullptr && (d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))) {
-          set_error("forward: output pointer missing"); return RTPE_E_INVALID;
-        }
-        a.N = N; a.H_in = Hi; a.W_in = Wi;
-        a.H_full = Ho; a.W_full = Wo;
-        if (dc) {
-          a.H_pos = Hi; a.W_pos = Wi; a.o_mul = 2; a.oy_add = k >> 1; a.ox_add = k & 1;
-        } else {
-          a.H_pos = Ho; a.W_pos = Wo; a.o_mul = 1;
-        }
-        a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
-        a.round_conv = (d.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
-        ConvTile tile;
-        if (merge)
-          tile = tile0;
-        else if (force)
-          tile = *force;
-        else if (tuned && (*tuned)[i * 4 + k].nt)
-          tile = (*tuned)[i * 4 + k];
-        else
-          tile = conv_make_tile(o.plan[k], N, a.H_pos, a.W_pos);
-        // the direct 1x1 kernel and the 1x1 pair address their input through one 2-GiB buffer window and write plain
-        // NHWC rows: a larger view (batch >= 164 at 640 x 640 for the 256 -> 64 conv) or another output form takes the
-        // one-workgroup-per-tile kernel, whose staging falls back per image
-        const bool direct_ok = a.x_bytes < 0x80000000ull && a.y != nullptr && a.y_nchw == nullptr && a.o_mul == 1;
-        if (tile.kind == 4 && !direct_ok) tile = conv_make_tile(o.plan[k], N, a.H_pos, a.W_pos, /*allow_direct=*/false);
-        // the persistent 64 -> 64 kernel (conv64.hip) takes no residual and writes plain NHWC rows through one buffer window
-        // (also when a tuned or imported shape says kind 5 but option "conv64" has been switched off since)
-        if (tile.kind == 5 && !(direct_ok && a.res == nullptr && !plane[d.in_t] && !plane[d.out_t] && get_option(kOptConv64) != 0))
-          tile = conv_make_tile(o.plan[k], N, a.H_pos, a.W_pos, true, /*allow_conv64=*/false);
-        conv_fill_args(o.geom[k], o.plan[k], tile, &a);
-        // the heads (1x1, 48 input channels, fp32 NCHW out): the direct scheme with an NCHW epilogue (conv_direct.hip),
-        // whatever launch shape was chosen or tuned for the layer (option "head_direct")
-        if (!merge && force == nullptr && get_option(kOptHeadDirect) != 0 && conv_head_supports(o.plan[k], a)) {
-          RTPE_HP_LAUNCH(rc = conv_head_launch(o.plan[k], a, s));
-          continue;
-        }
-        // the downsampling convs of the fuse layers from 48 input channels: persistent workgroups with register-resident weights
-        // (conv48s2.hip, option "conv48s2"), whatever launch shape was chosen or tuned for the layer
-        if (!merge && force == nullptr && get_option(kOptConv48s2) != 0 && !plane[d.in_t] && !(a.y != nullptr && plane[d.out_t]) &&
-            conv48s2_supports(o.plan[k], a)) {
-          RTPE_HP_LAUNCH(rc = conv48s2_launch(o.plan[k], a, s));
-          continue;
-        }
-        if (merge) {
-          // class k's weights and offsets go into the argument block of class 0; the launch follows the last class
-          if (k == 0) { merged = a; merged_tile = tile; merged.n_cls = 4; }
-          merged.w_c[k] = a.w;
-          merged.lo_yc[k] = a.lo_y; merged.lo_xc[k] = a.lo_x;
-          merged.oy_c[k] = a.oy_add; merged.ox_c[k] = a.ox_add;
-          if (k == o.n_geom - 1) {
-            // the four classes on one persistent kernel that shares their halo tiles (deconv48.hip, option "deconv48")
-            if (force == nullptr && get_option(kOptDeconv48) != 0 && deconv48_supports(o.plan[0], merged))
-              RTPE_HP_LAUNCH(rc = deconv48_launch(o.plan[0], merged, s));
-            else
-              RTPE_HP_LAUNCH(rc = conv_launch(o.plan[0], merged_tile, merged, s));
+      case kRoutePairTail: {   // with the head and, where it is folded, the head's skip projection
+        const OpState& oh = h->ops[r.by];
+        const bool proj = oh.proj_op >= 0 && routes[oh.proj_op].how == kRoutePairProj;
+        RTPE_HP_LAUNCH(rc = conv_pair_launch(oh.plan[0], args[r.by], o.plan[0], args[i], s, proj ? &h->ops[oh.proj_op].plan[0] : nullptr,
+                                             proj ? &args[oh.proj_op] : nullptr));
+        break;
+      }
+      case kRouteDeconvMerged: case kRouteDeconv48:
+        RTPE_HP_LAUNCH(rc = launch_conv(r.how, o.plan[0], r.tile[0], args[i], s));
+        break;
+      case kRouteTile: case kRouteStream: case kRouteDirect: case kRouteConv64: case kRouteHead: case kRouteS2:
+        // a conv on the kernel of its launch shape (a launch per class) or on the head / stride-2 kernel
+        for (int k = 0; k < o.n_geom && rc == RTPE_OK; ++k)
+          RTPE_HP_LAUNCH(rc = launch_conv(r.how, o.plan[k], r.tile[k], k ? conv_op_args(f, i, k, r.tile[k]) : args[i], s));
+        break;
+      default: {   // kRouteNone: the elementwise and student ops
+        if (d.kind == RTPE_OP_AUX_PACK) {
+          if (aux == nullptr) { set_error("forward: this program has a second input (use rtpe_hrnet_forward_aux)"); return RTPE_E_INVALID; }
+          const rtpe_tensor_desc& to = h->tensors[d.out_t];
+          rc = aux_pack_launch(reinterpret_cast<const float*>(aux), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)),
+                               to.channels, N, H >> to.ds_log2, W >> to.ds_log2, s);
+        } else if (d.kind == RTPE_OP_RESIZE) {
+          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+          const rtpe_tensor_desc& to = h->tensors[d.out_t];
+          rc = resize_nhwc_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, H >> ti.ds_log2,
+                                  W >> ti.ds_log2, reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels,
+                                  H >> to.ds_log2, W >> to.ds_log2, d.cout, N, s);
+        } else if (d.kind == RTPE_OP_GATE_MUL) {
+          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+          const rtpe_tensor_desc& to = h->tensors[d.out_t];
+          const size_t pixels = (size_t)N * (H >> ti.ds_log2) * (W >> ti.ds_log2);
+          float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
+          if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
+            set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
           }
-          continue;
+          float div;
+          memcpy(&div, &d.reserved[0], sizeof(float));
+          rc = gate_mul_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
+                               reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
+                               reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels, d.cout, pixels, div, att_out, s);
+        } else if (d.kind == RTPE_OP_CAST || d.kind == RTPE_OP_AVGPOOL || d.kind == RTPE_OP_SE ||
+                   d.kind == RTPE_OP_CAM_COMBINE || d.kind == RTPE_OP_SIGMOID_ADD) {
+          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+          const rtpe_tensor_desc& to = h->tensors[d.out_t];
+          const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
+          const size_t pixels = (size_t)N * Hi * Wi;
+          float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
+          if (d.kind == RTPE_OP_CAST) {
+            rc = cast_launch(tptr(d.in_t, d.in_coff), ti.channels, yo, to.channels, d.cout, pixels, s);
+          } else if (d.kind == RTPE_OP_AVGPOOL) {
+            rc = avgpool_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, yo, to.channels,
+                                d.cout, N, Hi, Wi, s);
+          } else if (d.kind == RTPE_OP_SE) {
+            rc = se_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, d.cin, d.cout, N, Hi * Wi,
+                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), yo, to.channels, s);
+          } else if (d.kind == RTPE_OP_CAM_COMBINE) {
+            rc = cam_combine_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
+                                    reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
+                                    reinterpret_cast<const float*>(tptr(d.term_t[0], 0)), h->tensors[d.term_t[0]].channels,
+                                    yo, to.channels, d.cout, N, (size_t)Hi * Wi, s);
+          } else {
+            float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
+            if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
+              set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
+            }
+            rc = sigmoid_add_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
+                                    reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
+                                    yo, to.channels, d.cout, pixels, att_out, s);
+          }
+        } else {  // FUSE
+          const rtpe_tensor_desc& to = h->tensors[d.out_t];
+          FuseArgs a;
+          memset(&a, 0, sizeof(a));
+          a.n_terms = d.n_terms;
+          for (int t = 0; t < d.n_terms; ++t) {
+            a.term[t] = tptr(d.term_t[t], 0);
+            a.term_ld[t] = h->tensors[d.term_t[t]].channels;
+            a.term_up[t] = d.term_up[t];
+          }
+          a.y = tptr(d.out_t, d.out_coff);
+          a.out_ld = to.channels; a.C = d.cout;
+          a.N = N; a.H = H >> to.ds_log2; a.W = W >> to.ds_log2;
+          a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
+          a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
+          RTPE_HP_LAUNCH(rc = fuse_launch(a, s));
         }
-        if (pairs_on && o.proj_head > 0 && pair_proj_runs(h, i, N, H, W)) {   // computed by the pair kernel: nothing to launch
-          proj_args = a;
-          proj_for = o.proj_head;
-          continue;
-        }
-        if (pairs_on && o.pair == 1 && direct_ok) {       // launched together with the next op (conv_pair.hip)
-          pair_args = a;
-          pair_pending = true;
-          continue;
-        }
-        RTPE_REQUIRE(proj_for != (int)i, "forward: op %zu is no 1x1 pair head at this shape, its projection was folded", i);
-        if (pair_pending) {
-          pair_pending = false;
-          const bool proj = proj_for == (int)i - 1;
-          RTPE_HP_LAUNCH(rc = conv_pair_launch(h->ops[i - 1].plan[0], pair_args, o.plan[0], a, s,
-                                               proj ? &h->ops[h->ops[i - 1].proj_op].plan[0] : nullptr, proj ? &proj_args : nullptr));
-          proj_for = -1;
-          continue;
-        }
-        RTPE_HP_LAUNCH(rc = conv_launch(o.plan[k], tile, a, s));
+        break;
       }
-    } else if (d.kind == RTPE_OP_AUX_PACK) {
-      if (aux == nullptr) { set_error("forward: this program has a second input (use rtpe_hrnet_forward_aux)"); return RTPE_E_INVALID; }
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      rc = aux_pack_launch(reinterpret_cast<const float*>(aux), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)),
-                           to.channels, N, H >> to.ds_log2, W >> to.ds_log2, s);
-    } else if (d.kind == RTPE_OP_RESIZE) {
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      rc = resize_nhwc_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, H >> ti.ds_log2,
-                              W >> ti.ds_log2, reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels,
-                              H >> to.ds_log2, W >> to.ds_log2, d.cout, N, s);
-    } else if (d.kind == RTPE_OP_GATE_MUL) {
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      const size_t pixels = (size_t)N * (H >> ti.ds_log2) * (W >> ti.ds_log2);
-      float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
-      if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
-        set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
-      }
-      float div;
-      memcpy(&div, &d.reserved[0], sizeof(float));
-      rc = gate_mul_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                           reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                           reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels, d.cout, pixels, div, att_out, s);
-    } else if (d.kind == RTPE_OP_CAST || d.kind == RTPE_OP_AVGPOOL || d.kind == RTPE_OP_SE ||
-               d.kind == RTPE_OP_CAM_COMBINE || d.kind == RTPE_OP_SIGMOID_ADD) {
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-      const size_t pixels = (size_t)N * Hi * Wi;
-      float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
-      if (d.kind == RTPE_OP_CAST) {
-        rc = cast_launch(tptr(d.in_t, d.in_coff), ti.channels, yo, to.channels, d.cout, pixels, s);
-      } else if (d.kind == RTPE_OP_AVGPOOL) {
-        rc = avgpool_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, yo, to.channels,
-                            d.cout, N, Hi, Wi, s);
-      } else if (d.kind == RTPE_OP_SE) {
-        rc = se_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, d.cin, d.cout, N, Hi * Wi,
-                       reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), yo, to.channels, s);
-      } else if (d.kind == RTPE_OP_CAM_COMBINE) {
-        rc = cam_combine_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                                reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                                reinterpret_cast<const float*>(tptr(d.term_t[0], 0)), h->tensors[d.term_t[0]].channels,
-                                yo, to.channels, d.cout, N, (size_t)Hi * Wi, s);
-      } else {
-        float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
-        if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
-          set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
-        }
-        rc = sigmoid_add_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                                reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                                yo, to.channels, d.cout, pixels, att_out, s);
-      }
-    } else {  // FUSE
-      const rtpe_tensor_desc& to = h->tensors[d.out_t];
-      FuseArgs a;
-      memset(&a, 0, sizeof(a));
-      a.n_terms = d.n_terms;
-      for (int t = 0; t < d.n_terms; ++t) {
-        a.term[t] = tptr(d.term_t[t], 0);
-        a.term_ld[t] = h->tensors[d.term_t[t]].channels;
-        a.term_up[t] = d.term_up[t];
-      }
-      a.y = tptr(d.out_t, d.out_coff);
-      a.out_ld = to.channels; a.C = d.cout;
-      a.N = N; a.H = H >> to.ds_log2; a.W = W >> to.ds_log2;
-      a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
-      a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
-      RTPE_HP_LAUNCH(rc = fuse_launch(a, s));
     }
     if (rc != RTPE_OK) return rc;
     if (lanes_on && cur_region > 0) {
       // (a 1x1 pair is ONE kernel, launched at the tail's place: the head's output exists behind that launch)
-      if (h->needs_event[i] && !pair_pending) RTPE_HIP_CHECK(hipEventRecord(h->op_event[i], s));
-      if (pairs_on && o.pair == 2 && h->needs_event[i - 1]) RTPE_HIP_CHECK(hipEventRecord(h->op_event[i - 1], s));
+      if (h->needs_event[i] && r.how != kRoutePairHead) RTPE_HIP_CHECK(hipEventRecord(h->op_event[i], s));
+      if (r.how == kRoutePairTail && h->needs_event[r.by]) RTPE_HIP_CHECK(hipEventRecord(h->op_event[r.by], s));
     }
-    const bool has_event = op_has_event(h, i, force == nullptr && only_op < 0);
+    const bool has_event = op_has_event(routes, i);
     if (timed && has_event) RTPE_HIP_CHECK(hipEventRecord(ev[i + 1], s));
-    if (rec && has_event) RTPE_HIP_CHECK(hipEventRecord((*rec)[i + 1], s));
+    if (rec && has_event) RTPE_HIP_CHECK(hipEventRecord(rec->ev[i + 1], s));
   }
   if (lanes_on && cur_region > 0) RTPE_HIP_CHECK(join_lanes());
   if (host_prof) {
@@ -1033,7 +1126,7 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
 #undef RTPE_HP_LAUNCH
   if (timed) {
     RTPE_HIP_CHECK(hipEventSynchronize(ev.back()));
-    const int rc2 = read_op_times(h, ev, force == nullptr && only_op < 0, op_ms);
+    const int rc2 = read_op_times(routes, ev, op_ms);
     for (auto& e : ev) hipEventDestroy(e);
     if (rc2 != RTPE_OK) return rc2;
   }
@@ -1052,7 +1145,7 @@ extern "C" int rtpe_hrnet_forward_flags(rtpe_hrnet* h, const void* x, int32_t x_
                                         size_t workspace_bytes, void* stream, uint32_t flags) {
   RTPE_REQUIRE((flags & ~(uint32_t)RTPE_FWD_NO_LANES) == 0, "forward_flags: unknown flag bits 0x%x", flags);
   return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, -1, -1, nullptr, nullptr, nullptr, flags);
+             reinterpret_cast<hipStream_t>(stream), nullptr, 0, nullptr, nullptr, flags);
 }
 
 extern "C" int rtpe_hrnet_forward_aux(rtpe_hrnet* h, const void* x, int32_t x_dtype, const void* aux_nchw_f32, int32_t N,
@@ -1060,7 +1153,7 @@ extern "C" int rtpe_hrnet_forward_aux(rtpe_hrnet* h, const void* x, int32_t x_dt
                                       void* workspace, size_t workspace_bytes, void* stream) {
   RTPE_REQUIRE(aux_nchw_f32 != nullptr, "forward_aux: the second input is null");
   return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, -1, -1, nullptr, nullptr, aux_nchw_f32);
+             reinterpret_cast<hipStream_t>(stream), nullptr, 0, nullptr, aux_nchw_f32);
 }
 
 extern "C" int rtpe_hrnet_forward_timed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
@@ -1145,8 +1238,9 @@ extern "C" int rtpe_conv2d_nhwc_ex(const void* x, int32_t N, int32_t H, int32_t 
   a.H_full = a.H_pos = H / stride; a.W_full = a.W_pos = W / stride; a.o_mul = 1;
   a.relu = (flags & RTPE_F_RELU) ? 1 : 0;
   a.round_conv = (flags & RTPE_F_ROUND_CONV) ? 1 : 0;
-  const bool one_window = a.x_bytes < 0x80000000ull;
-  const ConvTile tile = conv_make_tile(p, N, a.H_pos, a.W_pos, /*allow_direct=*/one_window, /*allow_conv64=*/one_window && res == nullptr);
+  const RouteOpts opt;
+  ConvTile tile = conv_make_tile(p, N, a.H_pos, a.W_pos);
+  conv_fix_tile(opt, p, a, /*plane_io=*/false, &tile);
   // diagnostic builds, RTPE_PROBE_PLANE=1: time a streaming launch with plane-major views ([C/48][N][H][W][48], what the
   // engine gives the inner tensors of the C >= 96 block chains) over the same bytes - the values are then meaningless
   static const int probe_plane = RTPE_DIAG_ENV_INT("RTPE_PROBE_PLANE", 0);
@@ -1162,7 +1256,7 @@ extern "C" int rtpe_conv2d_nhwc_ex(const void* x, int32_t N, int32_t H, int32_t 
   hipMemset(dbg, 0, 128);
   a.dbg = dbg;
 #endif
-  int rc = get_option(kOptConv48s2) != 0 && conv48s2_supports(p, a) ? conv48s2_launch(p, a, s) : conv_launch(p, tile, a, s);
+  int rc = launch_conv(conv_pick(opt, p, tile, a, /*plane_io=*/false), p, tile, a, s);
   hipError_t es2 = hipStreamSynchronize(s);
 #ifdef RTPE_CONV_STAMPS
   unsigned long long hd[16];
@@ -1288,20 +1382,12 @@ extern "C" int rtpe_deconv4x4s2_nhwc(const void* x, int32_t N, int32_t H, int32_
   int rc = RTPE_OK;
   std::vector<char*> dev_bufs;
   ConvArgs merged;
-  ConvTile merged_tile;
   memset(&merged, 0, sizeof(merged));
-  memset(&merged_tile, 0, sizeof(merged_tile));
-  // as in the forward: the four classes in one grid on class 0's launch shape when that is a one-workgroup-per-
-  // tile shape and all plans agree (RTPE_DECONV_MERGE=0: four launches); decided before any class is set up
-  static const int merge_deconv = env_int("RTPE_DECONV_MERGE", 1);
+  // as in the forward: the four classes in one launch on class 0's launch shape, or four launches
   ConvPlan plans[4];
   for (int k = 0; k < 4; ++k) plans[k] = conv_make_plan(ConvGeom{cin, cout, 4, 2, k, 2, 1});
   const ConvTile tile0 = conv_make_tile(plans[0], N, H, W);
-  bool merge = merge_deconv && tile0.kind == 0;
-  for (int k = 1; k < 4 && merge; ++k)
-    merge = plans[k].mt == plans[0].mt && plans[k].cc == plans[0].cc && plans[k].kc == plans[0].kc &&
-            plans[k].n_cchunks == plans[0].n_cchunks && plans[k].n_cb == plans[0].n_cb &&
-            plans[k].pstride == plans[0].pstride && plans[k].tapw == plans[0].tapw;
+  const bool merge = deconv_merges(plans, tile0);
   for (int k = 0; k < 4 && rc == RTPE_OK; ++k) {         // the four sub-pixel (parity) classes of the output
     ConvGeom g{cin, cout, 4, 2, k, 2, 1};
     const ConvPlan p = plans[k];
@@ -1331,13 +1417,8 @@ extern "C" int rtpe_deconv4x4s2_nhwc(const void* x, int32_t N, int32_t H, int32_
     const ConvTile tile = merge ? tile0 : conv_make_tile(p, N, a.H_pos, a.W_pos);
     conv_fill_args(g, p, tile, &a);
     if (merge) {
-      if (k == 0) { merged = a; merged_tile = tile; merged.n_cls = 4; }
-      merged.w_c[k] = a.w;
-      merged.lo_yc[k] = a.lo_y; merged.lo_xc[k] = a.lo_x;
-      merged.oy_c[k] = a.oy_add; merged.ox_c[k] = a.ox_add;
-      if (k == 3)
-        rc = get_option(kOptDeconv48) != 0 && deconv48_supports(plans[0], merged) ? deconv48_launch(plans[0], merged, s)
-                                                                                   : conv_launch(plans[0], merged_tile, merged, s);
+      deconv_merge_class(&merged, a, k);
+      if (k == 3) rc = launch_conv(deconv_pick(RouteOpts(), plans[0], merged), plans[0], tile0, merged, s);
       continue;
     }
     rc = conv_launch(p, tile, a, s);
@@ -1377,67 +1458,16 @@ extern "C" int rtpe_conv2d_nhwc(const void* x, int32_t N, int32_t H, int32_t W, 
                              flags & ~RTPE_F_F32, res, y, stream);
 }
 
-// introspection for bench / tuning: kernel variant and geometry of a conv op
+// introspection for bench / tuning: kernel variant and geometry of a conv op - the route of a forward of this shape that
+// binds a workspace, fp32 `preds` and `refined` (nominal, suitably aligned addresses: nothing is dereferenced)
 extern "C" int rtpe_hrnet_op_tile(const rtpe_hrnet* h, int32_t op, int32_t N, int32_t H, int32_t W, int32_t* out8) {
   RTPE_REQUIRE(h && out8 && op >= 0 && op < (int)h->ops.size(), "op_tile: bad argument");
-  const OpState& o = h->ops[op];
-  memset(out8, 0, 8 * sizeof(int32_t));
-  if (o.stem2 && get_option(kOptFusedStem) == 1 && stem_fused_supports(H, W)) {   // fused stem (stem_fused.hip): 8 x 16 tiles, 8 waves
-    out8[0] = 4; out8[1] = 4; out8[2] = 8; out8[3] = 8; out8[4] = 16; out8[5] = 64; out8[6] = 1;
-    out8[7] = o.stem2 == 1 ? -600001 : -600002;
-    return RTPE_OK;
-  }
-  if (o.n_geom == 0) return RTPE_OK;
-  const rtpe_op_desc& d = o.d;
-  const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-  const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-  const bool dc = d.kind == RTPE_OP_DECONV;
-  const int Hp = dc ? Hi : Hi / d.stride, Wp = dc ? Wi : Wi / d.stride;
-  ConvTile t = conv_make_tile(o.plan[0], N, Hp, Wp);
-  {
-    auto it = h->tuned.find(std::make_tuple(N, H, W));
-    if (it != h->tuned.end() && it->second[op * 4].nt) t = it->second[op * 4];
-  }
-  if (t.kind == 5 && (d.res_t >= 0 || (d.flags & RTPE_F_NO_NHWC))) t = conv_make_tile(o.plan[0], N, Hp, Wp, true, false);   // as run() does
-  if ((d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED)) && d.kind == RTPE_OP_CONV && d.ksize == 1 && d.cin == 48 && d.res_t < 0 &&
-      !(d.flags & RTPE_F_F32) && get_option(kOptHeadDirect) != 0 && o.plan[0].n_cb == 1 && (o.plan[0].mt == 2 || o.plan[0].mt == 3) &&
-      ((unsigned)Hi * (unsigned)Wi) % 32u == 0) {       // head on the direct scheme (conv_direct.hip): 32 pixels per wave step
-    out8[0] = o.plan[0].mt; out8[1] = 2; out8[2] = 4; out8[3] = 1; out8[4] = 32; out8[5] = 48; out8[6] = 1; out8[7] = -400001;
-    return RTPE_OK;
-  }
-  if (dc && get_option(kOptDeconv48) != 0 && t.kind == 0 && d.res_t < 0 && !(d.flags & RTPE_F_NO_NHWC) && !h->plane_ok[d.in_t] &&
-      !h->plane_ok[d.out_t] && o.plan[0].mt == 3 && o.plan[0].n_cb == 1 && o.plan[0].cout_pad == 48 && o.plan[0].n_cchunks <= 2) {
-    // the four classes on one persistent kernel (deconv48.hip): 8 x 16 input positions per tile, wave k = class k
-    out8[0] = 3; out8[1] = 2; out8[2] = 4; out8[3] = 8; out8[4] = 16; out8[5] = 48; out8[6] = 1; out8[7] = -300001;
-    return RTPE_OK;
-  }
-  if (!dc && get_option(kOptConv48s2) != 0 && d.ksize == 3 && d.stride == 2 && d.cin == 48 && d.res_t < 0 && !(d.flags & (RTPE_F_NO_NHWC | RTPE_F_F32)) &&
-      !h->plane_ok[d.in_t] && !h->plane_ok[d.out_t] && (d.cout == 48 || d.cout == 96 || d.cout == 192 || d.cout == 384) &&
-      o.plan[0].cout_pad == d.cout && Hi % 2 == 0 && Wi % 2 == 0) {
-    // persistent stride-2 kernel (conv48s2.hip): 8 x 8 output tiles, a wave = one group of 48 output channels
-    const int gw = d.cout == 48 ? 1 : d.cout == 96 ? 2 : 4;
-    out8[0] = 3; out8[1] = 2; out8[2] = 4; out8[3] = 8; out8[4] = 8; out8[5] = 48; out8[6] = d.cout / (48 * gw);
-    // -200001: a launch of its own; -20000n (n = 2, 3): first of n convs from one input in ONE launch; -200009: one of the others
-    out8[7] = o.s2g > 1 ? -(200000 + o.s2g) : o.s2g < 0 ? -200009 : -200001;
-    return RTPE_OK;
-  }
-  if (pair_proj_runs(h, op, N, H, W)) {             // computed inside its 1x1 pair (conv_pair.hip, PROJ): no launch of its own
-    out8[0] = 0; out8[1] = 1; out8[2] = 8; out8[3] = 1; out8[4] = 16; out8[5] = 64; out8[6] = 1; out8[7] = -800003;
-    return RTPE_OK;
-  }
-  if (o.pair && get_option(kOptPair1x1) != 0) {     // 1x1 pair (conv_pair.hip): 16-pixel tiles per wave, 8 waves
-    out8[0] = o.pair == 1 ? 16 : 4; out8[1] = 1; out8[2] = 8; out8[3] = 1; out8[4] = 16; out8[5] = o.pair == 1 ? 64 : 256; out8[6] = 1;
-    out8[7] = o.pair == 1 ? -800001 : -800002;
-    return RTPE_OK;
-  }
-  if (o.fuse) {       // fused BasicBlock (conv_block.hip): 6x32 tiles, 5 + 3 pixel tiles per wave
-    out8[0] = 3; out8[1] = o.fuse == 1 ? 5 : 3; out8[2] = 4; out8[3] = 6; out8[4] = 32; out8[5] = 48; out8[6] = 1;
-    out8[7] = o.fuse == 1 ? -900001 : -900002;
-    return RTPE_OK;
-  }
-  out8[0] = t.kind == 0 && t.mrun ? t.mrun : o.plan[0].mt; out8[1] = t.nt; out8[2] = t.waves; out8[3] = t.th; out8[4] = t.tw;
-  out8[5] = o.plan[0].cc; out8[6] = o.plan[0].n_cb; out8[7] = t.kind == 2 ? -(t.grid + 100000 * t.n_bufs) : t.kind == 4 ? -(700000 + t.grid) : t.kind == 5 ? -(500000 + t.grid)
-                                                            : (int32_t)t.lds_bytes;
+  const Fwd f(h, N, H, W, reinterpret_cast<void*>(256), reinterpret_cast<void*>(256), reinterpret_cast<void*>(256), RTPE_DTYPE_F32);
+  std::vector<Route> routes;
+  std::vector<ConvArgs> args;
+  const int rc = route_ops(f, &routes, &args);
+  if (rc != RTPE_OK) return rc;
+  route_label(h, routes, op, out8);
   return RTPE_OK;
 }
 
@@ -1457,7 +1487,11 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
   const size_t n_ops = h->ops.size();
   std::vector<float> ms(n_ops);
   int rc = run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, s, ms.data(), (int)n_ops,
-               -1, -1, nullptr, nullptr, aux);
+               nullptr, aux);
+  if (rc != RTPE_OK) return rc;
+  std::vector<Route> routes;                           // (of these forwards: no launch shape decides what is absorbed)
+  std::vector<ConvArgs> args;
+  rc = route_ops(Fwd(h, N, H, W, workspace, preds, refined, out_dtype), &routes, &args);
   if (rc != RTPE_OK) return rc;
 
   typedef std::tuple<int, int, int, int, int, int, int, int, int, int> Key;   // everything a launch shape depends on
@@ -1467,7 +1501,7 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
     const OpState& o = h->ops[i];
     const rtpe_op_desc& d = o.d;
     if (o.n_geom == 0) continue;
-    if (pair_proj_runs(h, i, N, H, W)) continue;       // computed inside its 1x1 pair in these forwards: nothing to time, stays untuned
+    if (routes[i].how == kRoutePairProj) continue;      // computed inside its 1x1 pair in these forwards: nothing to time, stays untuned
     const rtpe_tensor_desc& ti = h->tensors[d.in_t];
     const Key key = std::make_tuple(d.cin, d.cout, d.ksize, d.stride, (int)d.kind, (int)ti.ds_log2, d.res_t >= 0 ? 1 : 0,
                                     (int)(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED | RTPE_F_NO_NHWC | RTPE_F_F32)),
@@ -1501,7 +1535,7 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
     std::vector<float> best_ms(n_ops, 1e30f);
     for (int rep = 0; rep < 6; ++rep) {           // first repetition also warms caches for this choice
       rc = run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, s, ms.data(), (int)n_ops,
-               -1, -1, nullptr, nullptr, aux);
+               nullptr, aux);
       if (rc != RTPE_OK) { h->tuned.erase(shape); return rc; }
       if (rep == 0) continue;
       for (size_t i = 0; i < n_ops; ++i) best_ms[i] = ms[i] < best_ms[i] ? ms[i] : best_ms[i];
@@ -1554,17 +1588,17 @@ extern "C" int rtpe_hrnet_forward_record(rtpe_hrnet* h, const void* x, int32_t x
                                          void* workspace, size_t workspace_bytes, void* stream, int32_t slot) {
   RTPE_REQUIRE(h != nullptr && slot >= 0 && slot < 64, "forward_record: bad slot");
   return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, -1, -1, nullptr, &h->records[slot]);
+             reinterpret_cast<hipStream_t>(stream), nullptr, 0, &h->records[slot]);
 }
 
 extern "C" int rtpe_hrnet_read_record(rtpe_hrnet* h, int32_t slot, float* op_ms, int32_t n_ops) {
   RTPE_REQUIRE(h != nullptr && op_ms != nullptr, "read_record: null argument");
   DeviceGuard guard(h->device);
   auto it = h->records.find(slot);
-  RTPE_REQUIRE(it != h->records.end() && it->second.size() == h->ops.size() + 1 && n_ops >= (int)h->ops.size(),
+  RTPE_REQUIRE(it != h->records.end() && it->second.ev.size() == h->ops.size() + 1 && n_ops >= (int)h->ops.size(),
                "read_record: nothing recorded in slot %d", slot);
-  RTPE_HIP_CHECK(hipEventSynchronize(it->second.back()));
-  return read_op_times(h, it->second, true, op_ms);
+  RTPE_HIP_CHECK(hipEventSynchronize(it->second.ev.back()));
+  return read_op_times(it->second.routes, it->second.ev, op_ms);
 }
 
 // ---- tuned launch shapes: export / import (persisted by the caller, e.g. across processes) -------------------

@@ -339,12 +339,15 @@ def test_conv2d_fp32_is_exact(nat, cls, shape):
 # --------------------------------------------------------------------------- #
 # programs: stem (+ the 64 -> 64 stride-2 conv behind it), the direct heads, the 1x1 pair
 # --------------------------------------------------------------------------- #
-def _layer(cin, cout, k, s, g, bn=True, alpha_choices=(0.5, 1.0)):
+def _layer(cin, cout, k, s, g, bn=True, alpha_choices=(0.5, 1.0), density=1.0):
     """a Conv2d (+ BatchNorm2d that folds to exactly alpha, beta) with weights in {-1, 0, 1}; alpha a power of two and beta
-    a multiple of 1/2, so the quantum of the activations halves per layer at the most"""
+    a multiple of 1/2, so the quantum of the activations halves per layer at the most.  ``density`` < 1 keeps that share
+    of the weights and zeroes the others: the sums of a deep chain grow more slowly"""
     import torch.nn as nn
     conv = nn.Conv2d(cin, cout, k, s, k // 2, bias=not bn)
     w = torch.randint(-1, 2, conv.weight.shape, generator=g).float()
+    if density < 1.0:
+        w = w * (torch.rand(w.shape, generator=g) < density)
     alpha = torch.tensor(alpha_choices)[torch.randint(0, len(alpha_choices), (cout,), generator=g)] if bn else torch.ones(cout)
     beta = torch.randint(-8, 9, (cout,), generator=g).float() / 2
     norm = None
@@ -367,14 +370,20 @@ def _ref_layer(x, layer, k, s, relu, round_conv, res=None, quantum=None):
     return exact.reference(x, w, alpha, beta, res, k, s, 1, relu, round_conv).out
 
 
-def _forward(nat, eng, xg, N, H, W, out_shapes):
-    """rtpe_hrnet_forward on guarded input and outputs (the workspace is the executor's own)"""
+def _forward(nat, eng, xg, N, H, W, out_shapes, op_ms=None):
+    """rtpe_hrnet_forward on guarded input and outputs (the workspace is the executor's own); ``op_ms``: a list that
+    receives the per-op times of rtpe_hrnet_forward_timed instead"""
     ws = eng.workspace(N, H, W)
     pg, rg = [exact.guarded_out(s_, torch.float32) for s_ in out_shapes]
     xdt = nat.RTPE_DTYPE_F16 if xg.t.dtype == torch.float16 else nat.RTPE_DTYPE_F32
-    nat.check(nat.lib().rtpe_hrnet_forward_flags(eng._h, xg.t.data_ptr(), xdt, N, H, W, pg.t.data_ptr(), rg.t.data_ptr(),
-                                                 nat.RTPE_DTYPE_F32, ws.data_ptr(), ws.numel(),
-                                                 nat.stream_ptr(torch.device(DEV)), 0))
+    args = (eng._h, xg.t.data_ptr(), xdt, N, H, W, pg.t.data_ptr(), rg.t.data_ptr(), nat.RTPE_DTYPE_F32, ws.data_ptr(),
+            ws.numel(), nat.stream_ptr(torch.device(DEV)))
+    if op_ms is None:
+        nat.check(nat.lib().rtpe_hrnet_forward_flags(*args, 0))
+    else:
+        ms = (ctypes.c_float * len(eng.program.ops))()
+        nat.check(nat.lib().rtpe_hrnet_forward_timed(*args, ms, len(ms)))
+        op_ms[:] = list(ms)
     torch.cuda.synchronize()
     return pg, rg
 
@@ -431,6 +440,79 @@ def test_stem_and_direct_heads_are_exact(nat, shape):
                     assert (eng.op_tile(0, N, H, W)[7] == -600001) == (fused == 1)
                 pg, rg = _forward(nat, eng, xg, N, H, W, shapes)
             what = "stem program n%d %dx%d %s fused_stem=%d head_direct=%d" % (N, H, W, kind, fused, direct)
+            _same(pg.t.cpu().numpy(), want[0], what + " head 34")
+            _same(rg.t.cpu().numpy(), want[1], what + " head 17")
+            assert exact.guards_intact(xg, pg, rg), what
+
+
+def _block_program(g):
+    """the layers of: stem, conv 3x3 64 -> 48 stride 2 (the map at 1/4), one BasicBlock of the 48-channel branch (which
+    the executor flags for conv_block.hip), the two heads.  One alpha per layer behind the stem and a quarter of the
+    block's weights: max |activation| / quantum grows by about sqrt(taps x density) per layer, and the last sums
+    (48 taps at quantum 1/16) must stay below 2^24 quanta - _ref_layer asserts it for every layer of the chain"""
+    stem = _layer(3, 64, 3, 2, g)
+    down = _layer(64, 48, 3, 2, g, alpha_choices=(0.5,), density=0.5)
+    c1 = _layer(48, 48, 3, 1, g, alpha_choices=(0.5,), density=0.25)
+    c2 = _layer(48, 48, 3, 1, g, alpha_choices=(0.5,), density=0.25)
+    heads = [_layer(48, 34, 1, 1, g, bn=False), _layer(48, 17, 1, 1, g, bn=False)]
+    return stem, down, c1, c2, heads
+
+
+def _block_program_reference(layers, x):
+    stem, down, c1, c2, heads = layers
+    y = _ref_layer(x.double(), stem, 3, 2, True, True, quantum=1.0)
+    y = _ref_layer(y, down, 3, 2, True, True, quantum=0.5)
+    m = _ref_layer(y, c1, 3, 1, True, True, quantum=0.25)
+    y = _ref_layer(m, c2, 3, 1, True, True, res=y, quantum=0.125)
+    return [_ref_layer(y, hd, 1, 1, False, False, quantum=0.0625).float().numpy() for hd in heads]
+
+
+# input sizes: the block's map is the input's quarter.  conv_block_supports takes maps from 6 x 16 up: 16 x 16 and (W at
+# its limit, N = 3) 8 x 16 fuse, 16 x 8 does not and runs the two convs as launches of their own
+BLOCK_PROGRAM_SHAPES = [(1, 64, 64, True), (1, 64, 32, False), (3, 32, 64, True)]
+
+
+@pytest.mark.parametrize("shape", BLOCK_PROGRAM_SHAPES, ids=lambda s: "n%d_%dx%d_%s" % (s[:3] + ("fused" if s[3] else "two_launches",)))
+def test_basicblock_in_a_program_is_labelled_and_timed_as_it_runs(nat, shape):
+    """A flagged BasicBlock at a map size the fused kernel takes and at one it does not: rtpe_hrnet_op_tile and the per-op
+    times of rtpe_hrnet_forward_timed say what ran (the fused kernel: marks -900001 / -900002, the second conv's time
+    exactly 0; two launches: their launch shapes, a time each), and the outputs are THE answer either way."""
+    from rtpe.third_party.pose_higher_hrnet import Engine, ProgramBuilder
+    N, H, W, fuses = shape
+    g = torch.Generator().manual_seed(SEED + 48)
+    layers = _block_program(g)
+    stem, down, c1, c2, heads = layers
+    assert all(_affine_is_exact(l) for l in [stem, down, c1, c2] + heads)
+    b = ProgramBuilder(f32=False)
+    t = b.stem(stem[0], stem[1])
+    t = b.conv(t, down[0], down[1], relu=True)
+    m = b.conv(t, c1[0], c1[1], relu=True)
+    t = b.conv(m, c2[0], c2[1], relu=True, residual=t)
+    b.conv(t, heads[0][0], None, out_flag=nat.F_OUT_PREDS, nhwc=False)
+    b.conv(t, heads[1][0], None, out_flag=nat.F_OUT_REFINED, nhwc=False)
+    eng = Engine(b.finish(), 0)
+    # ops 2 and 3 are the block, and the executor flagged them: at a fusing size they report the fused kernel
+    assert [eng.op_tile(i, 1, 64, 64)[7] for i in (2, 3)] == [-900001, -900002]
+    x = torch.randint(-3, 4, (N, 3, H, W), generator=g).half()
+    want = _block_program_reference(layers, x)
+    xg = exact.guarded(x, exact.IN_SENTINEL)
+    shapes = [(N, 34, H // 4, W // 4), (N, 17, H // 4, W // 4)]
+    tiles = [eng.op_tile(i, N, H, W) for i in (2, 3)]
+    ms = []
+    _forward(nat, eng, xg, N, H, W, shapes, op_ms=ms)
+    if fuses:
+        assert [t_[7] for t_ in tiles] == [-900001, -900002]
+        assert ms[2] > 0 and ms[3] == 0.0
+    else:
+        for t_ in tiles:                                  # a launch shape: pixel tiles, waves, a tile; LDS bytes or the streaming form
+            assert t_[7] not in (-900001, -900002) and (t_[7] > 0 or t_[7] <= -100000)
+            assert t_[0] > 0 and t_[1] > 0 and t_[2] > 0 and t_[3] > 0 and t_[4] > 0
+        assert ms[2] > 0 and ms[3] > 0
+    for fused in (0, 1):
+        for direct in (0, 1):
+            with _Options(nat, fused_stem=fused, head_direct=direct):
+                pg, rg = _forward(nat, eng, xg, N, H, W, shapes)
+            what = "block program n%d %dx%d fused_stem=%d head_direct=%d" % (N, H, W, fused, direct)
             _same(pg.t.cpu().numpy(), want[0], what + " head 34")
             _same(rg.t.cpu().numpy(), want[1], what + " head 17")
             assert exact.guards_intact(xg, pg, rg), what
