@@ -220,7 +220,11 @@ int rtpe_hrnet_forward_flags(rtpe_hrnet* h, const void* x, int32_t x_dtype,
                              uint32_t flags);
 
 /* Same, but brackets every op with HIP events on `stream` and returns the
- * per-op time in ms (op_ms[n_ops]).  Host-returning (synchronises). */
+ * per-op time in ms (op_ms[n_ops]).  Host-returning (synchronises).  An op
+ * that the launch of an earlier op computes (rtpe_hrnet_op_tile's marks
+ * -200009, -600002, -900002) launches nothing: the second conv of a fused
+ * BasicBlock has no event and reports exactly 0; the others report the time
+ * between two event records with no kernel between them (>= 0). */
 int rtpe_hrnet_forward_timed(rtpe_hrnet* h, const void* x, int32_t x_dtype,
                              int32_t N, int32_t H, int32_t W,
                              void* preds, void* refined, int32_t out_dtype,

@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import exact
-from test_conv_exact_host import CLASSES, F32_CLASSES, SEED, regimes_of, seed_of
+import test_conv_exact_host as host
+from test_conv_exact_host import CLASSES, F32_CLASSES, SEED, _layer, _ref_layer, regimes_of, seed_of
 from test_gpu_parity import CONV_CASES
 
 pytestmark = pytest.mark.gpu
@@ -339,37 +340,6 @@ def test_conv2d_fp32_is_exact(nat, cls, shape):
 # --------------------------------------------------------------------------- #
 # programs: stem (+ the 64 -> 64 stride-2 conv behind it), the direct heads, the 1x1 pair
 # --------------------------------------------------------------------------- #
-def _layer(cin, cout, k, s, g, bn=True, alpha_choices=(0.5, 1.0), density=1.0):
-    """a Conv2d (+ BatchNorm2d that folds to exactly alpha, beta) with weights in {-1, 0, 1}; alpha a power of two and beta
-    a multiple of 1/2, so the quantum of the activations halves per layer at the most.  ``density`` < 1 keeps that share
-    of the weights and zeroes the others: the sums of a deep chain grow more slowly"""
-    import torch.nn as nn
-    conv = nn.Conv2d(cin, cout, k, s, k // 2, bias=not bn)
-    w = torch.randint(-1, 2, conv.weight.shape, generator=g).float()
-    if density < 1.0:
-        w = w * (torch.rand(w.shape, generator=g) < density)
-    alpha = torch.tensor(alpha_choices)[torch.randint(0, len(alpha_choices), (cout,), generator=g)] if bn else torch.ones(cout)
-    beta = torch.randint(-8, 9, (cout,), generator=g).float() / 2
-    norm = None
-    with torch.no_grad():
-        conv.weight.copy_(w)
-        if bn:
-            norm = nn.BatchNorm2d(cout)
-            norm.weight.copy_(alpha); norm.bias.copy_(beta); norm.running_mean.zero_(); norm.running_var.fill_(1.0 - norm.eps)
-        else:
-            conv.bias.copy_(beta)
-    conv.half()
-    return conv, norm, w.double(), alpha.double(), beta.double()
-
-
-def _ref_layer(x, layer, k, s, relu, round_conv, res=None, quantum=None):
-    """one layer of a program in float64; asserts the order-independence bound for its input"""
-    conv, norm, w, alpha, beta = layer
-    taps = w.shape[1] * k * k
-    assert torch.equal(torch.round(x / quantum) * quantum, x) and taps * float(x.abs().max()) / quantum < 2 ** 24
-    return exact.reference(x, w, alpha, beta, res, k, s, 1, relu, round_conv).out
-
-
 def _forward(nat, eng, xg, N, H, W, out_shapes, op_ms=None):
     """rtpe_hrnet_forward on guarded input and outputs (the workspace is the executor's own); ``op_ms``: a list that
     receives the per-op times of rtpe_hrnet_forward_timed instead"""
@@ -554,6 +524,103 @@ def test_1x1_pair_is_exact(nat, shape):
         _same(pg.t.cpu().numpy(), want[0], what + " head 34")
         _same(rg.t.cpu().numpy(), want[1], what + " head 17")
         assert exact.guards_intact(xg, pg, rg), what
+
+
+# --------------------------------------------------------------------------- #
+# sibling 3x3 stride-2 convs from one 48-channel map: conv48s2_launch_group, two or three layers as one grid
+# --------------------------------------------------------------------------- #
+S2_PREFIX = [3, 2, 4, 8, 8, 48]                     # rtpe_hrnet_op_tile of an op on conv48s2.hip, in front of n_cb and the mark
+SIBLING_PARAMS = [(set_id, shape) for i, set_id in enumerate(host.SIBLING_IDS) for shape in host.sibling_shapes(i)]
+SIBLING_PARAMS += [(set_id, host.SIBLING_WALKED) for set_id in host.SIBLING_WALKED_IDS]
+
+
+def _selection_head(c):
+    """a 1x1 conv without bias whose weights are the identity: output channel j is input channel j, exactly"""
+    import torch.nn as nn
+    conv = nn.Conv2d(c, c, 1, bias=False)
+    with torch.no_grad():
+        conv.weight.copy_(torch.eye(c).view(c, c, 1, 1))
+    return conv.half()
+
+
+def _sibling_engine(nat, set_id, deep, read):
+    """the program of a sibling set: front, the siblings next to each other, and two heads that read the siblings
+    ``read``; returns the executor and the index of the first sibling op"""
+    from rtpe.third_party.pose_higher_hrnet import Engine, ProgramBuilder
+    sibs = host.SIBLING_SETS[host.SIBLING_IDS.index(set_id)][1]
+    stem, convs = host.sibling_front_layers(deep)
+    layers = host.sibling_layers(set_id)
+    assert all(_affine_is_exact(l) for l in [stem] + [c[0] for c in convs] + layers)
+    b = ProgramBuilder(f32=False)
+    t = b.stem(stem[0], stem[1])
+    for layer, k, s in convs:
+        t = b.conv(t, layer[0], layer[1], relu=True)
+    first = len(b.ops)
+    outs = [b.conv(t, l[0], l[1], relu=bool(c[1])) for l, c in zip(layers, sibs)]
+    for k, flag in zip(read, (nat.F_OUT_PREDS, nat.F_OUT_REFINED)):
+        b.conv(outs[k], _selection_head(sibs[k][0]), None, out_flag=flag, nhwc=False)
+    prog = b.finish()
+    assert [(d.cin, d.cout, d.ksize, d.stride, d.in_t) for d in prog.ops[first:first + len(sibs)]] == \
+        [(48, c[0], 3, 2, t) for c in sibs]
+    return Engine(prog, 0), first
+
+
+@pytest.mark.parametrize("set_id,shape", SIBLING_PARAMS, ids=_CID)
+def test_sibling_stride2_convs_are_exact_as_one_launch(nat, set_id, shape):
+    """Two to four 3x3 stride-2 convs (48 or 96 output channels; each its own weights, alpha / beta, ReLU flag) that read
+    the same 48-channel map next to each other in a program: the executor runs the runs its static rule forms as ONE
+    launch of conv48s2.hip (conv48s2_launch_group: a slot per group of 48 channels with its own weights, affine, ReLU flag,
+    destination and row pitch).  Every element of every sibling is read back through a 1x1 head with identity weights
+    (fp32 NCHW; it reads -0 as +0: its sum starts at +0) - two siblings per program, so a set of three or four runs the
+    same layers in two programs - and compared with the float64 reference of its own layer
+    (test_conv_exact_host.sibling_outputs).  Asserted for every case: the launch labels under the default options (the
+    group marks of include/rtpe_hip.h: a test that silently ran single launches would prove nothing) and with conv48s2 = 0
+    (no conv48s2 mark), the per-op times of the small shapes, the outputs under conv48s2 0 / 1 x tile_dma 0 / 1, and the
+    guard bands.  The workspace is refilled with a finite value in front of every forward, so that an element a launch
+    does not write cannot keep the right value of the forward before."""
+    i = host.SIBLING_IDS.index(set_id)
+    sibs, marks = host.SIBLING_SETS[i][1:]
+    N, Ho, Wo = shape
+    deep = shape != host.SIBLING_WALKED
+    if not deep:
+        walked(N * (Ho // 8) * (Wo // 8))
+        assert N * (Ho // 8) * (Wo // 8) >= 5 * PERSISTENT_WORKGROUPS        # a workgroup's fifth halo tile: the ring of 4 wraps
+    x, t, q = host.sibling_front(deep, N, Ho, Wo)
+    H, W = x.shape[2:]
+    want = [(o + 0.0).float().numpy() for o in host.sibling_outputs(set_id, t, q)]
+    xg = exact.guarded(x, exact.IN_SENTINEL)
+    n = len(sibs)
+    fill = int(torch.tensor([host.SIBLING_PRESET], dtype=torch.float16).view(torch.int16)[0])
+    for read in [(0, 1)] + ([(2, 3 if n == 4 else 0)] if n > 2 else []):
+        eng, first = _sibling_engine(nat, set_id, deep, read)
+        ops = range(first, first + n)
+        shapes = [(N, sibs[k][0], Ho, Wo) for k in read]
+
+        def forward(what, **kw):
+            eng.workspace(N, H, W).view(torch.int16).fill_(fill)
+            pg, rg = _forward(nat, eng, xg, N, H, W, shapes, **kw)
+            _same(pg.t.cpu().numpy(), want[read[0]], what + " sibling %d" % read[0])
+            _same(rg.t.cpu().numpy(), want[read[1]], what + " sibling %d" % read[1])
+            assert exact.guards_intact(xg, pg, rg), what
+
+        what = "siblings %s n%d %dx%d heads %s" % (set_id, N, Ho, Wo, read)
+        assert [eng.op_tile(op, N, H, W) for op in ops] == [S2_PREFIX + [1, m] for m in marks], what
+        if deep:
+            # the first op of a group and a conv on its own are launches; an op the group's launch computes has an event of
+            # its own behind the group's with no kernel between them (include/rtpe_hip.h, rtpe_hrnet_forward_timed)
+            ms = []
+            forward(what + " timed", op_ms=ms)
+            for op, m in zip(ops, marks):
+                assert np.isfinite(ms[op]) and (ms[op] >= 0.0 if m == -200009 else ms[op] > 0.0), (what, op, m, ms[op])
+        for s2 in (1, 0):
+            for dma in (0, 1):
+                with _Options(nat, conv48s2=s2, tile_dma=dma):
+                    tiles = [eng.op_tile(op, N, H, W) for op in ops]
+                    if s2:
+                        assert [t_[7] for t_ in tiles] == marks, (what, tiles)
+                    else:
+                        assert not any(t_[:6] == S2_PREFIX and -200010 < t_[7] <= -200001 for t_ in tiles), (what, tiles)
+                    forward(what + " conv48s2=%d tile_dma=%d" % (s2, dma))
 
 
 # --------------------------------------------------------------------------- #
