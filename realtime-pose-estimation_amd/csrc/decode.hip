@@ -1577,8 +1577,9 @@ struct FlipPrepArgs {
 
 // FLIP: also the mirror image's maps (A_f, T_f); TAGS: also the tag maps (T_o, T_f); AGS: the j == 0 planes also write
 // the image's shared tag plane rs(P[:, J]) to `to` at plane plane0 / J + n (the expression of T_o[:, 0]); TF = false:
-// TAGS without T_f (the averaged-tag test reads the un-mirrored tag maps only)
-template <bool FLIP, bool TAGS, bool AGS = false, bool TF = TAGS>
+// TAGS without T_f (the averaged-tag test reads the un-mirrored tag maps only); AVG (with FLIP): neither A_o nor A_f is
+// written but their average H = (A_o + A_f) / 2, to `ao` (the decode without projection averages at this resolution)
+template <bool FLIP, bool TAGS, bool AGS = false, bool TF = TAGS, bool AVG = false>
 __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
   const int plane = blockIdx.y, n = plane / a.J, j = plane - n * a.J, q = a.perm[j];
   const int npix = a.h2 * a.w2;
@@ -1594,7 +1595,8 @@ __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
     axis_nc(a.sx, a.w4, a.w2, x, &x0, &x1, &lx0, &lx1);
     const size_t o = (size_t)(a.plane0 + plane) * npix + i;
     const float ph = taps_nc(P + (size_t)j * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
-    a.ao[o] = (ph + R[i]) / 2.f;
+    const float ho = (ph + R[i]) / 2.f;
+    if (!AVG) a.ao[o] = ho;
     if (TAGS) a.to[o] = taps_nc(P + (size_t)(a.J + j) * src_plane, a.w4, ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
     if (AGS && j == 0)
       a.to[(size_t)(a.plane0 / a.J + n) * npix + i] =
@@ -1607,7 +1609,9 @@ __device__ __forceinline__ void prep_planes(const FlipPrepArgs& a) {
       float lf0, lf1;
       axis_nc(a.sx, a.w4, a.w2, xs, &f0, &f1, &lf0, &lf1);
       const float fh = taps_nc(Pf + (size_t)q * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
-      a.af[o] = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
+      const float hf = (fh + Rf[(size_t)y * a.w2 + xs]) / 2.f;
+      if (AVG) a.ao[o] = (ho + hf) / 2.f;
+      else a.af[o] = hf;
       if (TF)
         a.tf[o] = taps_nc(Pf + (size_t)(a.J + q) * src_plane, a.w4, ident, y0, y1, f0, f1, ly0, ly1, lf0, lf1);
     }
@@ -1628,6 +1632,54 @@ __global__ void __launch_bounds__(256) ags_prep_kernel(const FlipPrepArgs a) { p
 // scale (tag_mean.hip's mean_plane_kernel reduces them behind this kernel)
 template <bool FLIP>
 __global__ void __launch_bounds__(256) mean_prep_kernel(const FlipPrepArgs a) { prep_planes<FLIP, true, false, false>(a); }
+
+// decode without projection (include/rtpe_hip_noproj.h), step 1 for one scale with flip: H = (A_o + A_f) / 2 of the
+// scale at its refined size [, T_o and T_f].  Without flip H = A_o: ms_prep_kernel<false, TAGS> writes it
+template <bool TAGS>
+__global__ void __launch_bounds__(256) np_prep_kernel(const FlipPrepArgs a) { prep_planes<true, TAGS, false, TAGS, true>(a); }
+
+// step 2 for every scale but the first: F = F + rs(H) in place at the decode grid, then F = F / div on the last scale
+// (div = 1: no division) - aggregate.hip's `dst + v`, then `/ div`, as separate operations.  One grid row per plane;
+// a thread handles V consecutive pixels of a row (V = 4: 16-byte loads and stores of F; needs ow % 4 == 0)
+struct NpAccumArgs {
+  const float* h;           // (N*J, sh, sw): H of the scale
+  float* f;                 // (N*J, oh, ow): F
+  NcAxes a;                 // (sh, sw) -> (oh, ow)
+  int plane0;               // first plane: image offset * J
+  float div;
+};
+
+template <int V>
+__global__ void __launch_bounds__(256) np_accum_kernel(const NpAccumArgs a) {
+  const int plane = a.plane0 + blockIdx.y;
+  const NcAxes& A = a.a;
+  const long long npix = (long long)A.oh * A.ow;
+  const float* src = a.h + (size_t)plane * A.sh * A.sw;
+  float* dst = a.f + (size_t)plane * npix;
+  for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * V; i < npix; i += (long long)gridDim.x * 256 * V) {
+    const int y = (int)(i / A.ow), x = (int)(i - (long long)y * A.ow);
+    int y0, y1;
+    float ly0, ly1;
+    axis_nc(A.sy, A.sh, A.oh, y, &y0, &y1, &ly0, &ly1);
+    float v[V];
+    if constexpr (V == 4) {
+      const float4 d = *reinterpret_cast<const float4*>(dst + i);
+      v[0] = d.x; v[1] = d.y; v[2] = d.z; v[3] = d.w;
+    } else {
+      v[0] = dst[i];
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      int x0, x1;
+      float lx0, lx1;
+      axis_nc(A.sx, A.sw, A.ow, x + k, &x0, &x1, &lx0, &lx1);
+      v[k] = v[k] + taps_nc(src, A.sw, A.ident, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+      if (a.div != 1.f) v[k] = v[k] / a.div;
+    }
+    if constexpr (V == 4) *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
+    else dst[i] = v[0];
+  }
+}
 
 }  // namespace rtpe
 
@@ -2421,6 +2473,156 @@ extern "C" int rtpe_adjust_refine_ms_mean_n(const float* maps, int32_t N, int32_
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_mean_n: P_dev is null");
   return decode_adjust_refine("adjust_refine_ms_mean_n",
                               MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev);
+}
+
+// ---------------------------------------------------------------------------
+// multi-scale (and flip) test WITHOUT projection to the image (include/rtpe_hip_noproj.h): rtpe/inference.py
+// multi_scale_inference(scale_factors, flip_test, project2image=False) for a whole batch.  The decode grid is r_0 =
+// (h2[0], w2[0]), the refined size of the largest scale.  The maps buffer, in floats:
+//     F                  (N*J, h2_0, w2_0)        the heat map, summed in place while the scales arrive
+//     T_o [, T_f]        (N*J, h2_b, w2_b) each   the tag maps of the scale-1 entry b = base at ITS refined size
+//     H_i, i = 1..S-1    (N*J, h2_i, w2_i)        the flip-averaged heat map of a later scale, read by its accumulate
+// rtpe_ms_np_prep of scale 0 writes H_0 straight into F; of a later scale, H_i and behind it F += rs(H_i) [/ S on the
+// last].  The decode reads F at integer pixels (DirectMap); the tags through FlipTag: a copy when scale 1 is first,
+// else the four taps of rs_(r_b -> r_0) on the fly (the arithmetic of aggregate_results' resize; the top-k gathers K
+// tags per plane and refine reads tags for missing joints only, so a resized copy would move more bytes).
+// ---------------------------------------------------------------------------
+struct NpLayout {
+  size_t f, to, tf, h[kMaxScales], total;     // float offsets; h[0] = f
+};
+
+static int np_layout(int N, int J, int S, const int32_t* h2, const int32_t* w2, int base, int flip, NpLayout* L) {
+  MsLayout M;                                 // (its checks: sizes, S <= kMaxScales, base one of the scales, J, planes)
+  const int rc = ms_layout(N, J, S, h2, w2, base, flip, kTagPerJoint, &M);
+  if (rc != RTPE_OK) return rc;
+  const size_t P = (size_t)N * J;
+  size_t o = P * h2[0] * w2[0];
+  L->f = L->h[0] = 0;
+  L->to = o;
+  o += P * h2[base] * w2[base];
+  L->tf = o;
+  if (flip) o += P * h2[base] * w2[base];
+  for (int i = 1; i < S; ++i) {
+    L->h[i] = o;
+    o += P * h2[i] * w2[i];
+  }
+  L->total = o;
+  return RTPE_OK;
+}
+
+struct NpSrc {
+  const float* maps;
+  int32_t N, J, S;
+  const int32_t *h2, *w2;
+  int32_t base, flip;
+  size_t maps_bytes;
+  int32_t oh, ow;           // filled by check(): the decode grid r_0
+  NpLayout L;               // likewise
+  int check(const char* who) {
+    const int rc = np_layout(N, J, S, h2, w2, base, flip, &L);
+    if (rc != RTPE_OK) return rc;
+    oh = h2[0];
+    ow = w2[0];
+    RTPE_REQUIRE(maps, "%s: bad argument", who);
+    RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "%s: maps buffer too small (%zu < %zu bytes)", who, maps_bytes,
+                 L.total * sizeof(float));
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    return f(DirectMap{maps + L.f, oh, ow},
+             FlipTag{maps + L.to, flip ? maps + L.tf : nullptr, nc_axes(h2[base], w2[base], oh, ow)}, 1 + flip);
+  }
+};
+
+extern "C" int rtpe_ms_np_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
+                                     int32_t base, int32_t flip, size_t* bytes) {
+  RTPE_REQUIRE(bytes, "ms_np_maps_bytes: null argument");
+  NpLayout L;
+  const int rc = np_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  *bytes = L.total * sizeof(float);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_ms_np_prep(const float* preds, int32_t h4, int32_t w4, int64_t preds_img_stride,
+                               const float* refined, int64_t refined_img_stride, const float* preds_f,
+                               int64_t preds_f_img_stride, const float* refined_f, int64_t refined_f_img_stride,
+                               int32_t n0, int32_t n, int32_t N, int32_t J, const int32_t* flip_index, int32_t S,
+                               const int32_t* h2, const int32_t* w2, int32_t base, int32_t flip, int32_t scale,
+                               float* maps, size_t maps_bytes, void* stream) {
+  NpLayout L;
+  int rc = np_layout(N, J, S, h2, w2, base, flip, &L);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(maps, "ms_np_prep: null argument");
+  RTPE_REQUIRE(scale >= 0 && scale < S, "ms_np_prep: scale %d of %d", scale, S);
+  RTPE_REQUIRE(n > 0 && n0 >= 0 && (int64_t)n0 + n <= N, "ms_np_prep: images %d..%d of %d", n0, n0 + n - 1, N);
+  RTPE_REQUIRE(maps_bytes >= L.total * sizeof(float), "ms_np_prep: maps buffer too small (%zu < %zu bytes)",
+               maps_bytes, L.total * sizeof(float));
+  FlipPrepArgs a;
+  rc = fill_prep("ms_np_prep", preds, h4, w4, preds_img_stride, refined, h2[scale], w2[scale], refined_img_stride,
+                 preds_f, preds_f_img_stride, refined_f, refined_f_img_stride, J, flip_index, flip != 0, &a);
+  if (rc != RTPE_OK) return rc;
+  a.plane0 = n0 * J;
+  a.ao = maps + L.h[scale];                   // scale 0: F itself
+  const bool tags = scale == base;
+  a.to = tags ? maps + L.to : nullptr;
+  a.tf = tags && flip ? maps + L.tf : nullptr;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid = prep_grid(h2[scale] * w2[scale], n * J);
+  if (flip && tags) hipLaunchKernelGGL((np_prep_kernel<true>), grid, dim3(256), 0, s, a);
+  else if (flip) hipLaunchKernelGGL((np_prep_kernel<false>), grid, dim3(256), 0, s, a);
+  else if (tags) hipLaunchKernelGGL((ms_prep_kernel<false, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((ms_prep_kernel<false, false>), grid, dim3(256), 0, s, a);
+  RTPE_HIP_CHECK(hipGetLastError());
+  if (scale == 0) return RTPE_OK;
+  NpAccumArgs b;
+  b.h = maps + L.h[scale];
+  b.f = maps + L.f;
+  b.a = nc_axes(h2[scale], w2[scale], h2[0], w2[0]);
+  b.plane0 = n0 * J;
+  b.div = scale == S - 1 ? (float)S : 1.f;
+  const long long npix = (long long)h2[0] * w2[0];
+  if (w2[0] % 4 == 0 && (reinterpret_cast<uintptr_t>(maps) & 15) == 0) {
+    const long long blocks = (npix / 4 + 255) / 256;
+    hipLaunchKernelGGL((np_accum_kernel<4>), dim3((unsigned)(blocks < 1024 ? blocks : 1024), n * J), dim3(256), 0, s, b);
+  } else {
+    const long long blocks = (npix + 255) / 256;
+    hipLaunchKernelGGL((np_accum_kernel<1>), dim3((unsigned)(blocks < 1024 ? blocks : 1024), n * J), dim3(256), 0, s, b);
+  }
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_topk_ms_np(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                               const int32_t* w2, int32_t base, int32_t flip, int32_t K, int32_t nms_ksize,
+                               int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
+                               void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_ms_np", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes}, K, nms_ksize, nms_pad,
+                     {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rtpe_adjust_refine_ms_np(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                        const int32_t* w2, int32_t base, int32_t flip, size_t maps_bytes,
+                                        const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                                        int32_t do_adjust, int32_t do_refine, float* scores, const float* topk_val,
+                                        const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
+                                        void* stream) {
+  return decode_adjust_refine("adjust_refine_ms_np", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr);
+}
+
+extern "C" int rtpe_adjust_refine_ms_np_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
+                                          const int32_t* w2, int32_t base, int32_t flip, size_t maps_bytes,
+                                          const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
+                                          int32_t do_adjust, int32_t do_refine, float* scores, const float* topk_val,
+                                          const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
+                                          void* stream, const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_np_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_ms_np_n", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes},
                               {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
                                scratch, scratch_bytes, stream}, P_dev);
 }

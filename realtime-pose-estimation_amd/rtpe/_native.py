@@ -222,6 +222,17 @@ _SIGS_TAGMEAN = {
     "rtpe_adjust_refine_ms_mean_n": (c_int32, list(_SIGS["rtpe_adjust_refine_ms_ags_n"][1])),
 }
 EXPORTS_TAGMEAN = tuple(_SIGS_TAGMEAN)  # those of include/rtpe_hip_tagmean.h, likewise
+# multi-scale / flip test without projection (include/rtpe_hip_noproj.h): the `_ms` entries; the decode grid is the
+# refined size of the largest scale, so the top-k and adjust + refine entries take no (oh, ow)
+_a = _SIGS["rtpe_adjust_refine_ms"][1]
+_SIGS_NOPROJ = {
+    "rtpe_ms_np_maps_bytes": (c_int32, list(_SIGS["rtpe_ms_maps_bytes"][1])),
+    "rtpe_ms_np_prep": (c_int32, list(_SIGS["rtpe_ms_prep"][1])),
+    "rtpe_topk_ms_np": (c_int32, _SIGS["rtpe_topk_ms"][1][:8] + _SIGS["rtpe_topk_ms"][1][10:]),
+    "rtpe_adjust_refine_ms_np": (c_int32, _a[:8] + _a[10:]),
+    "rtpe_adjust_refine_ms_np_n": (c_int32, _a[:8] + _a[10:] + [c_void_p]),
+}
+EXPORTS_NOPROJ = tuple(_SIGS_NOPROJ)    # those of include/rtpe_hip_noproj.h, likewise
 _lib = None
 
 
@@ -245,7 +256,7 @@ def lib():
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
-                list(_SIGS_TAGMEAN.items()):
+                list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -149,6 +149,11 @@ class TeacherPipeline:
     columns, with or without flip.  ``ags="mean"``: the averaged-tag test instead - that one tag map is the mean of
     the joints' tag maps (``HeatmapParser.parse_multi_scale``); ``"first"`` is ``True``, any other string a ValueError.
 
+    ``project2image=False`` (needs ``scale_factors``; ``(1,)`` for the single-scale protocol; not with ``ags``): the
+    test without projection to the image, ``multi_scale_inference(..., project2image=False)`` - the decode runs on the
+    refined size of the largest scale's input, r_0 = (H_0 / 2, W_0 / 2) (``HeatmapParser.parse_multi_scale``); people
+    are in heat-map pixels of that grid, and ``out_hw`` must be None or r_0.
+
     ``match_on``: ``"host"`` / ``"device"`` sets the parser's ``match_on`` (where the candidates are grouped into
     people, ``HeatmapParser``); None leaves the parser as it is.  With ``"device"`` the ``lowres_match`` call of
     ``stream()`` blocks on nothing; the order of the loop and the two-step delay of the results stay.
@@ -159,10 +164,18 @@ class TeacherPipeline:
     takes it as it is.  ``xform`` (N, 6): per image the float64 matrix of ``transforms.final_preds_matrix``, applied
     to (x, y) as ``get_final_preds`` does."""
 
+    project2image = True    # (the default of every pipeline; an instance asked for the other protocol sets its own)
+
     def __init__(self, model, parser=None, device=None, flip_test=False, flip_index=None, scale_factors=None,
-                 max_forward_pixels=MAX_FORWARD_PIXELS, ags=False, match_on=None):
+                 max_forward_pixels=MAX_FORWARD_PIXELS, ags=False, match_on=None, project2image=True):
         from .third_party.group import ags_mode
         ags = ags_mode(ags, "TeacherPipeline")  # False, True or "mean" (before any GPU work)
+        self.project2image = bool(project2image)
+        if not self.project2image and scale_factors is None:
+            raise ValueError("TeacherPipeline: project2image=False needs scale_factors (use (1,) for the single-scale "
+                             "protocol)")
+        if not self.project2image and ags:
+            raise ValueError("TeacherPipeline: ags has no batched form with project2image=False")
         if ags and scale_factors is None:
             raise ValueError("TeacherPipeline: ags=True needs scale_factors (use (1,) for the single-scale protocol)")
         if match_on not in (None, "host", "device"):
@@ -199,9 +212,13 @@ class TeacherPipeline:
     def _ms_begin(self, xs, out_hw):
         """maps buffer of a multi-scale batch (current stream); the decode size defaults to the scale-1 input size"""
         base = self.scale_factors.index(1)
+        refined_hw = [(x.shape[2] // 2, x.shape[3] // 2) for x in xs]
+        if not self.project2image:              # the decode grid is the refined size of the largest scale
+            return self.parser.ms_begin(xs[0].shape[0], refined_hw, out_hw, self.scale_factors, self.flip_test,
+                                        self.flip_index, self.device, False, False)
         hw = tuple(out_hw) if out_hw is not None else tuple(xs[base].shape[2:])
-        return self.parser.ms_begin(xs[0].shape[0], [(x.shape[2] // 2, x.shape[3] // 2) for x in xs], hw,
-                                    self.scale_factors, self.flip_test, self.flip_index, self.device, self.ags)
+        return self.parser.ms_begin(xs[0].shape[0], refined_hw, hw, self.scale_factors, self.flip_test,
+                                    self.flip_index, self.device, self.ags)
 
     def _ms_forwards(self, xs, fwd, on_outputs):
         """every scale's forward (and that of the mirror image) in sub-batches, in scale order, on the current stream;
@@ -222,6 +239,12 @@ class TeacherPipeline:
         n = (images[0] if isinstance(images, (list, tuple)) else images).shape[0]
         sizes = per_image_sizes(out_hw, n, "TeacherPipeline")
         if sizes is None:
+            if not self.project2image:
+                x0 = images[0] if isinstance(images, (list, tuple)) else images
+                r0 = (x0.shape[2] // 2, x0.shape[3] // 2)
+                if (int(out_hw[0]), int(out_hw[1])) != r0:
+                    raise ValueError("TeacherPipeline: without projection the decode grid is the refined size %s of "
+                                     "the largest scale, not out_hw = %s" % (r0, tuple(out_hw)))
             return tuple(out_hw)
         if self.flip_test or self.scale_factors is not None:
             raise ValueError("TeacherPipeline: per-image decode sizes are for the plain protocol only; with flip_test "
@@ -516,10 +539,11 @@ class StudentPipeline(TeacherPipeline):
 
     There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
 
-    def __init__(self, model, parser=None, device=None, match_on=None, flip_test=False, scale_factors=None, ags=False):
-        if flip_test or scale_factors is not None or ags:       # (before any GPU work)
-            raise ValueError("StudentPipeline: flip_test, scale_factors and ags are test protocols of the teacher; "
-                             "the students have the plain protocol only")
+    def __init__(self, model, parser=None, device=None, match_on=None, flip_test=False, scale_factors=None, ags=False,
+                 project2image=True):
+        if flip_test or scale_factors is not None or ags or not project2image:      # (before any GPU work)
+            raise ValueError("StudentPipeline: flip_test, scale_factors, ags and project2image=False are test "
+                             "protocols of the teacher; the students have the plain protocol only")
         super().__init__(model, parser, device, match_on=match_on)
 
     def _decode_hw(self, out_hw, images):

@@ -223,7 +223,8 @@ def _in_input_order(recs, order, n_images, device):
     return rec.index_select(0, inv.to(rec.device, non_blocking=True))
 
 
-def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk, batch_scales=None, image_ids=None):
+def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chunk, batch_scales=None, image_ids=None,
+                    project2image=True):
     """the tail of the batched drivers: images of one ``sizes`` entry form a group (``entry[base]`` is its
     projection size ``(w, h)``), a group is cut into chunks of ``batch_size``, ``warp_chunk(warp)`` makes one item of
     ``pipe.stream`` from ``warp(s, lo)`` - the chunk's images warped at scale ``s`` as one tensor - and the keypoints
@@ -231,12 +232,14 @@ def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chun
     ``batch_scales`` (``warp="batch"``): every ``(s, lo)`` that ``warp_chunk`` asks for, in its order; a chunk is then
     made by ONE ``transforms.warp_normalize_batch`` call for all of them, and ``warp`` only hands its tensors out.
     ``image_ids``: one id per image; the result is then ONE (len(images), RECORD_FLOATS) record tensor on the device in
-    input order, the mapping back done by the record kernel with each image's ``transforms.final_preds_matrix``."""
+    input order, the mapping back done by the record kernel with each image's ``transforms.final_preds_matrix``.
+    ``project2image=False``: the decode grid, and the size ``get_final_preds`` takes, is the heat-map size
+    ``[w2_0, h2_0]`` of the largest scale, half of ``entry[0]``."""
     from .third_party import transforms
     out = [None] * len(images)
     recs, order = [], []
     for key, idx in group_by_input_size(sizes):
-        w, h = key[base]
+        w, h = key[base] if project2image else (key[0][0] // 2, key[0][1] // 2)
         chunks = [idx[o:o + batch_size] for o in range(0, len(idx), batch_size)]
         meta = {}
 
@@ -280,7 +283,7 @@ def _stream_by_size(pipe, images, input_size, sizes, base, batch_size, warp_chun
 
 
 def flip_test_inference(model, parser, images, input_size=640, adjust=True, refine=True, batch_size=32,
-                        device="cuda", ags=False, match_on=None, warp="image", image_ids=None):
+                        device="cuda", ags=False, match_on=None, warp="image", image_ids=None, project2image=True):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors=(1,),
     flip_test=True, project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: every image is
     warped to its network input size, images of one size are batched (``batch_size`` at a time) through
@@ -301,16 +304,20 @@ def flip_test_inference(model, parser, images, input_size=640, adjust=True, refi
 
     ``image_ids`` (one int per image; needs ``match_on="device"``, given here or set on the parser): the result is one
     ``(len(images), engine.RECORD_FLOATS)`` float32 tensor on the device in input order - ``engine.pack_records`` of
-    the list result, ``get_final_preds`` included, written by the record kernel; the host reads no keypoint."""
+    the list result, ``get_final_preds`` included, written by the record kernel; the host reads no keypoint.
+
+    ``project2image=False``: the drop-in for the per-image call with ``project2image=False`` instead - the decode on
+    the heat-map grid (h2, w2), a quarter of the pixels and no projection (``multi_scale_batch_inference`` with
+    ``scale_factors=(1,)``, see there); not with ``ags``."""
     from .engine import TeacherPipeline
     from .third_party import transforms
     from .third_party.group import ags_mode
     batched = _warp_mode(warp)
     ags = ags_mode(ags, "flip_test_inference")
-    if ags:
+    if ags or not project2image:
         return multi_scale_batch_inference(model, parser, images, input_size, (1,), True, adjust, refine, batch_size,
                                            device=device, ags=ags, warp=warp, image_ids=image_ids,
-                                           **_match_kw(match_on))
+                                           project2image=project2image, **_match_kw(match_on))
     if not parser.tag_per_joint:
         raise ValueError("flip_test_inference: the flip test needs a parser with tag_per_joint=True")
     if batch_size < 1:
@@ -356,7 +363,7 @@ def multi_scale_input_sizes(image, input_size, scale_factors):
 
 def multi_scale_batch_inference(model, parser, images, input_size=640, scale_factors=(2, 1, 0.5), flip_test=True,
                                 adjust=True, refine=True, batch_size=32, max_forward_pixels=None, device="cuda",
-                                ags=False, match_on=None, warp="image", image_ids=None):
+                                ags=False, match_on=None, warp="image", image_ids=None, project2image=True):
     """Batched drop-in for ``multi_scale_inference(model, parser, img, input_size, scale_factors, flip_test,
     project2image=True, adjust, refine)`` over a list of (h, w, 3) uint8 images: images are grouped by their input
     sizes at every scale, every image is warped at every scale, each group is streamed ``batch_size`` images at a
@@ -378,10 +385,18 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
     ``warp``: ``"image"`` warps one image and one scale at a time, ``"batch"`` a whole chunk at every scale with one
     upload and one launch per scale (``transforms.warp_normalize_batch``, needs real uint8 images); same bits.
 
-    ``image_ids``: as for ``flip_test_inference`` - one record tensor on the device in input order."""
+    ``image_ids``: as for ``flip_test_inference`` - one record tensor on the device in input order.
+
+    ``project2image=False``: the drop-in for the per-image call with ``project2image=False`` - the heat maps are
+    averaged at each scale's own heat-map size and summed at that of the largest scale, where the decode runs
+    (``TeacherPipeline(..., project2image=False)``); ``get_final_preds``, and the ``xform`` of the records, take that
+    size ``[w2_0, h2_0]``.  ``ags`` together with it is a ValueError before any GPU work."""
     from .engine import MAX_FORWARD_PIXELS, TeacherPipeline
     from .third_party.group import ags_mode
     ags = ags_mode(ags, "multi_scale_batch_inference")
+    if ags and not project2image:
+        raise ValueError("multi_scale_batch_inference: ags has no batched form with project2image=False (it stays "
+                         "per-image, multi_scale_inference)")
     batched = _warp_mode(warp)
     kw = _match_kw(match_on)
     scales = check_scale_factors(scale_factors)
@@ -397,11 +412,11 @@ def multi_scale_batch_inference(model, parser, images, input_size=640, scale_fac
         parser.tag_per_joint = False                                    # as multi_scale_inference(..., ags=True)
     pipe = TeacherPipeline(model, parser, device=device, flip_test=flip_test, scale_factors=scales,
                            max_forward_pixels=MAX_FORWARD_PIXELS if max_forward_pixels is None else max_forward_pixels,
-                           ags=ags, **kw)
+                           ags=ags, **({} if project2image else {"project2image": False}), **kw)
     # one tensor per scale, largest first: the last warp, whose centre / scale is kept, is the smallest scale's
     return _stream_by_size(pipe, images, input_size, sizes, base, batch_size,
                            lambda warp: [warp(s, lo) for s in scales], [(s, lo) for s in scales] if batched else None,
-                           image_ids)
+                           image_ids, project2image)
 
 
 class _Shape:

@@ -8,7 +8,12 @@ headline configuration: batch 32, 640 x 640), then
   * multi_scale_inference(scale_factors=(1,), flip_test=True) image by image on 64 uint8 images of 640 x 640.
 Prints one JSON line.  Needs a GPU; there is no fallback.
 
+``--no-project``: instead, the flip test without projection (``project2image=False``, the decode on the heat-map grid)
+against the projected flip pipeline in the same process, A B B A, medians of ``--repeats`` runs of ``--steps`` batches,
+with the decode's device phases and the maps buffers of both (tools/noproj_compare.py).
+
     python tools/flip_bench.py [--steps 20] [--warmup 3] [--images 64]
+    python tools/flip_bench.py --no-project [--steps 12] [--warmup 3] [--repeats 4]
 """
 import argparse
 import json
@@ -33,6 +38,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--images", type=int, default=64, help="images of the per-image loop")
     ap.add_argument("--decode-reps", type=int, default=10)
+    ap.add_argument("--no-project", action="store_true",
+                    help="time the test without projection (project2image=False) against the projected protocol "
+                         "instead: A B B A, medians of --repeats runs of --steps batches (tools/noproj_compare.py)")
+    ap.add_argument("--repeats", type=int, default=4)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("flip_bench: no GPU (the flip test runs on the HIP path only)")
@@ -50,6 +59,11 @@ def main():
     sd = synth.make_state_dict(shapes, 0, "W0")
     model = build_hrnet_w48_teacher({"1." + k: v for k, v in sd.items()}).to(dev)
     B, S = args.batch, args.size
+    if args.no_project:
+        from noproj_compare import compare
+        print(json.dumps(compare(model, dev, B, S, (1,), args.steps, args.warmup, args.repeats, args.decode_reps,
+                                 parse_flip=True)))
+        return
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
     xs = [torch.randn(B, 3, S, S, generator=g, device=dev) for _ in range(4)]

@@ -11,7 +11,12 @@ inputs are 1280 x 1280, 640 x 640 and 320 x 320 for the default scales (2, 1, 0.
     state of the multi-scale pipeline.
 Prints one JSON line.  Needs a GPU; there is no fallback.
 
+``--no-project``: instead, the multi-scale (+ flip) test without projection (``project2image=False``) against the
+projected one in the same process, A B B A, medians of ``--repeats`` runs of ``--steps`` batches, with the decode's
+device phases and the maps buffers of both (tools/noproj_compare.py).
+
     python tools/multiscale_bench.py [--steps 6] [--warmup 2] [--images 32]
+    python tools/multiscale_bench.py --no-project [--steps 12] [--warmup 2] [--repeats 4]
 """
 import argparse
 import json
@@ -37,6 +42,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--images", type=int, default=32, help="images of the per-image loop")
     ap.add_argument("--decode-reps", type=int, default=5)
+    ap.add_argument("--no-project", action="store_true",
+                    help="time the test without projection (project2image=False) against the projected protocol "
+                         "instead: A B B A, medians of --repeats runs of --steps batches (tools/noproj_compare.py)")
+    ap.add_argument("--repeats", type=int, default=4)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("multiscale_bench: no GPU (the multi-scale test runs on the HIP path only)")
@@ -56,6 +65,10 @@ def main():
     model = build_hrnet_w48_teacher({"1." + k: v for k, v in sd.items()}).to(dev)
     B, S = args.batch, args.size
     scales = inference.check_scale_factors([float(v) if "." in v else int(v) for v in args.scales.split(",")])
+    if args.no_project:
+        from noproj_compare import compare
+        print(json.dumps(compare(model, dev, B, S, scales, args.steps, args.warmup, args.repeats, args.decode_reps)))
+        return
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
     xs = [torch.randn(B, 3, S, S, generator=g, device=dev) for _ in range(2)]
