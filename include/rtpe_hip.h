@@ -710,5 +710,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_records.h"
 #include "rtpe_hip_tagmean.h"
 #include "rtpe_hip_noproj.h"
+#include "rtpe_hip_anysize.h"
 
 #endif /* RTPE_HIP_H */

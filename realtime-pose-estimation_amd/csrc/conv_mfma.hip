@@ -770,7 +770,7 @@ static bool conv64_tile(const ConvPlan& p, int N, int H_pos, int W_pos, ConvTile
   return true;
 }
 
-ConvTile conv_make_tile(const ConvPlan& p, int N, int H_pos, int W_pos, bool allow_direct, bool allow_conv64) {
+ConvTile conv_make_tile(const ConvPlan& p, int N, int H_pos, int W_pos, bool allow_direct, bool allow_conv64, bool allow_stream) {
   if (allow_direct) {
     ConvTile t;
     if (direct_tile(p, &t)) return t;
@@ -780,7 +780,7 @@ ConvTile conv_make_tile(const ConvPlan& p, int N, int H_pos, int W_pos, bool all
     if (conv64_tile(p, N, H_pos, W_pos, &t)) return t;
   }
   static const int stream = getenv("RTPE_CONV_STREAM") ? atoi(getenv("RTPE_CONV_STREAM")) : 1;
-  if ((stream & 1) && conv_stream_supports(p)) {
+  if (allow_stream && (stream & 1) && conv_stream_supports(p)) {
     ConvTile t = make_stream_tile(p, N, H_pos, W_pos);
     if (t.nt) return t;
   }

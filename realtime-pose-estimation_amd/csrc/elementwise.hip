@@ -89,9 +89,78 @@ __global__ void __launch_bounds__(256) fuse_rows_kernel(const FuseArgs a, const 
   store16_wt(reinterpret_cast<T*>(a.y) + ((size_t)(n * (uint32_t)a.H + y) * a.W + x) * a.out_ld + cs * EPS, oraw);
 }
 
+// The sum at a ragged shape (FuseArgs::nearest; programs with the any_size property): term t holds term_h[t] x term_w[t] pixels
+// and F.interpolate(term, (H, W), mode="nearest") picks source min((int)floorf(dst * scale), in - 1) with the fp32 scale
+// (float)in / (float)out per axis - not dst >> up: from 3 to 9 columns the rule reads 0 0 0 1 1 1 2 2 2, the shift 0 0 0 0 1 1 1 1 2.
+// Grid and work split of fuse_rows_kernel.  The source row of every term and the source columns of the block's <= 257 output
+// columns are worked out once per workgroup into LDS, not per 16-byte piece.  Same adds in the same order as the other two.
+constexpr int kFuseCols = 257;     // 256 consecutive row pieces touch at most 256 columns + 1 (a piece run may start mid-pixel)
+template <typename T>
+__global__ void __launch_bounds__(256) fuse_nearest_kernel(const FuseArgs a, const FastDiv div_c8, const FastDiv div_h) {
+  constexpr int EPS = 16 / (int)sizeof(T);
+  __shared__ int sx[4][kFuseCols];
+  __shared__ int sy[4];
+  const int c8 = a.C / EPS;
+  const uint32_t p0 = blockIdx.x * 256u;
+  const uint32_t x_first = fdiv(p0, div_c8);
+  const uint32_t n = fdiv(blockIdx.y, div_h), y = blockIdx.y - n * (uint32_t)a.H;
+  for (int i = threadIdx.x; i < 4 * kFuseCols; i += 256) {
+    const int t = i / kFuseCols, k = i - t * kFuseCols;
+    const int x = (int)x_first + k;
+    if (t < a.n_terms && x < a.W) sx[t][k] = nearest_src(x, a.term_w[t], (float)a.term_w[t] / (float)a.W);
+  }
+  if ((int)threadIdx.x < a.n_terms)
+    sy[threadIdx.x] = nearest_src((int)y, a.term_h[threadIdx.x], (float)a.term_h[threadIdx.x] / (float)a.H);
+  __syncthreads();
+  const uint32_t p = p0 + threadIdx.x;
+  if (p >= (uint32_t)(a.W * c8)) return;
+  const uint32_t x = fdiv(p, div_c8), cs = p - x * (uint32_t)c8;
+  uint4 raw[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {                            // all loads first
+    if (t >= a.n_terms) break;
+    const size_t src = ((size_t)n * a.term_h[t] + sy[t]) * a.term_w[t] + sx[t][x - x_first];
+    raw[t] = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.term[t]) + src * a.term_ld[t] + cs * EPS);
+  }
+  float acc[EPS];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t >= a.n_terms) break;
+    T v[EPS];
+    __builtin_memcpy(v, &raw[t], 16);
+#pragma unroll
+    for (int j = 0; j < EPS; ++j) acc[j] = t == 0 ? (float)v[j] : (float)(T)(acc[j] + (float)v[j]);
+  }
+  T o[EPS];
+#pragma unroll
+  for (int j = 0; j < EPS; ++j) o[j] = (T)((acc[j] > 0.f || !a.relu) ? acc[j] : 0.f);
+  uint4 oraw;
+  __builtin_memcpy(&oraw, o, 16);
+  store16_wt(reinterpret_cast<T*>(a.y) + ((size_t)(n * (uint32_t)a.H + y) * a.W + x) * a.out_ld + cs * EPS, oraw);
+}
+
+// the shapes the nearest-to-size sampler takes (its grid has one row of workgroups per output row)
+bool fuse_nearest_supports(int N, int H, int W, int C, int f32) {
+  const long row_pieces = (long)W * (C / (f32 ? 4 : 8)), n_rows = (long)N * H;
+  return n_rows >= 1 && n_rows <= 65535 && row_pieces >= 1 && row_pieces < (1l << 20);
+}
+
 int fuse_launch(const FuseArgs& a, hipStream_t s) {
   const int eps = a.f32 ? 4 : 8;
   RTPE_REQUIRE(a.C % eps == 0 && a.n_terms >= 1 && a.n_terms <= 4, "fuse: C=%d terms=%d", a.C, a.n_terms);
+  if (a.nearest) {
+    RTPE_REQUIRE(fuse_nearest_supports(a.N, a.H, a.W, a.C, a.f32), "fuse: N=%d H=%d W=%d C=%d is too large for the nearest-to-size sampler",
+                 a.N, a.H, a.W, a.C);
+    for (int t = 0; t < a.n_terms; ++t)
+      RTPE_REQUIRE(a.term_h[t] >= 1 && a.term_w[t] >= 1 && a.term_h[t] <= a.H && a.term_w[t] <= a.W, "fuse: term %d is %d x %d", t,
+                   a.term_h[t], a.term_w[t]);
+    const dim3 grid((unsigned)(((long)a.W * (a.C / eps) + 255) / 256), (unsigned)(a.N * a.H));
+    const FastDiv dc = make_fastdiv((uint32_t)(a.C / eps)), dh = make_fastdiv((uint32_t)a.H);
+    if (a.f32) hipLaunchKernelGGL(fuse_nearest_kernel<float>, grid, dim3(256), 0, s, a, dc, dh);
+    else hipLaunchKernelGGL(fuse_nearest_kernel<_Float16>, grid, dim3(256), 0, s, a, dc, dh);
+    RTPE_HIP_CHECK(hipGetLastError());
+    return RTPE_OK;
+  }
   static const int rows = env_int("RTPE_FUSE_ROWS", 1);
   const long row_pieces = (long)a.W * (a.C / eps), n_rows = (long)a.N * a.H;
   if (rows && n_rows <= 65535 && n_rows < (1l << 20) && row_pieces < (1l << 20) && (long)a.N * a.H * a.W < (1l << 31)) {
@@ -129,7 +198,9 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
   constexpr bool kHalf = sizeof(T) == 2;
   __shared__ float patch[3][kStemPH][kStemPW + 1];
   __shared__ __attribute__((aligned(16))) float wl[27][kStemCO];
-  const int Ho = a.H >> 1, Wo = a.W >> 1;
+  // ceil(H / 2) x ceil(W / 2): with an odd side the last output row / column reads one tap beyond the image, which the
+  // staging below zeroes like the padding at the low edge
+  const int Ho = (a.H + 1) >> 1, Wo = (a.W + 1) >> 1;
   const int tiles_x = (Wo + kStemTW - 1) / kStemTW, tiles_y = (Ho + kStemTH - 1) / kStemTH;
   // Workgroups are dealt to the 8 XCDs round robin (blockIdx.x % 8): an XCD takes a CONTIGUOUS eighth of the row-major
   // tile list, so that neighbouring tiles - whose 65-float patch rows share their first / last 128-byte line and
@@ -277,9 +348,9 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
 }
 
 int stem_launch(const StemArgs& a, hipStream_t s) {
-  RTPE_REQUIRE(a.H % 2 == 0 && a.W % 2 == 0 && a.out_ld % 8 == 0, "stem: H=%d W=%d", a.H, a.W);
+  RTPE_REQUIRE(a.H >= 1 && a.W >= 1 && a.out_ld % 8 == 0, "stem: H=%d W=%d", a.H, a.W);
   RTPE_REQUIRE((size_t)a.N * 3 * a.H * a.W < 0x7fffffffull, "stem: input of %d x 3 x %d x %d elements", a.N, a.H, a.W);
-  const int Ho = a.H / 2, Wo = a.W / 2;
+  const int Ho = (a.H + 1) / 2, Wo = (a.W + 1) / 2;
   const int tiles = ((Wo + kStemTW - 1) / kStemTW) * ((Ho + kStemTH - 1) / kStemTH);
   const unsigned grid = (unsigned)(((size_t)tiles * a.N + 7) / 8 * 8);            // an eighth of the tiles per XCD
   if (a.f32)

@@ -104,6 +104,7 @@ struct rtpe_hrnet {
   std::vector<std::vector<int>> wait_ops;
   hipEvent_t fork_event = nullptr;
   bool has_regions = false;
+  bool any_size = false;     // rtpe_hrnet_set_any_size: ragged shapes (a side that is no multiple of 32) are taken, on the general paths
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -484,7 +485,7 @@ extern "C" int rtpe_hrnet_destroy(rtpe_hrnet* h) {
 static void slot_layout(const rtpe_hrnet* h, int N, int H, int W, std::vector<size_t>* offs, size_t* total) {
   std::vector<size_t> sz(h->n_slots, 0);
   for (const auto& t : h->tensors) {
-    const size_t px = t.ds_log2 < 0 ? 1 : (size_t)(H >> t.ds_log2) * (W >> t.ds_log2);
+    const size_t px = t.ds_log2 < 0 ? 1 : (size_t)extent(H, t.ds_log2) * extent(W, t.ds_log2);
     const size_t b = (size_t)N * px * t.channels * (t.reserved == 4 ? 4 : 2);
     if (b > sz[t.slot]) sz[t.slot] = b;
   }
@@ -494,8 +495,32 @@ static void slot_layout(const rtpe_hrnet* h, int N, int H, int W, std::vector<si
   *total = o;
 }
 
+// The shapes a handle takes, checked before anything is sized or launched.  Multiples of 32: every program.  Ragged shapes (a side
+// that is no multiple of 32): programs with the any_size property whose ops all have a general path - a transposed conv doubles a
+// map that the extent rule does not double, and a fused BasicBlock pair or a stride-2 group has no launch of its own to fall
+// back to in the records of a forward.  The nearest-to-size sampler of the fuse ops has one row of workgroups per output row.
+static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who) {
+  RTPE_REQUIRE(N > 0 && H >= 32 && W >= 32, "%s: N=%d H=%d W=%d", who, N, H, W);
+  if (!ragged(H, W)) return RTPE_OK;
+  RTPE_REQUIRE(h->any_size, "%s: N=%d H=%d W=%d: H and W must be multiples of 32 for this program (its branches at 1/4 .. 1/32 "
+               "are fused by factor-2 resampling; only programs with the any_size property take other sizes)", who, N, H, W);
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    const OpState& o = h->ops[i];
+    RTPE_REQUIRE(o.d.kind != RTPE_OP_DECONV && o.fuse == 0 && o.s2g == 0,
+                 "%s: op %zu (%s) cannot take a map of %d x %d input pixels (sides that are no multiples of 32)", who, i,
+                 o.d.kind == RTPE_OP_DECONV ? "transposed conv" : o.fuse ? "fused BasicBlock pair" : "grouped stride-2 conv", H, W);
+    if (o.d.kind == RTPE_OP_FUSE) {
+      const rtpe_tensor_desc& to = h->tensors[o.d.out_t];
+      RTPE_REQUIRE(fuse_nearest_supports(N, extent(H, to.ds_log2), extent(W, to.ds_log2), o.d.cout, (o.d.flags & RTPE_F_F32) ? 1 : 0),
+                   "%s: op %zu: a fuse sum of %d x %d x %d is too large for the nearest-to-size sampler", who, i, N,
+                   extent(H, to.ds_log2), extent(W, to.ds_log2));
+    }
+  }
+  return RTPE_OK;
+}
+
 extern "C" int rtpe_hrnet_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, size_t* bytes) {
-  RTPE_REQUIRE(h && bytes && N > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0,
+  RTPE_REQUIRE(h && bytes && N > 0 && H > 0 && W > 0 && (h->any_size || !ragged(H, W)),
                "workspace_bytes: N=%d H=%d W=%d (H, W must be multiples of 32)", N, H, W);
   std::vector<size_t> offs;
   slot_layout(h, N, H, W, &offs, bytes);
@@ -505,6 +530,7 @@ extern "C" int rtpe_hrnet_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_
 // plane-major tensors of one run: the candidates all of whose ops run on the streaming kernel with the launch
 // shapes in force (tiny maps fall back to the generic kernel, which only knows NHWC)
 static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W, const std::vector<ConvTile>* tuned) {
+  if (ragged(H, W)) return std::vector<char>(h->plane_ok.size(), 0);   // (the streaming kernel, which alone knows the layout, is not used)
   std::vector<char> plane = h->plane_ok;
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const OpState& o = h->ops[i];
@@ -513,7 +539,7 @@ static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W,
     if (!(plane[d.in_t] || plane[d.out_t] || (d.res_t >= 0 && plane[d.res_t]))) continue;
     const rtpe_tensor_desc& ti = h->tensors[d.in_t];
     const ConvTile t = (tuned && (*tuned)[i * 4].nt) ? (*tuned)[i * 4]
-                                                      : conv_make_tile(o.plan[0], N, H >> ti.ds_log2, W >> ti.ds_log2);
+                                                      : conv_make_tile(o.plan[0], N, extent(H, ti.ds_log2), extent(W, ti.ds_log2));
     if (t.kind != 2) {
       plane[d.in_t] = plane[d.out_t] = 0;
       if (d.res_t >= 0) plane[d.res_t] = 0;
@@ -541,28 +567,41 @@ struct Fwd {
   size_t ws_need;
   const std::vector<ConvTile>* tuned = nullptr;
   std::vector<char> plane;
+  bool rag;                 // a ragged shape: general paths, default launch shapes (nothing is tuned at such a shape)
   Fwd(const rtpe_hrnet* h_, int N_, int H_, int W_, void* ws, void* preds_, void* refined_, int out_dtype_)
-      : h(h_), N(N_), H(H_), W(W_), base(reinterpret_cast<char*>(ws)), preds(preds_), refined(refined_), out_dtype(out_dtype_) {
+      : h(h_), N(N_), H(H_), W(W_), base(reinterpret_cast<char*>(ws)), preds(preds_), refined(refined_), out_dtype(out_dtype_), rag(ragged(H_, W_)) {
     slot_layout(h, N, H, W, &offs, &ws_need);
     auto it = h->tuned.find(std::make_tuple(N, H, W));
-    if (it != h->tuned.end()) tuned = &it->second;
+    if (it != h->tuned.end() && !rag) tuned = &it->second;
     plane = plane_tensors(h, N, H, W, tuned);
   }
   size_t esz(int t) const { return h->tensors[t].reserved == 4 ? 4 : 2; }
   _Float16* tptr(int t, int coff) const {      // element type per tensor (fp16 or fp32): byte arithmetic
     return reinterpret_cast<_Float16*>(base + offs[h->tensors[t].slot] + (size_t)coff * esz(t));
   }
-  ConvTile tile(size_t i, int k, int H_pos, int W_pos) const {   // tuned, else the default
+  ConvTile tile(size_t i, int k, int H_pos, int W_pos) const {   // tuned, else the default; ragged: the kernel that takes every shape
+    if (rag) return conv_make_tile(h->ops[i].plan[k], N, H_pos, W_pos, /*allow_direct=*/false, /*allow_conv64=*/false, /*allow_stream=*/false);
     return tuned && (*tuned)[i * 4 + k].nt ? (*tuned)[i * 4 + k] : conv_make_tile(h->ops[i].plan[k], N, H_pos, W_pos);
   }
 };
 
 extern "C" int rtpe_hrnet_plane_major_tensors(const rtpe_hrnet* h, int32_t N, int32_t H, int32_t W, int32_t* count) {
   RTPE_REQUIRE(h != nullptr && count != nullptr, "plane_major_tensors: null argument");
+  {
+    const int rc = check_shape(h, N, H, W, "plane_major_tensors");
+    if (rc != RTPE_OK) return rc;
+  }
   const Fwd f(h, N, H, W, nullptr, nullptr, nullptr, RTPE_DTYPE_F32);
   *count = 0;
   for (char c : f.plane) *count += c;
   return RTPE_OK;
+}
+
+// the grid of output positions of conv op i per side: the input map of a transposed conv (one launch class per sub-pixel), else the
+// extent of the output, one stride-2 step below the input's (= the input's extent / stride for multiples of 32; ceil otherwise)
+static int conv_pos(const rtpe_hrnet* h, const rtpe_op_desc& d, int n) {
+  const int ds = h->tensors[d.in_t].ds_log2;
+  return extent(n, d.kind == RTPE_OP_DECONV || d.stride != 2 ? ds : ds + 1);
 }
 
 // argument block of parity class k of conv op i: pointers, sizes and flags (the launch shape's half is conv_fill_args')
@@ -571,9 +610,9 @@ static ConvArgs conv_op_args(const Fwd& f, size_t i, int k) {
   const OpState& o = h->ops[i];
   const rtpe_op_desc& d = o.d;
   const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-  const int N = f.N, Hi = f.H >> ti.ds_log2, Wi = f.W >> ti.ds_log2;
+  const int N = f.N, Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
   const bool dc = d.kind == RTPE_OP_DECONV;
-  const int Ho = dc ? Hi * 2 : Hi / d.stride, Wo = dc ? Wi * 2 : Wi / d.stride;
+  const int Ho = dc ? Hi * 2 : conv_pos(h, d, f.H), Wo = dc ? Wi * 2 : conv_pos(h, d, f.W);
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.x = f.tptr(d.in_t, d.in_coff);
@@ -701,7 +740,7 @@ static int route_ops(const Fwd& f, std::vector<Route>* routes, std::vector<ConvA
     auto absorb = [&](size_t j) { (*routes)[j].how = kRouteDoneBy; (*routes)[j].by = (int)i; };
     if (r.how == kRouteDoneBy) continue;
     if (d.kind == RTPE_OP_STEM) {
-      const int fused = stem_fused_supports(f.H, f.W) ? opt.fused_stem : 0;
+      const int fused = !f.rag && stem_fused_supports(f.H, f.W) ? opt.fused_stem : 0;
       r.how = fused == 1 && o.stem2 == 1 ? kRouteStemFused : fused == 2 && !(d.flags & RTPE_F_F32) ? kRouteStemConv1 : kRouteStemPlain;
       if (r.how == kRouteStemFused) absorb(i + 1);
       continue;
@@ -710,17 +749,22 @@ static int route_ops(const Fwd& f, std::vector<Route>* routes, std::vector<ConvA
     if (d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))
       RTPE_REQUIRE(((d.flags & RTPE_F_OUT_REFINED) ? f.refined : f.preds) != nullptr, "forward: output pointer missing");
     const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-    const int Hi = f.H >> ti.ds_log2, Wi = f.W >> ti.ds_log2;
+    const int Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
     const bool dc = d.kind == RTPE_OP_DECONV;
     // a flagged BasicBlock pair runs as one kernel from 6 x 16 maps up; a smaller map runs both convs on their own.  (A fused
     // kernel for the 96-channel branch was built and measured in round 5 - slower than the two streaming launches:
     // profiles/r05_block96_ablation.txt, tools/experiments/conv_block96.hip.)
-    if (o.fuse == 1 && conv_block_supports(d.cin, d.cout, Hi, Wi)) {
+    if (o.fuse == 1 && conv_block_supports(d.cin, d.cout, Hi, Wi)) {     // (never at a ragged shape: check_shape)
       r.how = kRouteBlock;
       absorb(i + 1);
       continue;
     }
-    for (int k = 0; k < o.n_geom; ++k) r.tile[k] = f.tile(i, k, dc ? Hi : Hi / d.stride, dc ? Wi : Wi / d.stride);
+    for (int k = 0; k < o.n_geom; ++k) r.tile[k] = f.tile(i, k, conv_pos(h, d, f.H), conv_pos(h, d, f.W));
+    if (f.rag) {       // every conv on the one-workgroup-per-tile kernel, which masks its reads and stores at every edge
+      (*args)[i] = conv_op_args(f, i, 0, r.tile[0]);
+      r.how = kRouteTile;
+      continue;
+    }
     if (dc && deconv_merges(o.plan, r.tile[0])) {
       (*args)[i] = deconv_merged_args(f, i, r.tile[0]);
       r.how = deconv_pick(opt, o.plan[0], (*args)[i]);
@@ -855,20 +899,24 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
   // the call (the stream and every buffer must belong to it) and give the caller's device back afterwards
   DeviceGuard guard(h->device);
   RTPE_HIP_CHECK(guard.err);
-  RTPE_REQUIRE(N > 0 && H % 32 == 0 && W % 32 == 0 && H >= 32 && W >= 32, "forward: N=%d H=%d W=%d", N, H, W);
+  {
+    const int rc = check_shape(h, N, H, W, "forward");
+    if (rc != RTPE_OK) return rc;
+  }
   RTPE_REQUIRE(x_dtype == RTPE_DTYPE_F16 || x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
   RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F16 || out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
   const Fwd f(h, N, H, W, ws, preds, refined, out_dtype);
   if (f.ws_need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, f.ws_need); return RTPE_E_NOMEM; }
   RTPE_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
   // Shapes an op cannot take are refused here, before the first launch, so that no half-run forward is left behind.
-  // avgpool: the kernel writes ceil(Hi / 2) x ceil(Wi / 2) pixels, the output tensor holds (H >> ds) x (W >> ds): a map
-  // with an odd side (1 x 1, 2 x 1) would be written beyond its tensor
+  // avgpool: the kernel writes ceil(Hi / 2) x ceil(Wi / 2) pixels, the output tensor holds extent(H, ds) x extent(W, ds): a
+  // map with an odd side (1 x 1, 2 x 1) of an input that is a multiple of 32 would be written beyond its tensor (a ragged
+  // input's tensors hold the ceil)
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const rtpe_op_desc& d = h->ops[i].d;
     if (d.kind != RTPE_OP_AVGPOOL) continue;
-    const int Hi = H >> h->tensors[d.in_t].ds_log2, Wi = W >> h->tensors[d.in_t].ds_log2;
-    const int Ho = H >> h->tensors[d.out_t].ds_log2, Wo = W >> h->tensors[d.out_t].ds_log2;
+    const int Hi = extent(H, h->tensors[d.in_t].ds_log2), Wi = extent(W, h->tensors[d.in_t].ds_log2);
+    const int Ho = extent(H, h->tensors[d.out_t].ds_log2), Wo = extent(W, h->tensors[d.out_t].ds_log2);
     RTPE_REQUIRE((Hi + 1) / 2 == Ho && (Wi + 1) / 2 == Wo,
                  "avgpool: a %d x %d map does not pool into the %d x %d output tensor", Hi, Wi, Ho, Wo);
   }
@@ -996,7 +1044,7 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
       }
       case kRouteBlock: {
         const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-        const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
+        const int Hi = extent(H, ti.ds_log2), Wi = extent(W, ti.ds_log2);
         const OpState& o2 = h->ops[i + 1];
         RTPE_HP_LAUNCH(rc = conv_block_launch(tptr(d.in_t, d.in_coff), ti.channels,
                                ((size_t)N * Hi * Wi * ti.channels - (size_t)d.in_coff) * 2,
@@ -1033,17 +1081,17 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           if (aux == nullptr) { set_error("forward: this program has a second input (use rtpe_hrnet_forward_aux)"); return RTPE_E_INVALID; }
           const rtpe_tensor_desc& to = h->tensors[d.out_t];
           rc = aux_pack_launch(reinterpret_cast<const float*>(aux), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)),
-                               to.channels, N, H >> to.ds_log2, W >> to.ds_log2, s);
+                               to.channels, N, extent(H, to.ds_log2), extent(W, to.ds_log2), s);
         } else if (d.kind == RTPE_OP_RESIZE) {
           const rtpe_tensor_desc& ti = h->tensors[d.in_t];
           const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          rc = resize_nhwc_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, H >> ti.ds_log2,
-                                  W >> ti.ds_log2, reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels,
-                                  H >> to.ds_log2, W >> to.ds_log2, d.cout, N, s);
+          rc = resize_nhwc_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, extent(H, ti.ds_log2),
+                                  extent(W, ti.ds_log2), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels,
+                                  extent(H, to.ds_log2), extent(W, to.ds_log2), d.cout, N, s);
         } else if (d.kind == RTPE_OP_GATE_MUL) {
           const rtpe_tensor_desc& ti = h->tensors[d.in_t];
           const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          const size_t pixels = (size_t)N * (H >> ti.ds_log2) * (W >> ti.ds_log2);
+          const size_t pixels = (size_t)N * extent(H, ti.ds_log2) * extent(W, ti.ds_log2);
           float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
           if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
             set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
@@ -1057,7 +1105,7 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
                    d.kind == RTPE_OP_CAM_COMBINE || d.kind == RTPE_OP_SIGMOID_ADD) {
           const rtpe_tensor_desc& ti = h->tensors[d.in_t];
           const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
+          const int Hi = extent(H, ti.ds_log2), Wi = extent(W, ti.ds_log2);
           const size_t pixels = (size_t)N * Hi * Wi;
           float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
           if (d.kind == RTPE_OP_CAST) {
@@ -1094,7 +1142,12 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           }
           a.y = tptr(d.out_t, d.out_coff);
           a.out_ld = to.channels; a.C = d.cout;
-          a.N = N; a.H = H >> to.ds_log2; a.W = W >> to.ds_log2;
+          a.N = N; a.H = extent(H, to.ds_log2); a.W = extent(W, to.ds_log2);
+          a.nearest = f.rag ? 1 : 0;
+          for (int t = 0; t < d.n_terms; ++t) {
+            a.term_h[t] = extent(H, h->tensors[d.term_t[t]].ds_log2);
+            a.term_w[t] = extent(W, h->tensors[d.term_t[t]].ds_log2);
+          }
           a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
           a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
           RTPE_HP_LAUNCH(rc = fuse_launch(a, s));
@@ -1172,7 +1225,7 @@ extern "C" int rtpe_hrnet_op_cost(const rtpe_hrnet* h, int32_t op, int32_t N, in
   *flops = 0; *bytes = 0;
   if (d.kind == RTPE_OP_FUSE) {
     const rtpe_tensor_desc& to = h->tensors[d.out_t];
-    const double px = (double)N * (H >> to.ds_log2) * (W >> to.ds_log2);
+    const double px = (double)N * extent(H, to.ds_log2) * extent(W, to.ds_log2);
     *bytes = px * d.cout * 2;
     for (int t = 0; t < d.n_terms; ++t) *bytes += px / (double)(1 << (2 * d.term_up[t])) * d.cout * 2;
     return RTPE_OK;
@@ -1180,25 +1233,44 @@ extern "C" int rtpe_hrnet_op_cost(const rtpe_hrnet* h, int32_t op, int32_t N, in
   const int cin_logical = d.reserved[0] > 0 ? d.reserved[0] : d.cin;
   if (d.kind >= RTPE_OP_CAST) {                      // small fp32 student ops: bytes only
     const rtpe_tensor_desc& ti = h->tensors[d.kind == RTPE_OP_AUX_PACK ? d.out_t : d.in_t];
-    const double px = (double)N * (H >> ti.ds_log2) * (W >> ti.ds_log2);
+    const double px = (double)N * extent(H, ti.ds_log2) * extent(W, ti.ds_log2);
     *bytes = px * ti.channels * 4 * 2;
     return RTPE_OK;
   }
   if (d.kind == RTPE_OP_STEM) {
-    const double po = (double)N * (H / 2) * (W / 2);
+    const double po = (double)N * extent(H, 1) * extent(W, 1);
     *flops = 2.0 * po * 64 * 27;
     *bytes = (double)N * 3 * H * W * 4 + po * 64 * 2;
     return RTPE_OK;
   }
   const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-  const double pi = (double)N * (H >> ti.ds_log2) * (W >> ti.ds_log2);
+  const double pi = (double)N * extent(H, ti.ds_log2) * extent(W, ti.ds_log2);
   const bool dc = d.kind == RTPE_OP_DECONV;
-  const double po = dc ? pi * 4 : pi / (d.stride * d.stride);
+  const double po = dc ? pi * 4 : (double)N * conv_pos(h, d, H) * conv_pos(h, d, W);
   const double taps = dc ? 4 : d.ksize * d.ksize;
   const double es = (d.flags & RTPE_F_F32) ? 4.0 : 2.0;       // bytes per element of this op's tensors
   *flops = 2.0 * po * d.cout * cin_logical * taps;
   *bytes = pi * cin_logical * es + po * d.cout * es + (d.res_t >= 0 ? po * d.cout * es : 0) +
            (double)cin_logical * d.cout * d.ksize * d.ksize * es;
+  return RTPE_OK;
+}
+
+// ---- ragged shapes (include/rtpe_hip_anysize.h) ----------------------------
+extern "C" int32_t rtpe_extent(int32_t n, int32_t ds_log2) { return n > 0 && ds_log2 >= 0 && ds_log2 < 31 ? extent(n, ds_log2) : 0; }
+
+extern "C" int32_t rtpe_nearest_src(int32_t dst, int32_t n_in, int32_t n_out) {
+  return dst >= 0 && n_in > 0 && dst < n_out ? nearest_src(dst, n_in, (float)n_in / (float)n_out) : -1;
+}
+
+extern "C" int rtpe_hrnet_set_any_size(rtpe_hrnet* h, int32_t on) {
+  RTPE_REQUIRE(h != nullptr && (on == 0 || on == 1), "set_any_size: bad argument");
+  h->any_size = on != 0;
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_hrnet_get_any_size(const rtpe_hrnet* h, int32_t* on) {
+  RTPE_REQUIRE(h != nullptr && on != nullptr, "get_any_size: null argument");
+  *on = h->any_size ? 1 : 0;
   return RTPE_OK;
 }
 
@@ -1462,6 +1534,10 @@ extern "C" int rtpe_conv2d_nhwc(const void* x, int32_t N, int32_t H, int32_t W, 
 // binds a workspace, fp32 `preds` and `refined` (nominal, suitably aligned addresses: nothing is dereferenced)
 extern "C" int rtpe_hrnet_op_tile(const rtpe_hrnet* h, int32_t op, int32_t N, int32_t H, int32_t W, int32_t* out8) {
   RTPE_REQUIRE(h && out8 && op >= 0 && op < (int)h->ops.size(), "op_tile: bad argument");
+  {
+    const int rc = check_shape(h, N, H, W, "op_tile");
+    if (rc != RTPE_OK) return rc;
+  }
   const Fwd f(h, N, H, W, reinterpret_cast<void*>(256), reinterpret_cast<void*>(256), reinterpret_cast<void*>(256), RTPE_DTYPE_F32);
   std::vector<Route> routes;
   std::vector<ConvArgs> args;
@@ -1481,6 +1557,8 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
                          void* preds, void* refined, int32_t out_dtype, void* workspace, size_t workspace_bytes,
                          void* stream) {
   RTPE_REQUIRE(h != nullptr, "autotune: null handle");
+  // a stream of native-size images has hundreds of shapes: ragged ones run on the default launch shapes and are never tuned
+  RTPE_REQUIRE(!ragged(H, W), "autotune: N=%d H=%d W=%d: shapes with a side that is no multiple of 32 are not tuned", N, H, W);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const auto shape = std::make_tuple(N, H, W);
   h->tuned.erase(shape);
@@ -1508,9 +1586,7 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
                                     (int)d.reserved[1] /* dilation: sets the halo */, (int)d.reserved[2]);
     Class& c = classes[key];
     if (c.ops.empty()) {
-      const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-      const bool dc = d.kind == RTPE_OP_DECONV;
-      const int Hp = dc ? Hi : Hi / d.stride, Wp = dc ? Wi : Wi / d.stride;
+      const int Hp = conv_pos(h, d, H), Wp = conv_pos(h, d, W);
       c.cands.resize(o.n_geom);
       for (int k = 0; k < o.n_geom; ++k) conv_enum_tiles(o.plan[k], N, Hp, Wp, &c.cands[k]);
       size_t nc = c.cands[0].size();
@@ -1641,10 +1717,7 @@ extern "C" int rtpe_hrnet_import_tuned(rtpe_hrnet* h, int32_t N, int32_t H, int3
       const int32_t* r = in + (i * 4 + k) * RTPE_TUNED_INTS;
       if (r[0] == 0) continue;
       RTPE_REQUIRE(k < o.n_geom, "import_tuned: op %zu has no launch shape %d", i, k);
-      const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-      const int Hi = H >> ti.ds_log2, Wi = W >> ti.ds_log2;
-      const bool dc = d.kind == RTPE_OP_DECONV;
-      conv_enum_tiles(o.plan[k], N, dc ? Hi : Hi / d.stride, dc ? Wi : Wi / d.stride, &cands);
+      conv_enum_tiles(o.plan[k], N, conv_pos(h, d, H), conv_pos(h, d, W), &cands);
       bool found = false;
       for (const ConvTile& c : cands) {
         if (c.nt == r[0] && c.waves == r[1] && c.th == r[2] && c.tw == r[3] && (int32_t)c.lds_bytes == r[4] &&

@@ -75,6 +75,20 @@ struct DeviceGuard {
   }
 };
 
+// Extent rule: pixels along a side of n input pixels of a tensor at 1 / 2^ds (rtpe_tensor_desc::ds_log2 >= 0).  A side that
+// is no multiple of 32 (programs with the any_size property only, include/rtpe_hip_anysize.h) leaves ceil(n / 2^ds): every
+// stride-2 conv with padding k / 2 and AvgPool2d(3, 2, 1) gives ceil(n / 2).  The two branches agree for ds <= 5; the old
+// one is kept for multiples of 32 so that such an input still has NO pixel at ds = 6 (a 2 x 1 map at ds = 5 pools into a
+// tensor that holds nothing: the forward refuses it instead of writing a pixel that no tensor has room for)
+inline int extent(int n, int ds) { return n % 32 != 0 ? (n + (1 << ds) - 1) >> ds : n >> ds; }
+inline bool ragged(int H, int W) { return H % 32 != 0 || W % 32 != 0; }
+
+// F.interpolate(mode="nearest", size=...) of PyTorch-CPU (nearest_neighbor_compute_source_index): one fp32 product
+__host__ __device__ inline int nearest_src(int dst, int n_in, float scale) {
+  const int s = (int)floorf((float)dst * scale);
+  return s < n_in - 1 ? s : n_in - 1;
+}
+
 // exact unsigned division by a runtime constant: q = umulhi(n, mul) for
 // n * d < 2^32 (all uses here: n < 2^20, d < 2^12)
 struct FastDiv {
@@ -209,7 +223,9 @@ ConvPlan conv_make_plan(const ConvGeom& g);
 // choose the tile for a position grid (N images of H_pos x W_pos positions)
 // (allow_direct = false: never the direct 1x1 kernel, whose launch needs a < 2 GiB input view and a plain NHWC output)
 // (allow_conv64 = false: never the persistent 64 -> 64 kernel, which takes no residual and writes plain NHWC rows)
-ConvTile conv_make_tile(const ConvPlan& p, int N, int H_pos, int W_pos, bool allow_direct = true, bool allow_conv64 = true);
+// (allow_stream = false: never the streaming kernel either - the one-workgroup-per-tile kernel, which takes every shape)
+ConvTile conv_make_tile(const ConvPlan& p, int N, int H_pos, int W_pos, bool allow_direct = true, bool allow_conv64 = true,
+                        bool allow_stream = true);
 // LDS bytes per row of the staged input tile of a tw-wide output tile: halo_w * pstride, padded (fp16) so that a
 // 16-pixel MFMA column tile which wraps to the next output row keeps the bank pattern of consecutive pixels
 int conv_row_pitch(const ConvPlan& p, int tw, int kind);
@@ -265,8 +281,13 @@ struct FuseArgs {
   int N, H, W;  // output spatial size
   int f32;      // 1: fp32 tensors (pointers are reinterpreted), 0: fp16
   int relu;     // final ReLU (HighResolutionModule) or plain sum (student heads)
+  // nearest = 1 (ragged shapes of any_size programs): term t holds term_h[t] x term_w[t] pixels and is read with PyTorch-CPU's
+  // nearest-to-size rule (nearest_src) instead of the shift by term_up[t]
+  int nearest;
+  int term_h[4], term_w[4];
 };
 int fuse_launch(const FuseArgs& a, hipStream_t s);
+bool fuse_nearest_supports(int N, int H, int W, int C, int f32);
 
 struct StemArgs {
   const void* x;  // NCHW (N,3,H,W), fp32 or fp16

@@ -233,6 +233,15 @@ _SIGS_NOPROJ = {
     "rtpe_adjust_refine_ms_np_n": (c_int32, _a[:8] + _a[10:] + [c_void_p]),
 }
 EXPORTS_NOPROJ = tuple(_SIGS_NOPROJ)    # those of include/rtpe_hip_noproj.h, likewise
+# inputs whose sides are not multiples of 32 (include/rtpe_hip_anysize.h): the extent rule, the nearest-to-size index rule
+# and the property of a handle that lets it take such shapes
+_SIGS_ANYSIZE = {
+    "rtpe_extent": (c_int32, [c_int32, c_int32]),
+    "rtpe_nearest_src": (c_int32, [c_int32, c_int32, c_int32]),
+    "rtpe_hrnet_set_any_size": (c_int32, [c_void_p, c_int32]),
+    "rtpe_hrnet_get_any_size": (c_int32, [c_void_p, POINTER(c_int32)]),
+}
+EXPORTS_ANYSIZE = tuple(_SIGS_ANYSIZE)  # those of include/rtpe_hip_anysize.h, likewise
 _lib = None
 
 
@@ -256,7 +265,7 @@ def lib():
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
-                list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()):
+                list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()
@@ -265,6 +274,30 @@ def lib():
                                "(`python -c \"import __graft_entry__ as g; g.build()\"`)" % (LIB_PATH, got, ABI_VERSION))
         _lib = L
     return _lib
+
+
+def extent(n, ds):
+    """pixels along a side of ``n`` input pixels of a tensor at 1 / 2^ds (csrc/rtpe_common.h ``extent``, the same rule):
+    ``n >> ds`` for a multiple of 32, as ever; otherwise ``ceil(n / 2^ds)``, what ``ds`` stride-2 convs with padding k // 2
+    or ``AvgPool2d(3, 2, 1)`` leave.  The two branches agree for ds <= 5; the first keeps a 32-wide input at ds = 6 a tensor
+    without pixels, which the avgpool op refuses to pool into."""
+    n, ds = int(n), int(ds)
+    return (n + (1 << ds) - 1) >> ds if n % 32 else n >> ds
+
+
+def ragged(H, W):
+    """a side that is no multiple of 32: only programs with ``any_size`` take such an input"""
+    return bool(int(H) % 32 or int(W) % 32)
+
+
+def nearest_src(dst, n_in, n_out):
+    """source index of ``F.interpolate(mode="nearest", size=n_out)`` on PyTorch-CPU, the rule of the fuse op at ragged
+    shapes (csrc/rtpe_common.h ``nearest_src``): ``min(int(floorf(dst * scale)), n_in - 1)`` with the fp32 scale
+    ``float(n_in) / float(n_out)`` and an fp32 product.  ``dst``: an int or an integer array."""
+    import numpy as np
+    scale = np.float32(n_in) / np.float32(n_out)
+    src = np.floor(np.asarray(dst, np.float32) * scale).astype(np.int64)
+    return np.minimum(src, n_in - 1)
 
 
 def check(rc):

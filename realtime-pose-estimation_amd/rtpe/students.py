@@ -210,7 +210,7 @@ class AttentionStudent(CompiledModule):
     def compile_program(self):
         """the forward of reference :724-771 as one program"""
         half = isinstance(self.stem[0], tofp16)
-        b = ProgramBuilder(f32=not half)
+        b = ProgramBuilder(f32=not half, any_size=True)
         t = self.stem[1].emit(b)
         if half:
             t = b.cast(t)                                   # tofp32 of the wrapped stem
@@ -233,9 +233,18 @@ class AttentionStudent(CompiledModule):
         return b.finish()
 
     def forward(self, x, out_hw=None, return_intermediate=False):
-        """x (N,3,H,W) fp32 on the GPU, H and W multiples of 32 -> (att (N,1,H/4,W/4) = sigmoid mask,
-        det (N,num_heatmaps+ae_dims,H/4,W/4)), both fp32.  ``out_hw`` and
-        ``return_intermediate`` are accepted and unused, as in the reference."""
+        """x (N,3,H,W) fp32 on the GPU, any H, W >= 32 -> (att (N,1,ceil(H/4),ceil(W/4)) = sigmoid mask,
+        det (N,num_heatmaps+ae_dims,ceil(H/4),ceil(W/4))), both fp32.  ``out_hw`` and
+        ``return_intermediate`` are accepted and unused, as in the reference.
+
+        Sizes.  As in the reference every map is ``ceil(n / 2^d)`` wide (the stride-2 convs and ``AvgPool2d(3, 2, 1)``),
+        and the low-resolution terms of the two heads are brought to the stem's size with
+        ``F.interpolate(mode="nearest", size=...)``'s index rule.  Inputs whose sides are both multiples of 32 run the
+        tuned fast kernels (the first forward of a new (N, H, W) autotunes its launch shapes).  Any other size runs the
+        general kernels - every conv on the one-workgroup-per-tile kernel, the stem on the VALU kernel - with their
+        default launch shapes and is never autotuned: a stream of native-size images has hundreds of shapes.  The
+        throughput at such sizes has not been measured.  Activation workspaces are cached per shape within
+        ``RTPE_WS_CACHE_MB``, least recently used dropped."""
         self._check_inference(x, "AttentionStudent.forward")
         att, det = self._engine(x.device).forward(x.float(), torch.float32)
         return att, det
@@ -308,7 +317,7 @@ class AttentionStudentSteps(CompiledModule):
         att_divisor = variant[1] if variant else None
         half = isinstance(self.stem[0], tofp16)
         P = self.inplanes
-        b = ProgramBuilder(f32=not half)
+        b = ProgramBuilder(f32=not half, any_size=True)
         t = self.stem[1].emit(b)
         if half:
             t = b.cast(t)
@@ -341,8 +350,11 @@ class AttentionStudentSteps(CompiledModule):
         return b.finish()
 
     def forward(self, x, out_hw=None, alt=None, att_divisor=None):
-        """x (N,3,H,W) fp32 on the GPU (H, W multiples of 32), alt (N,3,H,W) fp32: the image in the alternative
-        colour space -> (att (N,1,H/4,W/4) = sigmoid mask, det (N,num_heatmaps+ae_dims,H/4,W/4)), both fp32"""
+        """x (N,3,H,W) fp32 on the GPU (any H, W >= 32), alt (N,3,H,W) fp32: the image in the alternative
+        colour space -> (att (N,1,ceil(H/4),ceil(W/4)) = sigmoid mask, det (N,num_heatmaps+ae_dims,ceil(H/4),ceil(W/4))),
+        both fp32.  Sizes, kernels and tuning: as for ``AttentionStudent.forward`` - multiples of 32 run the tuned fast
+        kernels; any other size runs the general kernels on default launch shapes, is never autotuned, and its
+        throughput has not been measured."""
         self._check_inference(x, "AttentionStudentSteps.forward")
         if alt is None:
             raise NotImplementedError("ATM alt is expected")        # reference :993-994
