@@ -920,6 +920,34 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
     RTPE_REQUIRE((Hi + 1) / 2 == Ho && (Wi + 1) / 2 == Wo,
                  "avgpool: a %d x %d map does not pool into the %d x %d output tensor", Hi, Wi, Ho, Wo);
   }
+  // the fp16 forms of avgpool, se, cam_combine and sigmoid_add (an op of these kinds without RTPE_F_F32: the half body of
+  // AttentionStudent) move rows in 16-byte pieces of 8 halves: every tensor they touch is an fp16 tensor whose row, channel
+  // offset and channel count are multiples of 8; the SE limits are those of the fp32 form
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    const rtpe_op_desc& d = h->ops[i].d;
+    if ((d.flags & RTPE_F_F32) || (d.kind != RTPE_OP_AVGPOOL && d.kind != RTPE_OP_SE && d.kind != RTPE_OP_CAM_COMBINE &&
+                                   d.kind != RTPE_OP_SIGMOID_ADD)) continue;
+    const int ts[4] = {d.in_t, d.out_t, d.kind == RTPE_OP_SE || d.kind == RTPE_OP_AVGPOOL ? -1 : d.res_t,
+                       d.kind == RTPE_OP_CAM_COMBINE ? d.term_t[0] : -1};
+    for (int k = 0; k < 4; ++k) {
+      if (ts[k] < 0) continue;
+      const rtpe_tensor_desc& t = h->tensors[ts[k]];
+      const bool row = k == 0 && d.kind == RTPE_OP_SIGMOID_ADD;     // (the logits: one half per pixel is read, any row will do)
+      RTPE_REQUIRE(t.reserved != 4 && (row || t.channels % 8 == 0), "op %zu: the fp16 form of this op needs fp16 tensors with rows of a "
+                   "multiple of 8 channels (tensor %d: %d channels of %d bytes)", i, ts[k], t.channels, t.reserved == 4 ? 4 : 2);
+      const int coff = k == 0 ? d.in_coff : k == 1 ? d.out_coff : k == 2 ? d.res_coff : 0;
+      RTPE_REQUIRE(row || d.kind == RTPE_OP_SE || (coff >= 0 && coff + d.cout <= t.channels),
+                   "op %zu: channels [%d, %d) do not fit tensor %d of %d channels", i, coff, coff + d.cout, ts[k], t.channels);
+    }
+    RTPE_REQUIRE(d.in_coff % 8 == 0 && d.out_coff % 8 == 0 && d.res_coff % 8 == 0, "op %zu: channel offsets must be multiples of 8", i);
+    if (d.kind == RTPE_OP_SE) {
+      RTPE_REQUIRE(d.cin > 0 && d.cout > 0 && d.cin <= 512 && d.cout <= 128, "se: C=%d hidden=%d unsupported", d.cin, d.cout);
+      RTPE_REQUIRE(h->tensors[d.in_t].channels >= (d.cin + 7) / 8 * 8 && h->tensors[d.out_t].channels >= d.cin,
+                   "se: rows of %d and %d halves for C=%d", h->tensors[d.in_t].channels, h->tensors[d.out_t].channels, d.cin);
+    } else {
+      RTPE_REQUIRE(d.cout > 0 && d.cout % 8 == 0, "op %zu: the fp16 form of this op needs a channel count that is a multiple of 8 (%d)", i, d.cout);
+    }
+  }
   std::vector<Route> routes;
   std::vector<ConvArgs> args;
   {
@@ -1108,8 +1136,25 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           const int Hi = extent(H, ti.ds_log2), Wi = extent(W, ti.ds_log2);
           const size_t pixels = (size_t)N * Hi * Wi;
           float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
+          const bool h16 = !(d.flags & RTPE_F_F32) && d.kind != RTPE_OP_CAST;    // the fp16 forms (checked before the first launch)
+          float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
+          if (d.kind == RTPE_OP_SIGMOID_ADD && (d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
+            set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
+          }
           if (d.kind == RTPE_OP_CAST) {
             rc = cast_launch(tptr(d.in_t, d.in_coff), ti.channels, yo, to.channels, d.cout, pixels, s);
+          } else if (h16 && d.kind == RTPE_OP_AVGPOOL) {
+            rc = avgpool_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.out_t, d.out_coff), to.channels, d.cout, N, Hi, Wi, s);
+          } else if (h16 && d.kind == RTPE_OP_SE) {
+            rc = se_launch(tptr(d.in_t, d.in_coff), ti.channels, d.cin, d.cout, N, Hi * Wi,
+                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), tptr(d.out_t, d.out_coff), to.channels, s);
+          } else if (h16 && d.kind == RTPE_OP_CAM_COMBINE) {
+            rc = cam_combine_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.res_t, d.res_coff), h->tensors[d.res_t].channels,
+                                    tptr(d.term_t[0], 0), h->tensors[d.term_t[0]].channels, tptr(d.out_t, d.out_coff),
+                                    to.channels, d.cout, N, (size_t)Hi * Wi, s);
+          } else if (h16) {
+            rc = sigmoid_add_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.res_t, d.res_coff), h->tensors[d.res_t].channels,
+                                    tptr(d.out_t, d.out_coff), to.channels, d.cout, pixels, att_out, s);
           } else if (d.kind == RTPE_OP_AVGPOOL) {
             rc = avgpool_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, yo, to.channels,
                                 d.cout, N, Hi, Wi, s);
@@ -1122,10 +1167,6 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
                                     reinterpret_cast<const float*>(tptr(d.term_t[0], 0)), h->tensors[d.term_t[0]].channels,
                                     yo, to.channels, d.cout, N, (size_t)Hi * Wi, s);
           } else {
-            float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
-            if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
-              set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
-            }
             rc = sigmoid_add_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
                                     reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
                                     yo, to.channels, d.cout, pixels, att_out, s);
@@ -1231,10 +1272,10 @@ extern "C" int rtpe_hrnet_op_cost(const rtpe_hrnet* h, int32_t op, int32_t N, in
     return RTPE_OK;
   }
   const int cin_logical = d.reserved[0] > 0 ? d.reserved[0] : d.cin;
-  if (d.kind >= RTPE_OP_CAST) {                      // small fp32 student ops: bytes only
+  if (d.kind >= RTPE_OP_CAST) {                      // small student ops: bytes only
     const rtpe_tensor_desc& ti = h->tensors[d.kind == RTPE_OP_AUX_PACK ? d.out_t : d.in_t];
     const double px = (double)N * extent(H, ti.ds_log2) * extent(W, ti.ds_log2);
-    *bytes = px * ti.channels * 4 * 2;
+    *bytes = px * ti.channels * ((d.flags & RTPE_F_F32) ? 4 : 2) * 2;
     return RTPE_OK;
   }
   if (d.kind == RTPE_OP_STEM) {

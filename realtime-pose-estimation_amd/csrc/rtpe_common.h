@@ -321,7 +321,7 @@ struct StemFusedArgs {
 bool stem_fused_supports(int H, int W);
 int stem_fused_launch(const StemFusedArgs& a, hipStream_t s);
 
-// ---- student ops (student_ops.hip), fp32 NHWC ------------------------------
+// ---- student ops (student_ops.hip), NHWC ------------------------------
 int cast_launch(const _Float16* x, int in_ld, float* y, int out_ld, int C, size_t pixels, hipStream_t s);
 int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s);
 int se_launch(const float* x, int in_ld, int C, int hid, int N, int HW, const float* w, float* gate, int gate_ld,
@@ -329,6 +329,15 @@ int se_launch(const float* x, int in_ld, int C, int hid, int N, int HW, const fl
 int cam_combine_launch(const float* hdc, int hdc_ld, const float* res, int res_ld, const float* gate, int gate_ld,
                        float* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s);
 int sigmoid_add_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C,
+                       size_t pixels, float* att_out, hipStream_t s);
+// the fp16 forms (the half body of AttentionStudent): rows of 8 channels per 16 bytes, fp32 arithmetic, fp16 roundings where
+// PyTorch-CPU's half ops have them; the SE weights stay fp32 values, att_out stays an fp32 map
+int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s);
+int se_launch(const _Float16* x, int in_ld, int C, int hid, int N, int HW, const float* w, _Float16* gate, int gate_ld,
+              hipStream_t s);
+int cam_combine_launch(const _Float16* hdc, int hdc_ld, const _Float16* res, int res_ld, const _Float16* gate, int gate_ld,
+                       _Float16* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s);
+int sigmoid_add_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C,
                        size_t pixels, float* att_out, hipStream_t s);
 // y = x * sigmoid(att / div) (div == 0: no division), channels [0, C) of a row
 int gate_mul_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C,

@@ -1,7 +1,8 @@
-// The small fp32 NHWC ops of the dual-head student (config 5: AttentionStudent,
+// The small NHWC ops of the dual-head student (config 5: AttentionStudent,
 // rtpe/students.py:595-771 of the reference, built from ContextAwareModule
 // :145-201 and SELayer :118-142).  All are single-pass, HBM/latency-bound;
-// channel counts are multiples of 4 (16-byte rows pieces).
+// channel counts are multiples of 4 (16-byte rows pieces).  avgpool, se, cam_combine and sigmoid_add also have an
+// fp16 form (the half body: 16-byte pieces of 8 channels).
 #include "rtpe_common.h"
 
 namespace rtpe {
@@ -21,20 +22,64 @@ __global__ void __launch_bounds__(256) cast_kernel(const _Float16* x, int in_ld,
   }
 }
 
+// The four ops below exist in two storage precisions, like the convs (conv_mfma.hip, Prec<T>): fp32 (float, 4 channels per
+// 16-byte access) and fp16 (_Float16, 8 channels per 16-byte access: the half body of AttentionStudent, body_half=True).
+// The arithmetic is fp32 in both; Elem<T>::rnd marks the points at which PyTorch-CPU's half ops round to fp16 (pinned by
+// tests/test_student_half_host.py) and is the identity for fp32, whose instantiations compute what they always did.
+template <typename T> struct Elem;
+template <> struct Elem<float> {
+  static constexpr int N = 4;
+  static __device__ __forceinline__ float rnd(float v) { return v; }
+};
+template <> struct Elem<_Float16> {
+  static constexpr int N = 8;
+  // (the fp32 value is kept opaque, as in conv_mfma.hip's epilogue: the compiler would fuse the operation before it with the
+  // conversion into one v_fma_mix*_f16, which rounds the exact result once where PyTorch rounds to fp32 and then to fp16)
+  static __device__ __forceinline__ float rnd(float v) {
+    asm volatile("" : "+v"(v));
+    return (float)(_Float16)v;
+  }
+};
+
+template <typename T> struct Row {           // 16 bytes of a channel row, as fp32 values
+  float v[Elem<T>::N];
+  static __device__ __forceinline__ Row load(const T* p) {
+    T raw[Elem<T>::N];
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    __builtin_memcpy(raw, &u, 16);
+    Row r;
+#pragma unroll
+    for (int j = 0; j < Elem<T>::N; ++j) r.v[j] = (float)raw[j];
+    return r;
+  }
+  __device__ __forceinline__ void store(T* p) const {   // (the values are representable in T: rounded by Elem<T>::rnd)
+    T raw[Elem<T>::N];
+#pragma unroll
+    for (int j = 0; j < Elem<T>::N; ++j) raw[j] = (T)v[j];
+    uint4 u;
+    __builtin_memcpy(&u, raw, 16);
+    *reinterpret_cast<uint4*>(p) = u;
+  }
+};
+
 // AvgPool2d(kernel_size=3, stride=2, padding=1, count_include_pad=False), students.py:657-666
-__global__ void __launch_bounds__(256) avgpool_kernel(const float* x, int in_ld, float* y, int out_ld, int C, int N,
-                                                      int H, int W) {
+// fp16: the window is summed and divided in fp32, one rounding (ATen's avg_pool2d accumulates a half input in float)
+template <typename T>
+__global__ void __launch_bounds__(256) avgpool_kernel(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W) {
+  constexpr int EN = Elem<T>::N;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const int c4 = C >> 2;
+  const int c4 = C / EN;
   const size_t total = (size_t)N * Ho * Wo * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c = (int)(i % c4) * 4;
+    const int c = (int)(i % c4) * EN;
     size_t p = i / c4;
     const int ox = (int)(p % Wo);
     p /= Wo;
     const int oy = (int)(p % Ho);
     const int n = (int)(p / Ho);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    Row<T> s;
+#pragma unroll
+    for (int j = 0; j < EN; ++j) s.v[j] = 0.f;
     int cnt = 0;
     for (int ky = 0; ky < 3; ++ky) {
       const int iy = 2 * oy - 1 + ky;
@@ -42,36 +87,65 @@ __global__ void __launch_bounds__(256) avgpool_kernel(const float* x, int in_ld,
       for (int kx = 0; kx < 3; ++kx) {
         const int ix = 2 * ox - 1 + kx;
         if ((unsigned)ix >= (unsigned)W) continue;
-        const float4 v = *reinterpret_cast<const float4*>(x + (((size_t)n * H + iy) * W + ix) * in_ld + c);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        const Row<T> v = Row<T>::load(x + (((size_t)n * H + iy) * W + ix) * in_ld + c);
+#pragma unroll
+        for (int j = 0; j < EN; ++j) s.v[j] += v.v[j];
         ++cnt;
       }
     }
     const float d = (float)cnt;
-    *reinterpret_cast<float4*>(y + (((size_t)n * Ho + oy) * Wo + ox) * out_ld + c) =
-        make_float4(s.x / d, s.y / d, s.z / d, s.w / d);
+#pragma unroll
+    for (int j = 0; j < EN; ++j) s.v[j] = Elem<T>::rnd(s.v[j] / d);
+    s.store(y + (((size_t)n * Ho + oy) * Wo + ox) * out_ld + c);
   }
 }
 
 // SELayer, students.py:137-142: gate[n, c] = sigmoid(W2 relu(W1 mean_hw(x) + b1) + b2)
-// one workgroup per image; w: fc1 (hid, C) | b1 (hid) | fc2 (C, hid) | b2 (C), fp32
+// one workgroup per image; w: fc1 (hid, C) | b1 (hid) | fc2 (C, hid) | b2 (C), fp32 (fp16: the values of the half parameters)
+// fp16 rounds the mean (an fp32 sum divided by HW), each Linear behind its bias, and the sigmoid
 constexpr int kSeMaxC = 512, kSeMaxHid = 128;
-__global__ void __launch_bounds__(256) se_kernel(const float* x, int in_ld, int C, int hid, int HW, const float* w,
-                                                 float* gate, int gate_ld) {
+template <typename T>
+__global__ void __launch_bounds__(256) se_kernel(const T* x, int in_ld, int C, int hid, int HW, const float* w, T* gate,
+                                                 int gate_ld) {
   __shared__ float mean[kSeMaxC];
-  __shared__ float part[4][kSeMaxC];
+  __shared__ float part[4 * kSeMaxC];
   __shared__ float hbuf[kSeMaxHid];
   const int n = blockIdx.x;
-  const float* xi = x + (size_t)n * HW * in_ld;
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // each wave sums a quarter of the pixels; lanes stride over channels
-  for (int c = lane; c < C; c += 64) {
-    float s = 0.f;
-    for (int p = wv; p < HW; p += 4) s += xi[(size_t)p * in_ld + c];
-    part[wv][c] = s;
+  const T* xi = x + (size_t)n * HW * in_ld;
+  if constexpr (sizeof(T) == 4) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // each wave sums a quarter of the pixels; lanes stride over channels
+    for (int c = lane; c < C; c += 64) {
+      float s = 0.f;
+      for (int p = wv; p < HW; p += 4) s += xi[(size_t)p * in_ld + c];
+      part[wv * kSeMaxC + c] = s;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256)
+      mean[c] = (part[c] + part[kSeMaxC + c] + part[2 * kSeMaxC + c] + part[3 * kSeMaxC + c]) / (float)HW;
+  } else {
+    // 16-byte pieces of 8 channels: thread (g, o) sums piece o of the pixels g, g + G, ...; G = 256 / pieces >= 4 groups
+    const int no = (C + 7) >> 3, G = 256 / no, row = no * 8;       // (G * row <= 2048 floats of part)
+    const int g = threadIdx.x / no, o = threadIdx.x - g * no;
+    if (g < G) {
+      Row<T> s;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s.v[j] = 0.f;
+      for (int p = g; p < HW; p += G) {
+        const Row<T> v = Row<T>::load(xi + (size_t)p * in_ld + o * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s.v[j] += v.v[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) part[g * row + o * 8 + j] = s.v[j];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float s = part[c];
+      for (int k = 1; k < G; ++k) s += part[k * row + c];
+      mean[c] = Elem<T>::rnd(s / (float)HW);
+    }
   }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) mean[c] = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)HW;
   __syncthreads();
   const float* w1 = w;
   const float* b1 = w1 + (size_t)hid * C;
@@ -80,52 +154,63 @@ __global__ void __launch_bounds__(256) se_kernel(const float* x, int in_ld, int 
   for (int j = threadIdx.x; j < hid; j += 256) {
     float s = b1[j];
     for (int c = 0; c < C; ++c) s = __builtin_fmaf(w1[(size_t)j * C + c], mean[c], s);
+    s = Elem<T>::rnd(s);
     hbuf[j] = s > 0.f ? s : 0.f;
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
     float s = b2[c];
     for (int j = 0; j < hid; ++j) s = __builtin_fmaf(w2[(size_t)c * hid + j], hbuf[j], s);
-    gate[(size_t)n * gate_ld + c] = 1.f / (1.f + expf(-s));
+    s = Elem<T>::rnd(s);
+    gate[(size_t)n * gate_ld + c] = (T)Elem<T>::rnd(1.f / (1.f + expf(-s)));
   }
   // padding channels of the gate row (C not a multiple of 4): finite zeros, the combine op multiplies them in
-  for (int c = C + threadIdx.x; c < gate_ld; c += 256) gate[(size_t)n * gate_ld + c] = 0.f;
+  for (int c = C + threadIdx.x; c < gate_ld; c += 256) gate[(size_t)n * gate_ld + c] = (T)0.f;
 }
 
-// ContextAwareModule tail, students.py:199-200: relu(residual + hdc * gate[n, c])
-__global__ void __launch_bounds__(256) cam_combine_kernel(const float* hdc, int hdc_ld, const float* res, int res_ld,
-                                                          const float* gate, int gate_ld, float* y, int out_ld,
-                                                          int C, int N, size_t pix_per_image) {
-  const int c4 = C >> 2;
+// ContextAwareModule tail, students.py:199-200: relu(residual + hdc * gate[n, c]); fp16 rounds the product and the sum
+template <typename T>
+__global__ void __launch_bounds__(256) cam_combine_kernel(const T* hdc, int hdc_ld, const T* res, int res_ld, const T* gate,
+                                                          int gate_ld, T* y, int out_ld, int C, int N, size_t pix_per_image) {
+  constexpr int EN = Elem<T>::N;
+  const int c4 = C / EN;
   const size_t total = (size_t)N * pix_per_image * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t p = i / c4;
-    const int c = (int)(i - p * c4) * 4;
+    const int c = (int)(i - p * c4) * EN;
     const int n = (int)(p / pix_per_image);
-    const float4 h = *reinterpret_cast<const float4*>(hdc + p * hdc_ld + c);
-    const float4 r = *reinterpret_cast<const float4*>(res + p * res_ld + c);
-    const float4 g = *reinterpret_cast<const float4*>(gate + (size_t)n * gate_ld + c);
-    float4 o;
-    o.x = r.x + h.x * g.x; o.y = r.y + h.y * g.y; o.z = r.z + h.z * g.z; o.w = r.w + h.w * g.w;
-    o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f; o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
-    *reinterpret_cast<float4*>(y + p * out_ld + c) = o;
+    const Row<T> h = Row<T>::load(hdc + p * hdc_ld + c);
+    const Row<T> r = Row<T>::load(res + p * res_ld + c);
+    const Row<T> g = Row<T>::load(gate + (size_t)n * gate_ld + c);
+    Row<T> o;
+#pragma unroll
+    for (int j = 0; j < EN; ++j) {
+      const float t = Elem<T>::rnd(h.v[j] * g.v[j]);
+      const float v = Elem<T>::rnd(r.v[j] + t);
+      o.v[j] = v > 0.f ? v : 0.f;
+    }
+    o.store(y + p * out_ld + c);
   }
 }
 
 // AttentionStudent.forward, students.py:755-756: att = sigmoid(att / 20); stem_out + att (broadcast over C);
-// also emits att as the first NCHW output (N,1,H,W)
-__global__ void __launch_bounds__(256) sigmoid_add_kernel(const float* att, int att_ld, const float* x, int x_ld,
-                                                          float* y, int out_ld, int C, size_t pixels,
-                                                          float* att_out) {
-  const int c4 = C >> 2;
+// also emits att as the first NCHW output (N,1,H,W), fp32 in both precisions; fp16 rounds the quotient, the sigmoid and the sum
+template <typename T>
+__global__ void __launch_bounds__(256) sigmoid_add_kernel(const T* att, int att_ld, const T* x, int x_ld, T* y, int out_ld,
+                                                          int C, size_t pixels, float* att_out) {
+  constexpr int EN = Elem<T>::N;
+  const int c4 = C / EN;
   const size_t total = pixels * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t p = i / c4;
-    const int c = (int)(i - p * c4) * 4;
-    const float a = 1.f / (1.f + expf(-(att[p * att_ld] / 20.f)));
+    const int c = (int)(i - p * c4) * EN;
+    const float l = Elem<T>::rnd((float)att[p * att_ld] / 20.f);
+    const float a = Elem<T>::rnd(1.f / (1.f + expf(-l)));
     if (c == 0 && att_out) att_out[p] = a;
-    const float4 v = *reinterpret_cast<const float4*>(x + p * x_ld + c);
-    *reinterpret_cast<float4*>(y + p * out_ld + c) = make_float4(v.x + a, v.y + a, v.z + a, v.w + a);
+    Row<T> v = Row<T>::load(x + p * x_ld + c);
+#pragma unroll
+    for (int j = 0; j < EN; ++j) v.v[j] = Elem<T>::rnd(v.v[j] + a);
+    v.store(y + p * out_ld + c);
   }
 }
 
@@ -258,38 +343,83 @@ int cast_launch(const _Float16* x, int in_ld, float* y, int out_ld, int C, size_
   return RTPE_OK;
 }
 
-int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
-  RTPE_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0, "avgpool: channel counts must be multiples of 4");
-  const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
-  hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, in_ld, y, out_ld, C, N, H, W);
+template <typename T>
+static int avgpool_launch_t(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
+  constexpr int EN = Elem<T>::N;
+  RTPE_REQUIRE(C % EN == 0 && in_ld % EN == 0 && out_ld % EN == 0, "avgpool: channel counts must be multiples of %d", EN);
+  const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / EN);
+  hipLaunchKernelGGL(avgpool_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, x, in_ld, y, out_ld, C, N, H, W);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
+}
+
+int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
+  return avgpool_launch_t<float>(x, in_ld, y, out_ld, C, N, H, W, s);
+}
+
+int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
+  return avgpool_launch_t<_Float16>(x, in_ld, y, out_ld, C, N, H, W, s);
 }
 
 int se_launch(const float* x, int in_ld, int C, int hid, int N, int HW, const float* w, float* gate, int gate_ld,
               hipStream_t s) {
   RTPE_REQUIRE(C <= kSeMaxC && hid <= kSeMaxHid && C > 0 && hid > 0, "se: C=%d hidden=%d unsupported", C, hid);
-  hipLaunchKernelGGL(se_kernel, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld);
+  hipLaunchKernelGGL(se_kernel<float>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
+}
+
+// fp16: the rows of x are read in 16-byte pieces up to the piece that holds channel C - 1
+int se_launch(const _Float16* x, int in_ld, int C, int hid, int N, int HW, const float* w, _Float16* gate, int gate_ld,
+              hipStream_t s) {
+  RTPE_REQUIRE(C <= kSeMaxC && hid <= kSeMaxHid && C > 0 && hid > 0, "se: C=%d hidden=%d unsupported", C, hid);
+  RTPE_REQUIRE(in_ld % 8 == 0 && in_ld >= (C + 7) / 8 * 8 && gate_ld >= C, "se: rows of %d and %d halves for C=%d", in_ld, gate_ld, C);
+  hipLaunchKernelGGL(se_kernel<_Float16>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
+}
+
+template <typename T>
+static int cam_combine_launch_t(const T* hdc, int hdc_ld, const T* res, int res_ld, const T* gate, int gate_ld, T* y,
+                                int out_ld, int C, int N, size_t pix_per_image, hipStream_t s) {
+  constexpr int EN = Elem<T>::N;
+  RTPE_REQUIRE(C % EN == 0 && gate_ld % EN == 0 && (EN == 4 || (hdc_ld % EN == 0 && res_ld % EN == 0 && out_ld % EN == 0)),
+               "cam_combine: C must be a multiple of %d", EN);
+  hipLaunchKernelGGL(cam_combine_kernel<T>, dim3(grid_for((size_t)N * pix_per_image * (C / EN))), dim3(256), 0, s, hdc,
+                     hdc_ld, res, res_ld, gate, gate_ld, y, out_ld, C, N, pix_per_image);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
 
 int cam_combine_launch(const float* hdc, int hdc_ld, const float* res, int res_ld, const float* gate, int gate_ld,
                        float* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s) {
-  RTPE_REQUIRE(C % 4 == 0 && gate_ld % 4 == 0, "cam_combine: C must be a multiple of 4");
-  hipLaunchKernelGGL(cam_combine_kernel, dim3(grid_for((size_t)N * pix_per_image * (C / 4))), dim3(256), 0, s, hdc,
-                     hdc_ld, res, res_ld, gate, gate_ld, y, out_ld, C, N, pix_per_image);
+  return cam_combine_launch_t<float>(hdc, hdc_ld, res, res_ld, gate, gate_ld, y, out_ld, C, N, pix_per_image, s);
+}
+
+int cam_combine_launch(const _Float16* hdc, int hdc_ld, const _Float16* res, int res_ld, const _Float16* gate, int gate_ld,
+                       _Float16* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s) {
+  return cam_combine_launch_t<_Float16>(hdc, hdc_ld, res, res_ld, gate, gate_ld, y, out_ld, C, N, pix_per_image, s);
+}
+
+template <typename T>
+static int sigmoid_add_launch_t(const T* att, int att_ld, const T* x, int x_ld, T* y, int out_ld, int C, size_t pixels,
+                                float* att_out, hipStream_t s) {
+  constexpr int EN = Elem<T>::N;
+  RTPE_REQUIRE(C % EN == 0 && (EN == 4 || (x_ld % EN == 0 && out_ld % EN == 0)), "sigmoid_add: C must be a multiple of %d", EN);
+  hipLaunchKernelGGL(sigmoid_add_kernel<T>, dim3(grid_for(pixels * (C / EN))), dim3(256), 0, s, att, att_ld, x, x_ld, y,
+                     out_ld, C, pixels, att_out);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
 
 int sigmoid_add_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C,
                        size_t pixels, float* att_out, hipStream_t s) {
-  RTPE_REQUIRE(C % 4 == 0, "sigmoid_add: C must be a multiple of 4");
-  hipLaunchKernelGGL(sigmoid_add_kernel, dim3(grid_for(pixels * (C / 4))), dim3(256), 0, s, att, att_ld, x, x_ld, y,
-                     out_ld, C, pixels, att_out);
-  RTPE_HIP_CHECK(hipGetLastError());
-  return RTPE_OK;
+  return sigmoid_add_launch_t<float>(att, att_ld, x, x_ld, y, out_ld, C, pixels, att_out, s);
+}
+
+int sigmoid_add_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C,
+                       size_t pixels, float* att_out, hipStream_t s) {
+  return sigmoid_add_launch_t<_Float16>(att, att_ld, x, x_ld, y, out_ld, C, pixels, att_out, s);
 }
 
 int gate_mul_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C, size_t pixels,

@@ -14,7 +14,8 @@ section 2) and are not built.
 As for the teacher, the ``torch.nn`` leaves only hold parameters; ``forward``
 compiles the tree into one program (fp16 stem under the half wrapper, then a
 cast, then fp32 ops: dilated 3x3 convs on the exact-fp32 MFMA, SE gates, CAM
-combine, average pooling, sigmoid) and runs it on the HIP executor.  The quirks
+combine, average pooling, sigmoid; with ``AttentionStudent(body_half=True)`` no
+cast and the fp16 forms of the same ops) and runs it on the HIP executor.  The quirks
 of the reference forward are reproduced as they are: ``att = hi + 2*up(lo)``
 (:739-742), ``det_hi`` used for both ``hi`` and ``mid`` and ``det_mid`` never
 called (:759-760).
@@ -22,7 +23,7 @@ called (:759-760).
 import torch
 
 from . import _native as nat
-from .third_party.fp16_utils.fp16util import network_to_half, tofp16
+from .third_party.fp16_utils.fp16util import BN_convert_float, network_to_half, tofp16
 from .third_party.pose_higher_hrnet import BN_MOMENTUM, Bottleneck, CompiledModule, ProgramBuilder
 
 
@@ -80,9 +81,9 @@ class ContextAwareModule(torch.nn.Module):
         res = b.conv(x, self.residual[0], self.residual[1], relu=True)
         gate = self.se.emit(b, x)
         # torch.cat of the dilated branches (:191) without a copy: every branch writes its
-        # channels side by side; each slice is padded to a multiple of 4 channels (16 bytes)
+        # channels side by side; each slice is padded to the builder's granule (16 bytes: 4 fp32 or 8 fp16 channels)
         hc = self.hdcs[0][0].out_channels
-        hp = (hc + 3) // 4 * 4
+        hp = -(-hc // b.granule) * b.granule
         nd = len(self.hdcs)
         cat = b.new_tensor(hp * nd, b.tensors[x][1])
         for i, hdc in enumerate(self.hdcs):
@@ -107,7 +108,7 @@ class ContextAwareModule(torch.nn.Module):
         w1[:, col_map] = self.se.fc[0].weight.detach().float().cpu()
         gate = b.se(x, self.se.fc[0], self.se.fc[2], w1=w1)
         hc = self.hdcs[0][0].out_channels
-        hp = (hc + 3) // 4 * 4
+        hp = -(-hc // b.granule) * b.granule
         nd = len(self.hdcs)
         cat = b.new_tensor(hp * nd, b.tensors[x][1])
         for i, hdc in enumerate(self.hdcs):
@@ -169,8 +170,15 @@ class AttentionStudent(CompiledModule):
 
     def __init__(self, hhrnet_statedict_path=None, device="cuda", inplanes=48, num_heatmaps=17, ae_dims=1,
                  half_precision=True, init_fn=torch.nn.init.kaiming_normal_, trainable_stem=False,
-                 bn_momentum=0.1):
+                 bn_momentum=0.1, body_half=False):
+        """``body_half=True`` (needs ``half_precision=True``): everything behind the stem runs in fp16 storage with fp32
+        accumulation too - the reference module after ``BN_convert_float(model.half())`` with the ``tofp32`` between stem and
+        body removed: fp16 parameters, fp32 BatchNorm, fp16 activations, the outputs fp16 values returned as fp32."""
+        if body_half and not half_precision:
+            raise ValueError("rtpe: AttentionStudent(body_half=True) needs half_precision=True (the half body reads the "
+                             "fp16 output of the half-wrapped stem)")
         super().__init__()
+        self.body_half = bool(body_half)
         self.bn_momentum = bn_momentum
         self.num_heatmaps, self.ae_dims = num_heatmaps, ae_dims
         self.stem = StemHRNet()
@@ -188,6 +196,9 @@ class AttentionStudent(CompiledModule):
             torch.nn.Sequential(torch.nn.Identity(), self.stem)
         if hhrnet_statedict_path is not None:
             self.stem[1].load_pretrained(hhrnet_statedict_path, device, check=False)
+        if self.body_half:             # fp16 parameters, fp32 BatchNorm: fp32 checkpoints load into them as usual
+            for name in ("mid_stem", "att_lo", "att_mid", "att_hi", "att_top", "det_lo", "det_mid", "det_hi", "det_top"):
+                BN_convert_float(getattr(self, name).half())
         self._init_compiled()
         self.to(device)
         self.device = device
@@ -210,11 +221,13 @@ class AttentionStudent(CompiledModule):
     def compile_program(self):
         """the forward of reference :724-771 as one program"""
         half = isinstance(self.stem[0], tofp16)
-        b = ProgramBuilder(f32=not half, any_size=True)
+        body_half = getattr(self, "body_half", False)
+        # half body: no cast, every op behind the stem stays fp16 (rows and concat slices of multiples of 8 channels)
+        b = ProgramBuilder(f32=not half, any_size=True, granule=8 if body_half else 4)
         t = self.stem[1].emit(b)
-        if half:
+        if half and not body_half:
             t = b.cast(t)                                   # tofp32 of the wrapped stem
-        b.f32 = True
+        b.f32 = not body_half
         m = self.mid_stem
         t = b.conv(t, m[0], m[1], relu=True)
         stem_out = b.conv(t, m[3], m[4], relu=True)
@@ -234,7 +247,7 @@ class AttentionStudent(CompiledModule):
 
     def forward(self, x, out_hw=None, return_intermediate=False):
         """x (N,3,H,W) fp32 on the GPU, any H, W >= 32 -> (att (N,1,ceil(H/4),ceil(W/4)) = sigmoid mask,
-        det (N,num_heatmaps+ae_dims,ceil(H/4),ceil(W/4))), both fp32.  ``out_hw`` and
+        det (N,num_heatmaps+ae_dims,ceil(H/4),ceil(W/4))), both fp32 (``body_half=True``: fp16 values).  ``out_hw`` and
         ``return_intermediate`` are accepted and unused, as in the reference.
 
         Sizes.  As in the reference every map is ``ceil(n / 2^d)`` wide (the stride-2 convs and ``AvgPool2d(3, 2, 1)``),
@@ -259,7 +272,11 @@ class AttentionStudentSteps(CompiledModule):
     ``att_divisor`` value."""
 
     def __init__(self, hhrnet_statedict_path=None, device="cuda", inplanes=48, num_heatmaps=17, ae_dims=1,
-                 half_precision=True, init_fn=torch.nn.init.kaiming_normal_, trainable_stem=False, bn_momentum=0.1):
+                 half_precision=True, init_fn=torch.nn.init.kaiming_normal_, trainable_stem=False, bn_momentum=0.1,
+                 body_half=False):
+        if body_half:
+            raise NotImplementedError("rtpe: AttentionStudentSteps has no half body: its second-input ops (aux pack, resize, "
+                                      "gate_mul, the 5x5 stem) exist in fp32 only; use body_half=False")
         super().__init__()
         if inplanes % 4:
             raise NotImplementedError("rtpe: AttentionStudentSteps needs inplanes to be a multiple of 4 (16-byte rows)")

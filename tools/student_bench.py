@@ -14,6 +14,12 @@ refine (device events; the host matching between them is not counted).  Prints o
 Needs a GPU; there is no fallback.
 
     python tools/student_bench.py [--steps 12] [--warmup 3] [--repeats 4] [--decode-reps 5]
+
+``--body-half`` measures something else: the student with a half-precision body (``AttentionStudent(body_half=True)``)
+against the fp32 body, same weights, same input, one process - the forward alone and the synchronous step (a) - both
+warmed up (autotuned), order A B B A; written to profiles/student_half_bench.json.
+
+    python tools/student_bench.py --body-half [--steps 12] [--warmup 3] [--repeats 4]
 """
 import argparse
 import json
@@ -38,8 +44,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=4, help="timed runs per path, interleaved A B B A ...")
     ap.add_argument("--decode-reps", type=int, default=5)
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "student_pipeline_bench.json"))
+    ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--body-half", action="store_true", help="the half body against the fp32 body (see the module docstring)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "student_half_bench.json" if args.body_half else "student_pipeline_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("student_bench: no GPU (the students run on the HIP path only)")
     import __graft_entry__ as entry
@@ -93,6 +102,9 @@ def main():
             torch.cuda.synchronize(dev)
             return B * steps / (time.perf_counter() - t0), count(res)
         return run
+
+    if args.body_half:
+        return body_half_bench(args, stu, x, shapes, new_parser, expand_args, count)
 
     p_a, p_b = new_parser(), new_parser()
     paths = {"sync_expand": sync_rate(lambda det: p_a.parse_lowres(*expand_args(det), (S, S))),
@@ -171,6 +183,73 @@ def main():
     for key in order[1:]:
         out[key]["over_sync_expand"] = round(out[key]["img_s"] / base, 4)
     out["people_last_batch"] = people
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def body_half_bench(args, stu32, x, shapes, new_parser, expand_args, count):
+    """fp32 body against half body: forward alone and forward + ``parse_lowres`` on the expanded maps (bench.py's config-4
+    step), A B B A"""
+    from oracle import synth
+    from rtpe.students import AttentionStudent
+    dev, B, S = x.device, args.batch, args.size
+    stu16 = AttentionStudent(None, "cpu", 100, 17, 1, True, None, False, body_half=True).eval()
+    stu16.load_state_dict(synth.make_state_dict(shapes, 3, "W1"), strict=True)
+    stu16 = stu16.to(dev)
+    models = {"fp32_body": stu32, "half_body": stu16}
+    parsers = {k: new_parser() for k in models}
+
+    def forward(key):
+        def run(steps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                for _ in range(steps):
+                    models[key](x)
+            torch.cuda.synchronize(dev)
+            return B * steps / (time.perf_counter() - t0), 0
+        return run
+
+    def step(key):
+        def run(steps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                for _ in range(steps):
+                    att, det = models[key](x)
+                    res = parsers[key].parse_lowres(*expand_args(det.float()), (S, S))
+            torch.cuda.synchronize(dev)
+            return B * steps / (time.perf_counter() - t0), count(res)
+        return run
+
+    paths = {"forward_fp32_body": forward("fp32_body"), "forward_half_body": forward("half_body"),
+             "step_fp32_body": step("fp32_body"), "step_half_body": step("half_body")}
+    with torch.no_grad():
+        a32, d32 = stu32(x)
+        a16, d16 = stu16(x)
+    diff = {"att_max": float((a32 - a16).abs().max()), "det_max": float((d32 - d16).abs().max()),
+            "det_mean": float((d32 - d16).abs().mean()), "det_range": float(d32.abs().max())}
+    for run in paths.values():
+        run(args.warmup)
+    runs = {key: [] for key in paths}
+    order = list(paths)
+    for r in range(args.repeats):
+        for key in (order if r % 2 == 0 else order[::-1]):
+            runs[key].append(round(paths[key](args.steps)[0], 1))
+    out = {"metric": "student_half_body_throughput", "model": "AttentionStudent(inplanes=100)", "weights": "W1", "batch": B,
+           "size": S, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
+           "device": torch.cuda.get_device_name(dev), "order": "A B B A over " + ", ".join(order),
+           "half_vs_fp32_outputs": diff}
+    for key in order:
+        out[key] = {"img_s": round(float(np.median(runs[key])), 1), "img_s_runs": runs[key],
+                    "img_s_spread": round(max(runs[key]) - min(runs[key]), 1),
+                    "ms_per_step": round(1e3 * B / float(np.median(runs[key])), 3)}
+    out["forward_half_over_fp32"] = round(out["forward_half_body"]["img_s"] / out["forward_fp32_body"]["img_s"], 4)
+    out["step_half_over_fp32"] = round(out["step_half_body"]["img_s"] / out["step_fp32_body"]["img_s"], 4)
     line = json.dumps(out)
     print(line)
     if args.out:
