@@ -711,5 +711,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_tagmean.h"
 #include "rtpe_hip_noproj.h"
 #include "rtpe_hip_anysize.h"
+#include "rtpe_hip_mixed.h"
 
 #endif /* RTPE_HIP_H */

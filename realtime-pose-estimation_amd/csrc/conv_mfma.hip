@@ -79,7 +79,7 @@ __host__ __device__ constexpr int conv_weight_ring(int mt, int step_cycles) {
   return RTPE_WEIGHT_RING ? RTPE_WEIGHT_RING : d < 1 ? 1 : d;
 }
 
-template <typename T, int MT, int NT, int WAVES>
+template <typename T, int MT, int NT, int WAVES, bool MIXED = false>
 __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int EPS = Prec<T>::EPS;
@@ -156,6 +156,22 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
   const int co_base = (cb * mt_pack + msel * MT) * 16;        // first output channel of this workgroup
   const int py0 = tyi * a.th, px0 = txi * a.tw;
   const int iy0 = py0 * a.in_mul + lo_y, ix0 = px0 * a.in_mul + lo_x;
+  // A mixed-size batch (MIXED; ext_in / ext_out: one (h, w) pair per image at the input's / the output's level,
+  // rtpe_hip_mixed.h): image n's own extents mask every read and store, the canvas extents (H_in, W_in, H_full, W_full) stay
+  // the pitch.  Uniform per workgroup: two scalar loads of the table rows.  A tile wholly outside its image leaves before the
+  // first barrier.  !MIXED: the canvas extents do both, read from the argument block where they are used, as ever (an
+  // instantiation of its own: the registers of the other forwards' kernels do not move - four more scalars alive over the k
+  // loops cost the fp32 3 x 4 one a wave of occupancy).
+  int ext_hw[4] = {0, 0, 0, 0};
+  if constexpr (MIXED) {
+    ext_hw[0] = a.ext_in[2 * n]; ext_hw[1] = a.ext_in[2 * n + 1];
+    ext_hw[2] = a.ext_out[2 * n]; ext_hw[3] = a.ext_out[2 * n + 1];
+    if (py0 >= ext_hw[2] || px0 >= ext_hw[3]) return;
+  }
+#define Hm_in (MIXED ? ext_hw[0] : a.H_in)
+#define Wm_in (MIXED ? ext_hw[1] : a.W_in)
+#define Hm_pos (MIXED ? ext_hw[2] : a.H_pos)
+#define Wm_pos (MIXED ? ext_hw[3] : a.W_pos)
 
   // LDS byte offset of (tap, channel) for every (k chunk, lane group)
   const int kvalid = a.ntaps * a.cc;
@@ -229,7 +245,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
       const int py = py0 + (int)oyt, px = px0 + (int)oxt;
       const int ch = co_base + slot * EPS;
       rpre[it] = uint4{0u, 0u, 0u, 0u};
-      if (c < NT * 16 * CHG && py < a.H_pos && px < a.W_pos && ch < a.cout_store) {
+      if (c < NT * 16 * CHG && py < Hm_pos && px < Wm_pos && ch < a.cout_store) {
         const int oy = py * a.o_mul + oy_add, ox = px * a.o_mul + ox_add;
         const size_t pix = ((size_t)n * a.H_full + oy) * a.W_full + ox;
         rpre[it] = *reinterpret_cast<const uint4*>(rin + pix * a.res_ld + ch);
@@ -261,8 +277,8 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
         // LDS column hx holds input column: even ones first, then the odd ones (stride 2) / itself
         const int hxs = a.deint ? ((int)hx < a.n_even ? 2 * (int)hx : 2 * ((int)hx - a.n_even) + 1) : (int)hx;
         const int iy = iy0 + (int)hy, ix = ix0 + hxs;
-        const bool ok = (int)hx < a.halo_w && (int)s < slots && (unsigned)iy < (unsigned)a.H_in &&
-                        (unsigned)ix < (unsigned)a.W_in && cbase + (int)s * EPS < a.cin;
+        const bool ok = (int)hx < a.halo_w && (int)s < slots && (unsigned)iy < (unsigned)Hm_in &&
+                        (unsigned)ix < (unsigned)Wm_in && cbase + (int)s * EPS < a.cin;
         const uint32_t voff = ok ? (uint32_t)((iy * a.W_in + ix) * a.in_ld + cbase + (int)s * EPS) * (uint32_t)ES : 0x80000000u;
         if (L < (uint32_t)tile_slots)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(tile + ib * 16), 16, (int)voff, 0, 0, 0);
@@ -284,7 +300,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
         const uint32_t hxl = a.deint ? ((hx & 1u) ? (uint32_t)a.n_even + (hx >> 1) : (hx >> 1)) : hx;   // LDS column of input column hx
         dst[u] = idx < total ? (int)(hy * a.rowb + hxl * a.pstride + s * 16) : -1;
         v[u] = make_uint4(0, 0, 0, 0);
-        if (idx < total && (unsigned)iy < (unsigned)a.H_in && (unsigned)ix < (unsigned)a.W_in &&
+        if (idx < total && (unsigned)iy < (unsigned)Hm_in && (unsigned)ix < (unsigned)Wm_in &&
             cbase + (int)s * EPS < a.cin)
           v[u] = *reinterpret_cast<const uint4*>(xin + ((size_t)iy * a.W_in + ix) * a.in_ld + cbase + s * EPS);
       }
@@ -377,7 +393,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
   char* obuf = tile + wv * (NT * 16 * ROWB);
   // NCHW fp32 output as 16-byte row pieces (below) when four consecutive positions are four consecutive output pixels
   const bool nchw_rows = a.y_nchw != nullptr && a.nchw_f32 && a.o_mul == 1 && a.res == nullptr && (a.tw & 3) == 0 &&
-                         (a.W_pos & 3) == 0 && (a.W_full & 3) == 0 && (ox_add & 3) == 0 && ((uintptr_t)a.y_nchw & 15) == 0;
+                         (Wm_pos & 3) == 0 && (a.W_full & 3) == 0 && (ox_add & 3) == 0 && ((uintptr_t)a.y_nchw & 15) == 0;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
@@ -406,7 +422,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
         const uint32_t oyt = fdiv(p, a.div_tw);
         const uint32_t oxt = p - oyt * a.tw;
         const int py = py0 + (int)oyt, px = px0 + (int)oxt;
-        if (py < a.H_pos && px < a.W_pos) {
+        if (py < Hm_pos && px < Wm_pos) {
           const int oy = py * a.o_mul + oy_add, ox = px * a.o_mul + ox_add;
           const int c4 = co_base + m * 16 + g * 4;
 #pragma unroll
@@ -439,7 +455,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
       const uint32_t oxt = p - oyt * a.tw;
       const int py = py0 + (int)oyt, px = px0 + (int)oxt;
       const int ch = cblk + slot * EPS;
-      if (py >= a.H_pos || px >= a.W_pos || ch >= a.cout_store) continue;
+      if (py >= Hm_pos || px >= Wm_pos || ch >= a.cout_store) continue;
       const int oy = py * a.o_mul + oy_add, ox = px * a.o_mul + ox_add;
       const size_t pix = ((size_t)n * a.H_full + oy) * a.W_full + ox;
       uint4 raw = *reinterpret_cast<const uint4*>(obuf + pw * ROWB + slot * 16);
@@ -497,7 +513,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
       const uint32_t oyt = fdiv(p, a.div_tw);
       const uint32_t oxt = p - oyt * a.tw;
       const int py = py0 + (int)oyt, px = px0 + (int)oxt;
-      if (py >= a.H_pos || px >= a.W_pos) continue;
+      if (py >= Hm_pos || px >= Wm_pos) continue;
       T in4[4];
       if constexpr (kPlanes) {
         __builtin_memcpy(in4, obuf + c * CPITCH + q * 4 * ES, 4 * ES);
@@ -515,6 +531,10 @@ __global__ void __launch_bounds__(WAVES * 64) conv_mfma_kernel(const ConvArgs a)
       *reinterpret_cast<float4v*>(reinterpret_cast<float*>(a.y_nchw) + oi) = out;
     }
   }
+#undef Hm_in
+#undef Wm_in
+#undef Hm_pos
+#undef Wm_pos
 #ifdef RTPE_CONV_STAMPS
   RTPE_STAMP(6);
   if (a.dbg != nullptr && lane == 0) {
@@ -663,6 +683,13 @@ bool conv_deint(const ConvPlan& p, int kind) {
   V(2, 8, 4) V(2, 4, 4) V(2, 2, 4) V(2, 5, 4) V(2, 5, 5) V(2, 1, 4)                                     \
   V(1, 8, 4) V(1, 4, 4) V(1, 2, 4) V(1, 5, 4) V(1, 5, 5) V(1, 1, 4)                                     \
   V(6, 2, 2) V(6, 4, 1) V(4, 2, 2) V(4, 4, 1) V(3, 2, 2) V(3, 4, 1)
+
+// ... and those of them that a mixed-size batch can reach (ConvArgs::mixed; the MIXED instantiations): the default launch
+// shapes of the one-workgroup-per-tile kernel (conv_make_tile without the other kernels: 2, 4, 5 or 8 pixel tiles per wave
+// on 4 or 5 waves, whole cout blocks)
+#define RTPE_CONV_MIXED_VARIANTS(V)                                                                     \
+  V(3, 8, 4) V(3, 4, 4) V(3, 2, 4) V(3, 5, 4) V(3, 5, 5) V(4, 4, 4) V(4, 2, 4) V(4, 5, 4) V(4, 5, 5) V(6, 2, 4)   \
+  V(2, 8, 4) V(2, 4, 4) V(2, 2, 4) V(2, 5, 4) V(2, 5, 5) V(1, 8, 4) V(1, 4, 4) V(1, 2, 4) V(1, 5, 4) V(1, 5, 5)
 
 static bool conv_has_variant(int mt, int nt, int waves) {
 #define RTPE_V(MTv, NTv, Wv) if (mt == MTv && nt == NTv && waves == Wv) return true;
@@ -879,10 +906,10 @@ void conv_fill_args(const ConvGeom& g, const ConvPlan& p, const ConvTile& t, Con
   if (skipk) a->kc = 0;
 }
 
-template <typename T, int MT, int NT, int WAVES>
+template <typename T, int MT, int NT, int WAVES, bool MIXED = false>
 static int launch_variant(const ConvTile& t, const ConvArgs& a, int n_cb, hipStream_t s) {
   static unsigned long long attr_mask = 0;
-  auto kern = conv_mfma_kernel<T, MT, NT, WAVES>;
+  auto kern = conv_mfma_kernel<T, MT, NT, WAVES, MIXED>;
   if (first_use_on_device(&attr_mask)) {
     RTPE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -996,6 +1023,18 @@ int conv_launch(const ConvPlan& p, const ConvTile& t, const ConvArgs& a, hipStre
   RTPE_REQUIRE(t.mrun >= 0 ? a.wsplit <= 1 : (a.wsplit == 2 && t.waves % 2 == 0 && (p.mt / mrun) % 2 == 0), "conv: wave halves");
   RTPE_REQUIRE(p.mt % mrun == 0 && a.m_split == p.mt / mrun, "conv: %d cout tiles per workgroup do not divide the block of %d",
                mrun, p.mt);
+  if (a.mixed) {      // a mixed-size batch: the instantiations that mask by the extent table
+    RTPE_REQUIRE(a.ext_in != nullptr && a.ext_out != nullptr && a.o_mul == 1 && a.n_cls == 0 && t.mrun == 0,
+                 "conv: a mixed-size batch runs plain convs on whole cout blocks");
+#define RTPE_V(MTv, NTv, Wv)                                                                  \
+  if (mrun == MTv && t.nt == NTv && t.waves == Wv)                                            \
+    return p.esize == 4 ? launch_variant<float, MTv, NTv, Wv, true>(t, a, p.n_cb, s)           \
+                        : launch_variant<_Float16, MTv, NTv, Wv, true>(t, a, p.n_cb, s);
+    RTPE_CONV_MIXED_VARIANTS(RTPE_V)
+#undef RTPE_V
+    set_error("conv: no mixed-size kernel variant mt=%d nt=%d waves=%d", mrun, t.nt, t.waves);
+    return RTPE_E_INVALID;
+  }
 #define RTPE_V(MTv, NTv, Wv)                                                                  \
   if (mrun == MTv && t.nt == NTv && t.waves == Wv)                                            \
     return p.esize == 4 ? launch_variant<float, MTv, NTv, Wv>(t, a, p.n_cb, s)                 \

@@ -104,16 +104,28 @@ __global__ void __launch_bounds__(256) fuse_nearest_kernel(const FuseArgs a, con
   const uint32_t p0 = blockIdx.x * 256u;
   const uint32_t x_first = fdiv(p0, div_c8);
   const uint32_t n = fdiv(blockIdx.y, div_h), y = blockIdx.y - n * (uint32_t)a.H;
+  // mixed-size batches: the index rule runs on image n's own extents (this row's image: uniform per workgroup), the canvas
+  // extents (a.H, a.W, a.term_h, a.term_w) address; a row or a block of columns outside the image has nothing to do
+  int Hm = a.H, Wm = a.W;
+  if (a.ext_out != nullptr) {
+    Hm = a.ext_out[2 * n]; Wm = a.ext_out[2 * n + 1];
+    if ((int)y >= Hm || (int)x_first >= Wm) return;
+  }
   for (int i = threadIdx.x; i < 4 * kFuseCols; i += 256) {
     const int t = i / kFuseCols, k = i - t * kFuseCols;
     const int x = (int)x_first + k;
-    if (t < a.n_terms && x < a.W) sx[t][k] = nearest_src(x, a.term_w[t], (float)a.term_w[t] / (float)a.W);
+    if (t < a.n_terms && x < Wm) {
+      const int tw = a.ext_out != nullptr ? a.ext_term[t][2 * n + 1] : a.term_w[t];
+      sx[t][k] = nearest_src(x, tw, (float)tw / (float)Wm);
+    }
   }
-  if ((int)threadIdx.x < a.n_terms)
-    sy[threadIdx.x] = nearest_src((int)y, a.term_h[threadIdx.x], (float)a.term_h[threadIdx.x] / (float)a.H);
+  if ((int)threadIdx.x < a.n_terms) {
+    const int th = a.ext_out != nullptr ? a.ext_term[threadIdx.x][2 * n] : a.term_h[threadIdx.x];
+    sy[threadIdx.x] = nearest_src((int)y, th, (float)th / (float)Hm);
+  }
   __syncthreads();
   const uint32_t p = p0 + threadIdx.x;
-  if (p >= (uint32_t)(a.W * c8)) return;
+  if (p >= (uint32_t)(Wm * c8)) return;
   const uint32_t x = fdiv(p, div_c8), cs = p - x * (uint32_t)c8;
   uint4 raw[4];
 #pragma unroll
@@ -200,7 +212,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
   __shared__ __attribute__((aligned(16))) float wl[27][kStemCO];
   // ceil(H / 2) x ceil(W / 2): with an odd side the last output row / column reads one tap beyond the image, which the
   // staging below zeroes like the padding at the low edge
-  const int Ho = (a.H + 1) >> 1, Wo = (a.W + 1) >> 1;
+  const int Ho = (a.H + 1) >> 1, Wo = (a.W + 1) >> 1;      // (mixed-size batches: of the canvas - the pitch of y)
   const int tiles_x = (Wo + kStemTW - 1) / kStemTW, tiles_y = (Ho + kStemTH - 1) / kStemTH;
   // Workgroups are dealt to the 8 XCDs round robin (blockIdx.x % 8): an XCD takes a CONTIGUOUS eighth of the row-major
   // tile list, so that neighbouring tiles - whose 65-float patch rows share their first / last 128-byte line and
@@ -214,6 +226,14 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
   const int oy0 = ty * kStemTH, ox0 = tx * kStemTW;
   const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;
   const int tid = threadIdx.x;
+  // mixed-size batches: image n's own h x w inside the a.H x a.W canvas - taps beyond it are zero padding, outputs exist up to
+  // ceil(h / 2) x ceil(w / 2); a tile wholly outside leaves before the barrier
+  int Hm = a.H, Wm = a.W;
+  if (a.ext != nullptr) {
+    Hm = a.ext[2 * n]; Wm = a.ext[2 * n + 1];
+    if (oy0 >= ((Hm + 1) >> 1) || ox0 >= ((Wm + 1) >> 1)) return;
+  }
+  const int Hmo = (Hm + 1) >> 1, Wmo = (Wm + 1) >> 1;
 
   // Staging: ALL global loads of a thread are issued before the first LDS write.  (The plain loops compiled to one
   // load + s_waitcnt vmcnt(0) per iteration: ~20 dependent memory round trips per workgroup, which - not the
@@ -233,7 +253,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
       const int py = rem / kStemPW, px = rem - py * kStemPW;
       const int iy = iy0 + py, ix = ix0 + px;
       *dst = i < kPatch ? (c * kStemPH + py) * (kStemPW + 1) + px : -1;
-      *ok = i < kPatch && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+      *ok = i < kPatch && (unsigned)iy < (unsigned)Hm && (unsigned)ix < (unsigned)Wm;
       // (no branch around the load: an element outside the image reads a clamped pixel and is zeroed below)
       const int cy = iy < 0 ? 0 : (iy >= a.H ? a.H - 1 : iy), cx = ix < 0 ? 0 : (ix >= a.W ? a.W - 1 : ix);
       *src = ((n * 3 + c) * a.H + cy) * a.W + cx;             // < 2^31 elements (host-checked)
@@ -327,7 +347,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a) {
   for (int p = 0; p < 8; ++p) {
     const int idx = p * 8 + g;
     const int oy = oy0 + 2 * wv + (idx >> 5), ox = ox0 + (idx & 31);
-    if (oy >= Ho || ox >= Wo) continue;
+    if (oy >= Hmo || ox >= Wmo) continue;
     T* dst = reinterpret_cast<T*>(a.y) + (((size_t)n * Ho + oy) * Wo + ox) * a.out_ld + cg * 8;
 #pragma unroll
     for (int q = 0; q < 8 / EPS; ++q) {

@@ -499,9 +499,30 @@ static void slot_layout(const rtpe_hrnet* h, int N, int H, int W, std::vector<si
 // that is no multiple of 32): programs with the any_size property whose ops all have a general path - a transposed conv doubles a
 // map that the extent rule does not double, and a fused BasicBlock pair or a stride-2 group has no launch of its own to fall
 // back to in the records of a forward.  The nearest-to-size sampler of the fuse ops has one row of workgroups per output row.
-static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who) {
+// A mixed-size batch (`mixed`, rtpe_hip_mixed.h) is held to the rules of a ragged shape whatever its canvas size, and its ops
+// to those that mask by the extent table: no second input, and no tensor below 1/32 read by a conv, a fuse sum or an SE mean.
+static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who, bool mixed = false) {
   RTPE_REQUIRE(N > 0 && H >= 32 && W >= 32, "%s: N=%d H=%d W=%d", who, N, H, W);
-  if (!ragged(H, W)) return RTPE_OK;
+  if (mixed) {
+    RTPE_REQUIRE(h->any_size, "%s: a mixed-size batch needs a program with the any_size property (the students'); this program "
+                 "takes one size per batch, multiples of 32", who);
+    for (size_t i = 0; i < h->ops.size(); ++i) {
+      const rtpe_op_desc& d = h->ops[i].d;
+      RTPE_REQUIRE(d.kind != RTPE_OP_AUX_PACK && d.kind != RTPE_OP_RESIZE && d.kind != RTPE_OP_GATE_MUL,
+                   "%s: op %zu: a program with a second input (aux pack, resize, gate_mul) takes no mixed-size batch", who, i);
+      int top = -1;                                     // the deepest level whose row of the table this op reads
+      if (d.kind == RTPE_OP_CONV) top = h->tensors[d.in_t].ds_log2 + (d.stride == 2 ? 1 : 0);
+      if (d.kind == RTPE_OP_STEM) top = 1;
+      if (d.kind == RTPE_OP_AVGPOOL || d.kind == RTPE_OP_SE) top = h->tensors[d.in_t].ds_log2;
+      if (d.kind == RTPE_OP_FUSE) {
+        top = h->tensors[d.out_t].ds_log2;
+        for (int t = 0; t < d.n_terms; ++t) top = h->tensors[d.term_t[t]].ds_log2 > top ? h->tensors[d.term_t[t]].ds_log2 : top;
+      }
+      RTPE_REQUIRE(top < RTPE_MIXED_LEVELS, "%s: op %zu works at 1 / 2^%d, the extent table ends at 1 / 2^%d", who, i, top,
+                   RTPE_MIXED_LEVELS - 1);
+    }
+  }
+  if (!ragged(H, W) && !mixed) return RTPE_OK;
   RTPE_REQUIRE(h->any_size, "%s: N=%d H=%d W=%d: H and W must be multiples of 32 for this program (its branches at 1/4 .. 1/32 "
                "are fused by factor-2 resampling; only programs with the any_size property take other sizes)", who, N, H, W);
   for (size_t i = 0; i < h->ops.size(); ++i) {
@@ -529,8 +550,8 @@ extern "C" int rtpe_hrnet_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_
 
 // plane-major tensors of one run: the candidates all of whose ops run on the streaming kernel with the launch
 // shapes in force (tiny maps fall back to the generic kernel, which only knows NHWC)
-static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W, const std::vector<ConvTile>* tuned) {
-  if (ragged(H, W)) return std::vector<char>(h->plane_ok.size(), 0);   // (the streaming kernel, which alone knows the layout, is not used)
+static std::vector<char> plane_tensors(const rtpe_hrnet* h, int N, int H, int W, const std::vector<ConvTile>* tuned, bool rag) {
+  if (rag) return std::vector<char>(h->plane_ok.size(), 0);   // (the streaming kernel, which alone knows the layout, is not used)
   std::vector<char> plane = h->plane_ok;
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const OpState& o = h->ops[i];
@@ -568,12 +589,15 @@ struct Fwd {
   const std::vector<ConvTile>* tuned = nullptr;
   std::vector<char> plane;
   bool rag;                 // a ragged shape: general paths, default launch shapes (nothing is tuned at such a shape)
-  Fwd(const rtpe_hrnet* h_, int N_, int H_, int W_, void* ws, void* preds_, void* refined_, int out_dtype_)
-      : h(h_), N(N_), H(H_), W(W_), base(reinterpret_cast<char*>(ws)), preds(preds_), refined(refined_), out_dtype(out_dtype_), rag(ragged(H_, W_)) {
+  const int32_t* ext;       // a mixed-size batch (always `rag`): the extent table on the device, else nullptr
+  const int32_t* level(int ds) const { return ext + (size_t)ds * 2 * N; }     // (h, w) of every image at 1 / 2^ds
+  Fwd(const rtpe_hrnet* h_, int N_, int H_, int W_, void* ws, void* preds_, void* refined_, int out_dtype_, const int32_t* ext_ = nullptr)
+      : h(h_), N(N_), H(H_), W(W_), base(reinterpret_cast<char*>(ws)), preds(preds_), refined(refined_), out_dtype(out_dtype_),
+        rag(ragged(H_, W_) || ext_ != nullptr), ext(ext_) {
     slot_layout(h, N, H, W, &offs, &ws_need);
     auto it = h->tuned.find(std::make_tuple(N, H, W));
     if (it != h->tuned.end() && !rag) tuned = &it->second;
-    plane = plane_tensors(h, N, H, W, tuned);
+    plane = plane_tensors(h, N, H, W, tuned, rag);
   }
   size_t esz(int t) const { return h->tensors[t].reserved == 4 ? 4 : 2; }
   _Float16* tptr(int t, int coff) const {      // element type per tensor (fp16 or fp32): byte arithmetic
@@ -651,6 +675,11 @@ static ConvArgs conv_op_args(const Fwd& f, size_t i, int k) {
   }
   a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
   a.round_conv = (d.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
+  if (f.ext != nullptr) {     // (no transposed conv in a mixed-size batch: check_shape) a stride-2 conv writes the next level
+    a.mixed = 1;
+    a.ext_in = f.level(ti.ds_log2);
+    a.ext_out = f.level(ti.ds_log2 + (d.stride == 2 ? 1 : 0));
+  }
   return a;
 }
 
@@ -879,7 +908,7 @@ static int read_op_times(const std::vector<Route>& r, const std::vector<hipEvent
 
 static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, void* preds, void* refined,
                int out_dtype, void* ws, size_t ws_bytes, hipStream_t s_main, float* op_ms, int n_ms,
-               rtpe_record* rec = nullptr, const void* aux = nullptr, uint32_t fwd_flags = 0) {
+               rtpe_record* rec = nullptr, const void* aux = nullptr, uint32_t fwd_flags = 0, const int32_t* ext = nullptr) {
   RTPE_REQUIRE(h && x && ws, "forward: null argument");
   static const int host_prof = env_int("RTPE_HOST_PROF", 0);       // host time of a forward: where it goes (stderr)
   typedef std::chrono::steady_clock hclock;
@@ -900,12 +929,12 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
   DeviceGuard guard(h->device);
   RTPE_HIP_CHECK(guard.err);
   {
-    const int rc = check_shape(h, N, H, W, "forward");
+    const int rc = check_shape(h, N, H, W, "forward", ext != nullptr);
     if (rc != RTPE_OK) return rc;
   }
   RTPE_REQUIRE(x_dtype == RTPE_DTYPE_F16 || x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
   RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F16 || out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
-  const Fwd f(h, N, H, W, ws, preds, refined, out_dtype);
+  const Fwd f(h, N, H, W, ws, preds, refined, out_dtype, ext);
   if (f.ws_need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, f.ws_need); return RTPE_E_NOMEM; }
   RTPE_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
   // Shapes an op cannot take are refused here, before the first launch, so that no half-run forward is left behind.
@@ -1067,6 +1096,7 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
         a.y = tptr(d.out_t, d.out_coff);
         a.N = N; a.H = H; a.W = W; a.out_ld = h->tensors[d.out_t].channels;
         a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
+        a.ext = ext ? f.level(0) : nullptr;
         RTPE_HP_LAUNCH(rc = stem_launch(a, s));
         break;
       }
@@ -1137,6 +1167,7 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           const size_t pixels = (size_t)N * Hi * Wi;
           float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
           const bool h16 = !(d.flags & RTPE_F_F32) && d.kind != RTPE_OP_CAST;    // the fp16 forms (checked before the first launch)
+          const int* ext_in = ext ? f.level(ti.ds_log2) : nullptr;            // avgpool, se: image n's own part of the map
           float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
           if (d.kind == RTPE_OP_SIGMOID_ADD && (d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
             set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
@@ -1144,10 +1175,10 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           if (d.kind == RTPE_OP_CAST) {
             rc = cast_launch(tptr(d.in_t, d.in_coff), ti.channels, yo, to.channels, d.cout, pixels, s);
           } else if (h16 && d.kind == RTPE_OP_AVGPOOL) {
-            rc = avgpool_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.out_t, d.out_coff), to.channels, d.cout, N, Hi, Wi, s);
+            rc = avgpool_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.out_t, d.out_coff), to.channels, d.cout, N, Hi, Wi, s, ext_in);
           } else if (h16 && d.kind == RTPE_OP_SE) {
             rc = se_launch(tptr(d.in_t, d.in_coff), ti.channels, d.cin, d.cout, N, Hi * Wi,
-                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), tptr(d.out_t, d.out_coff), to.channels, s);
+                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), tptr(d.out_t, d.out_coff), to.channels, s, ext_in, Wi);
           } else if (h16 && d.kind == RTPE_OP_CAM_COMBINE) {
             rc = cam_combine_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.res_t, d.res_coff), h->tensors[d.res_t].channels,
                                     tptr(d.term_t[0], 0), h->tensors[d.term_t[0]].channels, tptr(d.out_t, d.out_coff),
@@ -1157,10 +1188,10 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
                                     tptr(d.out_t, d.out_coff), to.channels, d.cout, pixels, att_out, s);
           } else if (d.kind == RTPE_OP_AVGPOOL) {
             rc = avgpool_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, yo, to.channels,
-                                d.cout, N, Hi, Wi, s);
+                                d.cout, N, Hi, Wi, s, ext_in);
           } else if (d.kind == RTPE_OP_SE) {
             rc = se_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, d.cin, d.cout, N, Hi * Wi,
-                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), yo, to.channels, s);
+                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), yo, to.channels, s, ext_in, Wi);
           } else if (d.kind == RTPE_OP_CAM_COMBINE) {
             rc = cam_combine_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
                                     reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
@@ -1188,7 +1219,9 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
           for (int t = 0; t < d.n_terms; ++t) {
             a.term_h[t] = extent(H, h->tensors[d.term_t[t]].ds_log2);
             a.term_w[t] = extent(W, h->tensors[d.term_t[t]].ds_log2);
+            if (ext) a.ext_term[t] = f.level(h->tensors[d.term_t[t]].ds_log2);
           }
+          if (ext) a.ext_out = f.level(to.ds_log2);
           a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
           a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
           RTPE_HP_LAUNCH(rc = fuse_launch(a, s));
@@ -1207,6 +1240,23 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
     if (rec && has_event) RTPE_HIP_CHECK(hipEventRecord(rec->ev[i + 1], s));
   }
   if (lanes_on && cur_region > 0) RTPE_HIP_CHECK(join_lanes());
+  if (ext != nullptr) {
+    // a mixed-size batch: whatever the forward left outside an image's own region of the two outputs becomes 0.0
+    float* y[2] = {nullptr, nullptr};
+    int C[2] = {0, 0}, lv[2] = {0, 0};
+    for (const OpState& o : h->ops) {
+      const rtpe_op_desc& d = o.d;
+      if (!(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))) continue;
+      const int k = (d.flags & RTPE_F_OUT_REFINED) ? 1 : 0;
+      y[k] = reinterpret_cast<float*>(k ? refined : preds);
+      C[k] = d.kind == RTPE_OP_SIGMOID_ADD ? 1 : d.cout;
+      lv[k] = h->tensors[d.in_t].ds_log2 + (d.kind == RTPE_OP_CONV && d.stride == 2 ? 1 : 0);
+    }
+    for (int k = 0; k < 2; ++k) if (y[k] == nullptr) C[k] = 0;
+    const int rc = mask_outputs_launch(y[0], C[0], extent(H, lv[0]), extent(W, lv[0]), f.level(lv[0]), y[1], C[1], extent(H, lv[1]),
+                                       extent(W, lv[1]), f.level(lv[1]), N, s_main);
+    if (rc != RTPE_OK) return rc;
+  }
   if (host_prof) {
     static double sum_total = 0.0, sum_launch = 0.0;
     static int n_calls = 0;
@@ -1313,6 +1363,77 @@ extern "C" int rtpe_hrnet_get_any_size(const rtpe_hrnet* h, int32_t* on) {
   RTPE_REQUIRE(h != nullptr && on != nullptr, "get_any_size: null argument");
   *on = h->any_size ? 1 : 0;
   return RTPE_OK;
+}
+
+// ---- mixed-size batches (include/rtpe_hip_mixed.h) -------------------------
+static size_t mixed_table_bytes(int N) { return align_up((size_t)RTPE_MIXED_LEVELS * 2 * N * sizeof(int32_t), 256); }
+
+extern "C" int rtpe_mixed_table_ints(int32_t N, int32_t* count) {
+  RTPE_REQUIRE(N > 0 && N <= (1 << 20) && count != nullptr, "mixed_table_ints: N=%d", N);
+  *count = RTPE_MIXED_LEVELS * 2 * N;
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_mixed_table_fill(const int32_t* sizes_hw, int32_t N, int32_t Hc, int32_t Wc, int32_t* table, int32_t n_ints) {
+  RTPE_REQUIRE(sizes_hw != nullptr && table != nullptr && N > 0 && N <= (1 << 20), "mixed_table_fill: null argument or N=%d", N);
+  RTPE_REQUIRE(n_ints >= RTPE_MIXED_LEVELS * 2 * N, "mixed_table_fill: %d integers for %d images (%d needed)", n_ints, N,
+               RTPE_MIXED_LEVELS * 2 * N);
+  RTPE_REQUIRE(Hc >= 32 && Wc >= 32, "mixed_table_fill: canvas %d x %d", Hc, Wc);
+  for (int n = 0; n < N; ++n) {
+    const int hn = sizes_hw[2 * n], wn = sizes_hw[2 * n + 1];
+    RTPE_REQUIRE(hn >= 32 && wn >= 32, "mixed_table_fill: image %d is %d x %d, both sides must be at least 32", n, hn, wn);
+    RTPE_REQUIRE(hn <= Hc && wn <= Wc, "mixed_table_fill: image %d is %d x %d, larger than the %d x %d canvas", n, hn, wn, Hc, Wc);
+  }
+  for (int d = 0; d < RTPE_MIXED_LEVELS; ++d)
+    for (int n = 0; n < N; ++n) {
+      table[((size_t)d * N + n) * 2] = extent(sizes_hw[2 * n], d);
+      table[((size_t)d * N + n) * 2 + 1] = extent(sizes_hw[2 * n + 1], d);
+    }
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_hrnet_mixed_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_t Hc, int32_t Wc, size_t* bytes) {
+  RTPE_REQUIRE(h != nullptr && bytes != nullptr, "mixed_workspace_bytes: null argument");
+  {
+    const int rc = check_shape(h, N, Hc, Wc, "mixed_workspace_bytes", true);
+    if (rc != RTPE_OK) return rc;
+  }
+  std::vector<size_t> offs;
+  slot_layout(h, N, Hc, Wc, &offs, bytes);
+  *bytes = align_up(*bytes, 256) + mixed_table_bytes(N);
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t Hc, int32_t Wc,
+                                        const int32_t* sizes_hw, int32_t* table_pinned, int32_t table_ints, void* preds,
+                                        void* refined, int32_t out_dtype, void* workspace, size_t workspace_bytes, void* stream,
+                                        uint32_t flags) {
+  RTPE_REQUIRE(h && x && workspace && sizes_hw && table_pinned, "forward_mixed: null argument");
+  RTPE_REQUIRE((flags & ~(uint32_t)RTPE_FWD_NO_LANES) == 0, "forward_mixed: unknown flag bits 0x%x", flags);
+  RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F32, "forward_mixed: the outputs are float32 buffers");
+  // everything that can be refused is refused here, before the table leaves the host
+  int rc = check_shape(h, N, Hc, Wc, "forward_mixed", true);
+  if (rc != RTPE_OK) return rc;
+  rc = rtpe_mixed_table_fill(sizes_hw, N, Hc, Wc, table_pinned, table_ints);
+  if (rc != RTPE_OK) return rc;
+  std::vector<size_t> offs;
+  size_t ws_need = 0;
+  slot_layout(h, N, Hc, Wc, &offs, &ws_need);
+  ws_need = align_up(ws_need, 256);
+  if (ws_need + mixed_table_bytes(N) > workspace_bytes) {
+    set_error("forward_mixed: workspace %zu < %zu", workspace_bytes, ws_need + mixed_table_bytes(N));
+    return RTPE_E_NOMEM;
+  }
+  RTPE_REQUIRE(((uintptr_t)workspace & 255) == 0, "forward_mixed: workspace must be 256-byte aligned");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int32_t* table_dev = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + ws_need);
+  {
+    DeviceGuard guard(h->device);
+    RTPE_HIP_CHECK(guard.err);
+    // in stream order, from the caller's pinned block: nothing blocks, nothing is allocated
+    RTPE_HIP_CHECK(hipMemcpyAsync(table_dev, table_pinned, (size_t)RTPE_MIXED_LEVELS * 2 * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  return run(h, x, x_dtype, N, Hc, Wc, preds, refined, out_dtype, workspace, ws_need, s, nullptr, 0, nullptr, nullptr, flags, table_dev);
 }
 
 // ---- single-layer entry (layer-level parity tests) -------------------------

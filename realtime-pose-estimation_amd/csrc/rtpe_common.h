@@ -168,7 +168,17 @@ struct ConvArgs {
   // several sub-launches in ONE grid (one-workgroup-per-tile kernel): the 4 sub-pixel classes of the transposed
   // conv.  Class c uses w_c[c], lo_yc/lo_xc[c], oy_c/ox_c[c]; everything else is common.  0 = a plain launch
   int n_cls;
-  const _Float16* w_c[4];
+  // one-workgroup-per-tile kernel, mixed-size batches (rtpe_hip_mixed.h; never a merged transposed conv): mixed = 1 and
+  // ext_in / ext_out = device rows of the extent table, (h, w) of every image at the level of the input / of the output.
+  // They mask reads and stores; H_in, W_in, H_full, W_full (the canvas) address.  0: the canvas extents do both
+  int mixed;
+  union {
+    const _Float16* w_c[4];
+    struct {
+      const int* ext_in;
+      const int* ext_out;
+    };
+  };
   int lo_yc[4], lo_xc[4], oy_c[4], ox_c[4];
   int buf_bytes;         // streaming kernel: bytes of one LDS tile buffer
   int n_bufs;            // streaming kernel: halo tile buffers (2 or 3)
@@ -184,6 +194,10 @@ struct ConvArgs {
   int ablate;            // profiling ablations (RTPE_STREAM_ABL): 1 skip MFMA k-loops, 2 skip residual loads + output stores, 4 skip halo DMA
   unsigned long long* dbg;  // diagnostic builds only (-DRTPE_CONV_STAMPS): per-segment cycle sums
 };
+// (the block is a kernel argument: `mixed` sits in what was padding and the table rows share the words of w_c, so that the
+// kernels of every other forward see the layout they always had - the one-workgroup-per-tile kernel is bound by its scalar
+// registers, 16 more bytes of arguments moved the register allocation of a dozen instantiations)
+static_assert(sizeof(ConvArgs) == 464, "ConvArgs: the layout of the kernel argument block moved");
 
 struct ConvPlan {       // weight-layout half of the plan (fixed at create time)
   int mt;               // cout tiles (x16) per wave = per workgroup
@@ -285,6 +299,10 @@ struct FuseArgs {
   // nearest-to-size rule (nearest_src) instead of the shift by term_up[t]
   int nearest;
   int term_h[4], term_w[4];
+  // mixed-size batches (nearest only): (h, w) of every image at the level of the output / of term t; H, W, term_h, term_w
+  // (the canvas) address.  nullptr: one size for all images
+  const int* ext_out;
+  const int* ext_term[4];
 };
 int fuse_launch(const FuseArgs& a, hipStream_t s);
 bool fuse_nearest_supports(int N, int H, int W, int C, int f32);
@@ -298,6 +316,7 @@ struct StemArgs {
   _Float16* y;  // NHWC (N,H/2,W/2,64)
   int N, H, W, out_ld;
   int f32;      // 1: fp32 weights / output, no intermediate rounding
+  const int* ext;   // mixed-size batches: (h, w) of every input image inside the H x W canvas; nullptr: H x W
 };
 int stem_launch(const StemArgs& a, hipStream_t s);
 
@@ -323,18 +342,22 @@ int stem_fused_launch(const StemFusedArgs& a, hipStream_t s);
 
 // ---- student ops (student_ops.hip), NHWC ------------------------------
 int cast_launch(const _Float16* x, int in_ld, float* y, int out_ld, int C, size_t pixels, hipStream_t s);
-int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s);
+// ext (avgpool, se): mixed-size batches - (h, w) of every image of the input map inside the H x W canvas (se: HW = H * W, W = Wc)
+int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s, const int* ext = nullptr);
 int se_launch(const float* x, int in_ld, int C, int hid, int N, int HW, const float* w, float* gate, int gate_ld,
-              hipStream_t s);
+              hipStream_t s, const int* ext = nullptr, int Wc = 0);
 int cam_combine_launch(const float* hdc, int hdc_ld, const float* res, int res_ld, const float* gate, int gate_ld,
                        float* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s);
 int sigmoid_add_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C,
                        size_t pixels, float* att_out, hipStream_t s);
 // the fp16 forms (the half body of AttentionStudent): rows of 8 channels per 16 bytes, fp32 arithmetic, fp16 roundings where
 // PyTorch-CPU's half ops have them; the SE weights stay fp32 values, att_out stays an fp32 map
-int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s);
+int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s, const int* ext = nullptr);
 int se_launch(const _Float16* x, int in_ld, int C, int hid, int N, int HW, const float* w, _Float16* gate, int gate_ld,
-              hipStream_t s);
+              hipStream_t s, const int* ext = nullptr, int Wc = 0);
+// mixed-size batches: zero every element of the two fp32 NCHW outputs (N, C, H, W) that lies outside its image's h x w
+int mask_outputs_launch(float* y0, int C0, int H0, int W0, const int* ext0, float* y1, int C1, int H1, int W1, const int* ext1,
+                        int N, hipStream_t s);
 int cam_combine_launch(const _Float16* hdc, int hdc_ld, const _Float16* res, int res_ld, const _Float16* gate, int gate_ld,
                        _Float16* y, int out_ld, int C, int N, size_t pix_per_image, hipStream_t s);
 int sigmoid_add_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C,

@@ -64,8 +64,11 @@ template <typename T> struct Row {           // 16 bytes of a channel row, as fp
 
 // AvgPool2d(kernel_size=3, stride=2, padding=1, count_include_pad=False), students.py:657-666
 // fp16: the window is summed and divided in fp32, one rounding (ATen's avg_pool2d accumulates a half input in float)
+// ext (mixed-size batches): (h, w) of every image inside the H x W canvas - the window and its divisor count the taps inside
+// the image, outputs exist up to ceil(h / 2) x ceil(w / 2); H, W, Ho, Wo of the canvas address
 template <typename T>
-__global__ void __launch_bounds__(256) avgpool_kernel(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W) {
+__global__ void __launch_bounds__(256) avgpool_kernel(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W,
+                                                      const int* ext) {
   constexpr int EN = Elem<T>::N;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int c4 = C / EN;
@@ -77,16 +80,21 @@ __global__ void __launch_bounds__(256) avgpool_kernel(const T* x, int in_ld, T* 
     p /= Wo;
     const int oy = (int)(p % Ho);
     const int n = (int)(p / Ho);
+    int Hm = H, Wm = W;
+    if (ext != nullptr) {
+      Hm = ext[2 * n]; Wm = ext[2 * n + 1];
+      if (oy >= ((Hm + 1) >> 1) || ox >= ((Wm + 1) >> 1)) continue;
+    }
     Row<T> s;
 #pragma unroll
     for (int j = 0; j < EN; ++j) s.v[j] = 0.f;
     int cnt = 0;
     for (int ky = 0; ky < 3; ++ky) {
       const int iy = 2 * oy - 1 + ky;
-      if ((unsigned)iy >= (unsigned)H) continue;
+      if ((unsigned)iy >= (unsigned)Hm) continue;
       for (int kx = 0; kx < 3; ++kx) {
         const int ix = 2 * ox - 1 + kx;
-        if ((unsigned)ix >= (unsigned)W) continue;
+        if ((unsigned)ix >= (unsigned)Wm) continue;
         const Row<T> v = Row<T>::load(x + (((size_t)n * H + iy) * W + ix) * in_ld + c);
 #pragma unroll
         for (int j = 0; j < EN; ++j) s.v[j] += v.v[j];
@@ -105,19 +113,25 @@ __global__ void __launch_bounds__(256) avgpool_kernel(const T* x, int in_ld, T* 
 // fp16 rounds the mean (an fp32 sum divided by HW), each Linear behind its bias, and the sigmoid
 constexpr int kSeMaxC = 512, kSeMaxHid = 128;
 template <typename T>
+// ext (mixed-size batches): image n's map is h x w inside a canvas of HW pixels with rows of Wc - the loops walk the image's
+// own row-major pixel index p < h * w, as they would on the image alone (same fp32 summation order, same bits), and map it
+// to the canvas pixel (p / w) * Wc + p % w; the mean divides by h * w
 __global__ void __launch_bounds__(256) se_kernel(const T* x, int in_ld, int C, int hid, int HW, const float* w, T* gate,
-                                                 int gate_ld) {
+                                                 int gate_ld, const int* ext, int Wc) {
   __shared__ float mean[kSeMaxC];
   __shared__ float part[4 * kSeMaxC];
   __shared__ float hbuf[kSeMaxHid];
   const int n = blockIdx.x;
   const T* xi = x + (size_t)n * HW * in_ld;
+  const int wm = ext != nullptr ? ext[2 * n + 1] : 0;
+  if (ext != nullptr) HW = ext[2 * n] * wm;
+  auto canvas = [&](int p) { return ext != nullptr ? (p / wm) * Wc + (p - (p / wm) * wm) : p; };
   if constexpr (sizeof(T) == 4) {
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // each wave sums a quarter of the pixels; lanes stride over channels
     for (int c = lane; c < C; c += 64) {
       float s = 0.f;
-      for (int p = wv; p < HW; p += 4) s += xi[(size_t)p * in_ld + c];
+      for (int p = wv; p < HW; p += 4) s += xi[(size_t)canvas(p) * in_ld + c];
       part[wv * kSeMaxC + c] = s;
     }
     __syncthreads();
@@ -132,7 +146,7 @@ __global__ void __launch_bounds__(256) se_kernel(const T* x, int in_ld, int C, i
 #pragma unroll
       for (int j = 0; j < 8; ++j) s.v[j] = 0.f;
       for (int p = g; p < HW; p += G) {
-        const Row<T> v = Row<T>::load(xi + (size_t)p * in_ld + o * 8);
+        const Row<T> v = Row<T>::load(xi + (size_t)canvas(p) * in_ld + o * 8);
 #pragma unroll
         for (int j = 0; j < 8; ++j) s.v[j] += v.v[j];
       }
@@ -330,6 +344,21 @@ __global__ void __launch_bounds__(256) rgb_to_alt_kernel(const float* src, float
   }
 }
 
+// mixed-size batches: every element of the two fp32 NCHW outputs outside its image's own h x w becomes 0.0 (whatever the
+// forward left there: tiles outside an image are never computed, sigmoid_add runs over the whole canvas)
+__global__ void __launch_bounds__(256) mask_outputs_kernel(float* y0, int C0, int H0, int W0, const int* ext0, float* y1,
+                                                           int C1, int H1, int W1, const int* ext1, int N) {
+  const size_t t0 = (size_t)N * C0 * H0 * W0, t1 = (size_t)N * C1 * H1 * W1;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < t0 + t1; i += (size_t)gridDim.x * 256) {
+    const bool second = i >= t0;
+    const size_t k = second ? i - t0 : i;
+    const int C = second ? C1 : C0, H = second ? H1 : H0, W = second ? W1 : W0;
+    const int* ext = second ? ext1 : ext0;
+    const int x = (int)(k % W), y = (int)((k / W) % H), n = (int)(k / ((size_t)W * H * C));
+    if (y >= ext[2 * n] || x >= ext[2 * n + 1]) (second ? y1 : y0)[k] = 0.f;
+  }
+}
+
 static unsigned grid_for(size_t total) {
   size_t b = (total + 255) / 256;
   if (b > 256 * 16) b = 256 * 16;
@@ -344,37 +373,38 @@ int cast_launch(const _Float16* x, int in_ld, float* y, int out_ld, int C, size_
 }
 
 template <typename T>
-static int avgpool_launch_t(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
+static int avgpool_launch_t(const T* x, int in_ld, T* y, int out_ld, int C, int N, int H, int W, hipStream_t s, const int* ext) {
   constexpr int EN = Elem<T>::N;
   RTPE_REQUIRE(C % EN == 0 && in_ld % EN == 0 && out_ld % EN == 0, "avgpool: channel counts must be multiples of %d", EN);
   const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / EN);
-  hipLaunchKernelGGL(avgpool_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, x, in_ld, y, out_ld, C, N, H, W);
+  hipLaunchKernelGGL(avgpool_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, x, in_ld, y, out_ld, C, N, H, W, ext);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
 
-int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
-  return avgpool_launch_t<float>(x, in_ld, y, out_ld, C, N, H, W, s);
+int avgpool_launch(const float* x, int in_ld, float* y, int out_ld, int C, int N, int H, int W, hipStream_t s, const int* ext) {
+  return avgpool_launch_t<float>(x, in_ld, y, out_ld, C, N, H, W, s, ext);
 }
 
-int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s) {
-  return avgpool_launch_t<_Float16>(x, in_ld, y, out_ld, C, N, H, W, s);
+int avgpool_launch(const _Float16* x, int in_ld, _Float16* y, int out_ld, int C, int N, int H, int W, hipStream_t s,
+                   const int* ext) {
+  return avgpool_launch_t<_Float16>(x, in_ld, y, out_ld, C, N, H, W, s, ext);
 }
 
 int se_launch(const float* x, int in_ld, int C, int hid, int N, int HW, const float* w, float* gate, int gate_ld,
-              hipStream_t s) {
+              hipStream_t s, const int* ext, int Wc) {
   RTPE_REQUIRE(C <= kSeMaxC && hid <= kSeMaxHid && C > 0 && hid > 0, "se: C=%d hidden=%d unsupported", C, hid);
-  hipLaunchKernelGGL(se_kernel<float>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld);
+  hipLaunchKernelGGL(se_kernel<float>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld, ext, Wc);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
 
 // fp16: the rows of x are read in 16-byte pieces up to the piece that holds channel C - 1
 int se_launch(const _Float16* x, int in_ld, int C, int hid, int N, int HW, const float* w, _Float16* gate, int gate_ld,
-              hipStream_t s) {
+              hipStream_t s, const int* ext, int Wc) {
   RTPE_REQUIRE(C <= kSeMaxC && hid <= kSeMaxHid && C > 0 && hid > 0, "se: C=%d hidden=%d unsupported", C, hid);
   RTPE_REQUIRE(in_ld % 8 == 0 && in_ld >= (C + 7) / 8 * 8 && gate_ld >= C, "se: rows of %d and %d halves for C=%d", in_ld, gate_ld, C);
-  hipLaunchKernelGGL(se_kernel<_Float16>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld);
+  hipLaunchKernelGGL(se_kernel<_Float16>, dim3(N), dim3(256), 0, s, x, in_ld, C, hid, HW, w, gate, gate_ld, ext, Wc);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
@@ -420,6 +450,17 @@ int sigmoid_add_launch(const float* att, int att_ld, const float* x, int x_ld, f
 int sigmoid_add_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C,
                        size_t pixels, float* att_out, hipStream_t s) {
   return sigmoid_add_launch_t<_Float16>(att, att_ld, x, x_ld, y, out_ld, C, pixels, att_out, s);
+}
+
+int mask_outputs_launch(float* y0, int C0, int H0, int W0, const int* ext0, float* y1, int C1, int H1, int W1, const int* ext1,
+                        int N, hipStream_t s) {
+  RTPE_REQUIRE(ext0 && ext1 && N > 0 && (y0 || C0 == 0) && (y1 || C1 == 0) && C0 >= 0 && C1 >= 0 && H0 > 0 && W0 > 0 && H1 > 0 && W1 > 0,
+               "mask_outputs: bad argument");
+  if (C0 + C1 == 0) return RTPE_OK;
+  const size_t total = (size_t)N * C0 * H0 * W0 + (size_t)N * C1 * H1 * W1;
+  hipLaunchKernelGGL(mask_outputs_kernel, dim3(grid_for(total)), dim3(256), 0, s, y0, C0, H0, W0, ext0, y1, C1, H1, W1, ext1, N);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
 }
 
 int gate_mul_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C, size_t pixels,

@@ -242,6 +242,17 @@ _SIGS_ANYSIZE = {
     "rtpe_hrnet_get_any_size": (c_int32, [c_void_p, POINTER(c_int32)]),
 }
 EXPORTS_ANYSIZE = tuple(_SIGS_ANYSIZE)  # those of include/rtpe_hip_anysize.h, likewise
+# one forward over images of different sizes (include/rtpe_hip_mixed.h): the extent table and the forward on a canvas
+MIXED_LEVELS = 6
+_SIGS_MIXED = {
+    "rtpe_mixed_table_ints": (c_int32, [c_int32, POINTER(c_int32)]),
+    "rtpe_mixed_table_fill": (c_int32, [POINTER(c_int32), c_int32, c_int32, c_int32, POINTER(c_int32), c_int32]),
+    "rtpe_hrnet_mixed_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_hrnet_forward_mixed": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                           c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t,
+                                           c_void_p, c_uint32]),
+}
+EXPORTS_MIXED = tuple(_SIGS_MIXED)      # those of include/rtpe_hip_mixed.h, likewise
 _lib = None
 
 
@@ -265,7 +276,8 @@ def lib():
             raise RuntimeError("rtpe: cannot load %s: %s" % (LIB_PATH, e)) from e
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
-                list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()):
+                list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
+                list(_SIGS_MIXED.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -537,6 +537,9 @@ class StudentPipeline(TeacherPipeline):
     callable and two-step delay; ``on_forward(k, batch)`` gets the batch as it was given and returns ``(att, det)``.
     One decode size per batch.  ``match_on`` as for ``TeacherPipeline``; ``gather`` is inherited.
 
+    Images of different sizes: ``call_mixed(images)`` runs ONE forward over all of them (``AttentionStudent.forward_mixed``)
+    and decodes each at its own size; ``stream()`` and ``__call__`` take one size per batch and refuse a mixed batch.
+
     There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
 
     def __init__(self, model, parser=None, device=None, match_on=None, flip_test=False, scale_factors=None, ags=False,
@@ -547,6 +550,10 @@ class StudentPipeline(TeacherPipeline):
         super().__init__(model, parser, device, match_on=match_on)
 
     def _decode_hw(self, out_hw, images):
+        # (the first thing ``__call__`` and every step of ``stream()`` do with a batch, before any GPU work)
+        if self._is_mixed(images):
+            raise ValueError("StudentPipeline: a mixed-size batch (a list of (3, h, w) images, a (canvas, sizes) pair) is "
+                             "neither streamed nor decoded at one size; use call_mixed")
         hw = super()._decode_hw(out_hw, images)
         if hw is not None and len(hw) and hasattr(hw[0], "__len__"):
             raise ValueError("StudentPipeline: one decode size (h, w) per batch; per-image sizes are for the teacher's "
@@ -568,6 +575,39 @@ class StudentPipeline(TeacherPipeline):
         det = outs[1].float()
         J = det.shape[1] - 1
         return self.parser.lowres_topk_shared(det[:, :J], det[:, J:], hw)
+
+    @staticmethod
+    def _is_mixed(batch):
+        """a list of (3, h, w) images or a (canvas, sizes) pair - what ``call_mixed`` / ``forward_mixed`` take"""
+        if not isinstance(batch, (list, tuple)) or not batch:
+            return False
+        if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
+            return True
+        return len(batch) == 2 and not torch.is_tensor(batch[1]) and batch[1] is not None
+
+    @torch.no_grad()
+    def call_mixed(self, images, image_ids=None):
+        """images: a list of (3, h_n, w_n) tensors on the GPU, any sizes >= 32 -> per image what ``self(x_n[None])``
+        returns for it: ``pack_mixed``, ONE ``forward_mixed``, then every image decoded on its own with
+        ``parse_lowres_shared`` at its own (h_n, w_n) from a contiguous copy of its region of ``det``.  (A batched decode
+        of a mixed batch needs a sampler with per-image input extents, which no entry has yet.)  With ``image_ids`` (N
+        ints; ``match_on="device"``): one (1, RECORD_FLOATS) record tensor per image."""
+        from .students import pack_mixed, unpack_mixed
+        if not hasattr(self.model, "forward_mixed"):
+            raise ValueError("StudentPipeline.call_mixed: the model has no forward_mixed")
+        canvas, sizes = pack_mixed(images)
+        if image_ids is not None and len(image_ids) != len(sizes):
+            raise ValueError("StudentPipeline.call_mixed: %d image ids for %d images" % (len(image_ids), len(sizes)))
+        records = [None if image_ids is None else self.parser.check_records(1, ([image_ids[n]], None))
+                   for n in range(len(sizes))]
+        att, det = self.model.forward_mixed(canvas, sizes)
+        out = []
+        for n, (_, d) in enumerate(unpack_mixed(att, det, sizes)):
+            d = d.unsqueeze(0).float().contiguous()
+            J = d.shape[1] - 1
+            res = self.parser.parse_lowres_shared(d[:, :J], d[:, J:], sizes[n], records=records[n])
+            out.append(res if records[n] is not None else res[0])
+        return out
 
     @torch.no_grad()
     def __call__(self, images, out_hw=None, alt=None, image_ids=None, xform=None):

@@ -24,7 +24,48 @@ import torch
 
 from . import _native as nat
 from .third_party.fp16_utils.fp16util import BN_convert_float, network_to_half, tofp16
-from .third_party.pose_higher_hrnet import BN_MOMENTUM, Bottleneck, CompiledModule, ProgramBuilder
+from .third_party.pose_higher_hrnet import BN_MOMENTUM, Bottleneck, CompiledModule, ProgramBuilder, check_mixed_sizes
+
+
+def pack_mixed(images, canvas_hw=None):
+    """images of different sizes -> one canvas for ``AttentionStudent.forward_mixed``.
+
+    ``images``: a list of (3, h_n, w_n) tensors on one device, h_n, w_n >= 32.  Returns ``(canvas, sizes)``: canvas
+    (N, 3, Hc, Wc) float32 with image n at ``[n, :, :h_n, :w_n]`` and zeros elsewhere, ``sizes = [(h_n, w_n)]``.
+    ``Hc, Wc`` are the largest h_n and w_n, or ``canvas_hw`` (not smaller than those)."""
+    images = list(images)
+    if not images:
+        raise ValueError("pack_mixed: no images")
+    for n, im in enumerate(images):
+        if not torch.is_tensor(im) or im.dim() != 3 or im.shape[0] != 3:
+            raise ValueError("pack_mixed: image %d must be a (3, h, w) tensor" % n)
+        if im.device != images[0].device:
+            raise ValueError("pack_mixed: images on different devices (%s and %s)" % (images[0].device, im.device))
+    sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
+    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
+    if canvas_hw is not None:
+        ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
+        if ch < Hc or cw < Wc:
+            raise ValueError("pack_mixed: a %d x %d canvas does not hold images of up to %d x %d" % (ch, cw, Hc, Wc))
+        Hc, Wc = ch, cw
+    sizes = check_mixed_sizes(sizes, len(images), Hc, Wc)
+    canvas = torch.zeros((len(images), 3, Hc, Wc), dtype=torch.float32, device=images[0].device)
+    for n, (im, (h, w)) in enumerate(zip(images, sizes)):
+        canvas[n, :, :h, :w] = im
+    return canvas, sizes
+
+
+def unpack_mixed(att, det, sizes):
+    """the output canvases of ``forward_mixed`` -> ``[(att_n, det_n)]``: per image the views
+    ``[n, :, :ceil(h_n / 4), :ceil(w_n / 4)]`` (nothing is copied)"""
+    sizes = check_mixed_sizes(sizes, att.shape[0], att.shape[2] * 4, att.shape[3] * 4)
+    if det.shape[0] != att.shape[0] or det.shape[2:] != att.shape[2:]:
+        raise ValueError("unpack_mixed: att %s and det %s are not one batch" % (tuple(att.shape), tuple(det.shape)))
+    out = []
+    for n, (h, w) in enumerate(sizes):
+        eh, ew = nat.extent(h, 2), nat.extent(w, 2)
+        out.append((att[n, :, :eh, :ew], det[n, :, :eh, :ew]))
+    return out
 
 
 def init_weights(module, init_fn=torch.nn.init.kaiming_normal_, bias_val=0.0):
@@ -262,6 +303,23 @@ class AttentionStudent(CompiledModule):
         att, det = self._engine(x.device).forward(x.float(), torch.float32)
         return att, det
 
+    def forward_mixed(self, canvas, sizes):
+        """one forward over N images of different sizes: ``canvas`` (N,3,Hc,Wc) fp32 on the GPU with image n at
+        ``[n, :, :h_n, :w_n]`` and ``sizes = [(h_n, w_n)]`` (``pack_mixed``) -> (att (N,1,eh,ew), det
+        (N,num_heatmaps+ae_dims,eh,ew)) with eh, ew = the extents of Hc, Wc at 1/4.  Image n's region
+        ``[n, :, :ceil(h_n/4), :ceil(w_n/4)]`` holds the bits of ``self(x_n[None])``; every element outside the regions is
+        0.0, whatever the canvas holds outside the images (``unpack_mixed`` gives the regions).  Both bodies.
+
+        Every kernel addresses by the canvas extents and masks by image n's own ("Mixed-size
+        batches").  A mixed batch always runs the general kernels on default launch shapes and is never autotuned,
+        whatever the canvas size."""
+        if canvas.dim() != 4 or canvas.shape[1] != 3:
+            raise ValueError("AttentionStudent.forward_mixed: expected a canvas (N,3,Hc,Wc), got %s" % (tuple(canvas.shape),))
+        sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])     # (before any GPU work)
+        self._check_inference(canvas, "AttentionStudent.forward_mixed")
+        att, det = self._engine(canvas.device).forward_mixed(canvas.float(), sizes)
+        return att, det
+
 
 class AttentionStudentSteps(CompiledModule):
     """reference :786-1063: the student that ``distillation.py:137`` trains.  The stem features get the
@@ -365,6 +423,10 @@ class AttentionStudentSteps(CompiledModule):
         x = self.steps[2].emit(b, x)
         b.conv(x, self.steps[3], None, out_flag=nat.F_OUT_REFINED, nhwc=False)
         return b.finish()
+
+    def forward_mixed(self, canvas, sizes):
+        raise NotImplementedError("rtpe: AttentionStudentSteps has no mixed-size forward: its second input (aux pack, "
+                                  "resize) and its 5x5 stem are not masked per image; use AttentionStudent")
 
     def forward(self, x, out_hw=None, alt=None, att_divisor=None):
         """x (N,3,H,W) fp32 on the GPU (any H, W >= 32), alt (N,3,H,W) fp32: the image in the alternative

@@ -1,0 +1,142 @@
+"""What one forward over a batch of images of different sizes buys the students on a stream of native-size images, on
+one GPU.
+
+The students take an image as it is, so two images share a forward only if they have the same (H, W): a stream of COCO
+images runs one forward per image, the launch-bound regime.  ``AttentionStudent.forward_mixed``
+runs N images of different sizes in one canvas.  In one process, on the seeded mix of COCO-like sizes that
+``tools/mixed_size_bench.py`` draws (``mix_sizes``), with the config-4 student (``AttentionStudent(inplanes=100)``, seeded
+W1 weights), fp32 body and half body:
+
+  A  the per-image loop ``stu(x_n[None])`` over all images - all there was before ``forward_mixed``: the baseline;
+  B  ``forward_mixed`` on batches of --batch images, the list sorted by area before it is cut into batches, the
+     canvases packed beforehand (A's inputs are ready too).
+
+Both are run once first (workspaces allocated, the multiple-of-32 shapes of A autotuned; B is compared with A bit for bit on
+every image there), then timed A B B A ... (--repeats passes each, a pass = every image once, one synchronisation at its
+end): images/s, medians beside every run, the forward time per batch of B and per image of A, and the canvas waste (canvas
+pixels over the sum of the image pixels).  One more pass of B packs its canvases inside the timed region
+(``pack_mixed``).  Forward only: the decode of a mixed batch runs per image (``StudentPipeline.call_mixed``) and is not
+part of this measurement.
+
+Prints one JSON line per model (--out FILE also writes them).  Needs a GPU; there is no fallback.
+
+    python tools/student_mixed_bench.py [--images 256] [--batch 32] [--repeats 4] [--out profiles/student_mixed_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "realtime-pose-estimation_amd"), os.path.join(ROOT, "tools")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=256, help="images of the seeded mix")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--repeats", type=int, default=4, help="timed passes per mode, interleaved A B B A ...")
+    ap.add_argument("--out", help="also write the JSON lines to this file")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("student_mixed_bench: no GPU (the forward runs on the HIP path only)")
+    import __graft_entry__ as entry
+    entry.build()
+    from mixed_size_bench import mix_sizes
+    from oracle import synth
+    from rtpe import _native as nat
+    from rtpe.students import AttentionStudent, pack_mixed, unpack_mixed
+    torch.set_num_threads(nat.host_threads(8))
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    with open(os.path.join(ROOT, "tests", "golden", "student_shapes.json")) as f:
+        shapes = {k: tuple(v) for k, v in json.load(f)["shapes"].items()}
+    sizes = mix_sizes(args.images)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    images = [torch.randn(3, h, w, generator=g, device=dev) for h, w in sizes]
+    order = sorted(range(len(sizes)), key=lambda i: (sizes[i][0] * sizes[i][1], sizes[i]))
+    chunks = [order[o:o + args.batch] for o in range(0, len(order), args.batch)]
+    image_px = sum(h * w for h, w in sizes)
+
+    def timed(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize(dev)
+        return res, time.perf_counter() - t0
+
+    lines = []
+    for body_half in (False, True):
+        stu = AttentionStudent(None, "cpu", 100, 17, 1, True, None, False, body_half=body_half).eval()
+        stu.load_state_dict(synth.make_state_dict(shapes, 3, "W1"), strict=True)
+        stu = stu.to(dev)
+        packed = [pack_mixed([images[i] for i in c]) for c in chunks]
+        canvas_px = sum(c.shape[0] * c.shape[2] * c.shape[3] for c, _ in packed)
+
+        def loop_a(keep=False):
+            out = []
+            with torch.no_grad():
+                for x in images:
+                    r = stu(x[None])
+                    if keep:
+                        out.append(r)
+            return out
+
+        def loop_b(keep=False, pack=False):
+            out = []
+            with torch.no_grad():
+                for c, (canvas, sz) in zip(chunks, packed):
+                    if pack:
+                        canvas, sz = pack_mixed([images[i] for i in c])
+                    r = stu.forward_mixed(canvas, sz)
+                    if keep:
+                        out.append(r)
+            return out
+        ra, first_a = timed(lambda: loop_a(True))
+        rb, first_b = timed(lambda: loop_b(True))
+        same = True
+        for c, (att, det), (_, sz) in zip(chunks, rb, packed):
+            for i, (a, d) in zip(c, unpack_mixed(att, det, sz)):
+                same = same and bool(torch.equal(a, ra[i][0][0])) and bool(torch.equal(d, ra[i][1][0]))
+        del ra, rb
+        runs = {"A": [], "B": []}
+        for r in range(args.repeats):
+            for m in (("A", "B") if r % 2 == 0 else ("B", "A")):
+                _, dt = timed(loop_a if m == "A" else loop_b)
+                runs[m].append(dt)
+        _, dt_pack = timed(lambda: loop_b(pack=True))
+        med = {m: float(np.median(v)) for m, v in runs.items()}
+        lines.append({
+            "metric": "student_mixed_batch_forward", "model": "AttentionStudent(inplanes=100)", "weights": "W1",
+            "body": "half" if body_half else "fp32", "device": torch.cuda.get_device_name(dev), "images": len(images),
+            "distinct_sizes": len(set(sizes)), "batch": args.batch, "batches_per_pass": len(chunks), "repeats": args.repeats,
+            "order": "A B B A", "results_bit_identical": bool(same),
+            "A_per_image_loop": {"img_s": round(len(images) / med["A"], 1),
+                                 "img_s_runs": [round(len(images) / t, 1) for t in runs["A"]],
+                                 "forward_ms_per_image": round(med["A"] * 1e3 / len(images), 4),
+                                 "first_pass_s": round(first_a, 2)},
+            "B_forward_mixed": {"img_s": round(len(images) / med["B"], 1),
+                                "img_s_runs": [round(len(images) / t, 1) for t in runs["B"]],
+                                "forward_ms_per_batch": round(med["B"] * 1e3 / len(chunks), 3),
+                                "first_pass_s": round(first_b, 2),
+                                "img_s_with_pack_mixed": round(len(images) / dt_pack, 1)},
+            "canvas_waste": round(canvas_px / image_px, 4),
+            "speedup_B_over_A": round(med["A"] / med["B"], 3)})
+        del stu, packed
+        torch.cuda.empty_cache()
+    for ln in lines:
+        print(json.dumps(ln))
+    if args.out:
+        with open(args.out, "w") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
