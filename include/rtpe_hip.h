@@ -698,7 +698,8 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
  * pre-processing (a whole chunk of images warped at every test scale), declared in rtpe_hip_warp.h, and those of the
  * shared-tag decode (the dual-head students: one tag map per image), declared in rtpe_hip_shared.h, and the layer-level entry
  * of the 1x1 pair kernel, declared in rtpe_hip_pair.h, and those of the device-resident keypoint records, declared in
- * rtpe_hip_records.h. */
+ * rtpe_hip_records.h, and those of the one-pass decode of a mixed-size batch from its canvas, declared in
+ * rtpe_hip_mixdec.h. */
 
 #ifdef __cplusplus
 }
@@ -712,5 +713,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_noproj.h"
 #include "rtpe_hip_anysize.h"
 #include "rtpe_hip_mixed.h"
+#include "rtpe_hip_mixdec.h"
 
 #endif /* RTPE_HIP_H */

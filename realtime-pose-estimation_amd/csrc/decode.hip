@@ -148,6 +148,15 @@ struct NetSizesTag {        // the per-joint tag maps of the same images, D == 1
   const SizeEntry* tab;
 };
 
+// NetSizesTag with ONE tag plane per image, shared by its J joints (a mixed-size batch of the dual-head students decoded
+// from its canvas, include/rtpe_hip_mixdec.h): plane_tag gives a SharedBilinearTag with the axes of the image's entry,
+// so the (image * J + joint) plane index selects the image's plane and the joint's tap order there, and only there.
+// m.sh / m.sw are the canvas extents (the pitch); the image's own extents are the n_in of its entry's axes.
+struct NetMixedTag {
+  BilinearMap m;            // p, img_stride: the shared planes; J: the joints that share one
+  const SizeEntry* tab;
+};
+
 template <class Map> struct PerImageSize { static constexpr bool value = false; };
 template <> struct PerImageSize<NetSizesMap> { static constexpr bool value = true; };
 
@@ -169,6 +178,14 @@ __device__ __forceinline__ const TagMap& plane_tag(const TagMap& t, int) { retur
 __device__ __forceinline__ BilinearTag plane_tag(const NetSizesTag& s, int plane) {
   const SizeEntry* e = s.tab + plane / s.m.J;
   BilinearTag v{s.m};
+  v.m.ay = e->ty;
+  v.m.ax = e->tx;
+  v.m.small = e->small;
+  return v;
+}
+__device__ __forceinline__ SharedBilinearTag plane_tag(const NetMixedTag& s, int plane) {
+  const SizeEntry* e = s.tab + plane / s.m.J;
+  SharedBilinearTag v{s.m};
   v.m.ay = e->ty;
   v.m.ax = e->tx;
   v.m.small = e->small;
@@ -2066,6 +2083,133 @@ extern "C" int rtpe_adjust_refine_fused_topk_sizes_n(const float* hm, int32_t hh
   RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_sizes_n: P_dev is null");
   return decode_adjust_refine("adjust_refine_fused_topk_sizes_n",
                               NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
+                                          table_bytes, max_oh, max_ow, w_enc},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, P_dev, true);
+}
+
+// ---------------------------------------------------------------------------
+// a mixed-size batch of a dual-head student decoded from its canvas (include/rtpe_hip_mixdec.h): NetSizesSrc with ONE
+// tag plane per image (NetSharedSrc's `tg`) and with (hh, hw) / (th, tw) read as the PITCH of the planes - the canvas
+// extents, which only address.  Image n's own extents, which only clamp, are the n_in of its entry's axes
+// (rtpe_decode_mixed_fill); the axes that make_bilinear derives from the pitch are never read (NetSizesMap,
+// NetMixedTag).  Every heat-map kernel is the NetSizesMap instantiation that the `_sizes` entries launch.
+// ---------------------------------------------------------------------------
+struct NetMixedSrc {
+  const float* hm;
+  int32_t hh, hw;
+  int64_t hm_img_stride;
+  const float* tg;
+  int32_t th, tw;
+  int64_t tg_img_stride;
+  int32_t N, J;
+  const void* table;
+  size_t table_bytes;
+  int32_t oh, ow, w_enc;
+  int check(const char* who) const {
+    RTPE_REQUIRE(hm && tg && table, "%s: null argument", who);
+    RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "%s: bad argument (N=%d, J=%d; J <= %d)", who, N, J, kMaxJ);
+    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
+    RTPE_REQUIRE(hm_img_stride >= (int64_t)J * hh * hw && tg_img_stride >= (int64_t)th * tw,
+                 "%s: an image stride is below the size of an image's planes", who);
+    RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "%s: sizes table too small (%zu < %zu bytes)", who,
+                 table_bytes, (size_t)N * sizeof(SizeEntry));
+    RTPE_REQUIRE(w_enc >= ow, "%s: w_enc=%d is below the largest width %d", who, w_enc, ow);
+    RTPE_REQUIRE((int64_t)oh * w_enc <= 0x7fffffff, "%s: y * w_enc + x exceeds 32 bits (max_oh=%d, w_enc=%d)", who, oh,
+                 w_enc);
+    return RTPE_OK;
+  }
+  template <class F>
+  int with_maps(F f) const {
+    const SizeEntry* tab = reinterpret_cast<const SizeEntry*>(table);
+    return f(NetSizesMap{make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow), tab, w_enc},
+             NetMixedTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow), tab}, 1);
+  }
+};
+
+// HOST function.  Entry n: the axes of an image whose maps span heat_hw[n] / tag_hw[n] of planes of pitch (hh, hw) /
+// (th, tw), decoded at out_hw[n].  Everything is checked before the first entry is written: a wrong entry would make
+// the device read outside the planes.
+extern "C" int rtpe_decode_mixed_fill(const int32_t* out_hw, const int32_t* heat_hw, const int32_t* tag_hw, int32_t N,
+                                      int32_t hh, int32_t hw, int32_t th, int32_t tw, void* table, size_t table_bytes,
+                                      int32_t* max_oh, int32_t* max_ow) {
+  RTPE_REQUIRE(out_hw && heat_hw && table && N > 0, "decode_mixed_fill: bad argument");
+  RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0, "decode_mixed_fill: bad shape");
+  RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "decode_mixed_fill: sizes table too small (%zu < %zu bytes)",
+               table_bytes, (size_t)N * sizeof(SizeEntry));
+  if (tag_hw == nullptr) tag_hw = heat_hw;                  // the tag extents are the heat extents
+  int mh = 0, mw = 0;
+  for (int n = 0; n < N; ++n) {
+    RTPE_REQUIRE(out_hw[2 * n] > 0 && out_hw[2 * n + 1] > 0, "decode_mixed_fill: image %d has size %d x %d", n,
+                 out_hw[2 * n], out_hw[2 * n + 1]);
+    RTPE_REQUIRE(heat_hw[2 * n] > 0 && heat_hw[2 * n + 1] > 0 && tag_hw[2 * n] > 0 && tag_hw[2 * n + 1] > 0,
+                 "decode_mixed_fill: image %d has map extents %d x %d (heat), %d x %d (tag)", n, heat_hw[2 * n],
+                 heat_hw[2 * n + 1], tag_hw[2 * n], tag_hw[2 * n + 1]);
+    RTPE_REQUIRE(heat_hw[2 * n] <= hh && heat_hw[2 * n + 1] <= hw,
+                 "decode_mixed_fill: image %d: heat extent %d x %d is above the pitch %d x %d", n, heat_hw[2 * n],
+                 heat_hw[2 * n + 1], hh, hw);
+    RTPE_REQUIRE(tag_hw[2 * n] <= th && tag_hw[2 * n + 1] <= tw,
+                 "decode_mixed_fill: image %d: tag extent %d x %d is above the pitch %d x %d", n, tag_hw[2 * n],
+                 tag_hw[2 * n + 1], th, tw);
+    mh = out_hw[2 * n] > mh ? out_hw[2 * n] : mh;
+    mw = out_hw[2 * n + 1] > mw ? out_hw[2 * n + 1] : mw;
+  }
+  SizeEntry* tab = reinterpret_cast<SizeEntry*>(table);
+  for (int n = 0; n < N; ++n) {
+    SizeEntry e;
+    memset(&e, 0, sizeof(e));
+    e.oh = out_hw[2 * n];
+    e.ow = out_hw[2 * n + 1];
+    e.hy = make_axis(heat_hw[2 * n], e.oh);
+    e.hx = make_axis(heat_hw[2 * n + 1], e.ow);
+    e.ty = make_axis(tag_hw[2 * n], e.oh);
+    e.tx = make_axis(tag_hw[2 * n + 1], e.ow);
+    e.small = small_output(e.oh, e.ow);
+    tab[n] = e;
+  }
+  if (max_oh) *max_oh = mh;
+  if (max_ow) *max_ow = mw;
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_topk_fused_mixed(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
+                                     int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J,
+                                     const void* sizes_table, size_t table_bytes, int32_t max_oh, int32_t max_ow,
+                                     int32_t w_enc, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
+                                     int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_topk("topk_fused_mixed",
+                     NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table, table_bytes,
+                                 max_oh, max_ow, w_enc},
+                     K, nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rtpe_adjust_refine_fused_mixed_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                   const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                   int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
+                                                   int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
+                                                   float* ans_out, const int32_t* person_img, int32_t P,
+                                                   int32_t do_adjust, int32_t do_refine, float* scores,
+                                                   const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                   void* scratch, size_t scratch_bytes, void* stream) {
+  return decode_adjust_refine("adjust_refine_fused_mixed_topk",
+                              NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
+                                          table_bytes, max_oh, max_ow, w_enc},
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
+                               scratch, scratch_bytes, stream}, nullptr, true);
+}
+
+extern "C" int rtpe_adjust_refine_fused_mixed_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
+                                                     const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
+                                                     int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
+                                                     int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
+                                                     float* ans_out, const int32_t* person_img, int32_t P,
+                                                     int32_t do_adjust, int32_t do_refine, float* scores,
+                                                     const float* topk_val, const int32_t* topk_ind, int32_t K,
+                                                     void* scratch, size_t scratch_bytes, void* stream,
+                                                     const int32_t* P_dev) {
+  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_mixed_topk_n: P_dev is null");
+  return decode_adjust_refine("adjust_refine_fused_mixed_topk_n",
+                              NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
                                           table_bytes, max_oh, max_ow, w_enc},
                               {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
                                scratch, scratch_bytes, stream}, P_dev, true);

@@ -253,6 +253,16 @@ _SIGS_MIXED = {
                                            c_void_p, c_uint32]),
 }
 EXPORTS_MIXED = tuple(_SIGS_MIXED)      # those of include/rtpe_hip_mixed.h, likewise
+# one-pass decode of a mixed-size batch from its canvas (include/rtpe_hip_mixdec.h): the table fill with the images' own
+# map extents, and the arguments of the `_sizes` entries with (hh, hw, th, tw) read as the pitch, `tg` one plane per image
+_SIGS_MIXDEC = {
+    "rtpe_decode_mixed_fill": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_size_t, POINTER(c_int32), POINTER(c_int32)]),
+    "rtpe_topk_fused_mixed": (c_int32, list(_SIGS_SIZES["rtpe_topk_fused_sizes"][1])),
+    "rtpe_adjust_refine_fused_mixed_topk": (c_int32, list(_SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes"][1])),
+    "rtpe_adjust_refine_fused_mixed_topk_n": (c_int32, list(_SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes_n"][1])),
+}
+EXPORTS_MIXDEC = tuple(_SIGS_MIXDEC)    # those of include/rtpe_hip_mixdec.h, likewise
 _lib = None
 
 
@@ -277,7 +287,7 @@ def lib():
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
-                list(_SIGS_MIXED.items()):
+                list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -358,6 +358,17 @@ class TeacherPipeline:
         stream that was current when the loop started: that stream is made to wait - on the device - for the event
         behind the record kernel.  The loop body then holds no host wait on decode work: every buffer of such a batch
         is device memory handed out again in stream order, or a pinned block reused only when its upload is done."""
+        def begin(k, x):
+            return x, self._decode_hw(out_hw(k) if callable(out_hw) else out_hw, x)
+        return self._stream_loop(batches, begin, self._stream_forwards, self._stream_topk, on_forward, decode_stream,
+                                 in_flight, exclusive, records)
+
+    def _stream_loop(self, batches, begin, forwards, topk, on_forward, decode_stream, in_flight, exclusive, records):
+        """the loop of ``stream()`` (its docstring), written once for every kind of batch.  A kind is three steps:
+        ``begin(k, batch) -> (batch, hw)`` - the batch as the forwards take it and its decode size(s), every refusal
+        before any GPU work; ``forwards(k, batch, on_forward)`` - the forwards on the current stream -> the tuple of
+        FRESH output tensors the decode reads; ``topk(outs, hw)`` - phase 1 of the decode -> the state that
+        ``lowres_match`` / ``lowres_finish`` take.  A generator."""
         import os
         mode = decode_stream or os.environ.get("RTPE_DECODE_STREAM", "side")
         if mode not in ("side", "same"):
@@ -400,7 +411,7 @@ class TeacherPipeline:
         # ``on_forward`` must return FRESH output tensors for every batch (the plain forward does): the decode of
         # batch k runs on the side stream while F(k+1) runs on the main one, and nothing makes F(k+1) wait for it.
         def run_forwards(k, x):
-            return self._stream_forwards(k, x, on_forward)
+            return forwards(k, x, on_forward)
 
         ms = self.scale_factors is not None
 
@@ -434,7 +445,7 @@ class TeacherPipeline:
         try:
             with torch.no_grad():
                 for k, x in enumerate(batches):
-                    hw_k = self._decode_hw(out_hw(k) if callable(out_hw) else out_hw, x)
+                    x, hw_k = begin(k, x)
                     rec_k = None
                     if records is not None:
                         ids_k, xf_k = records(k)
@@ -453,8 +464,10 @@ class TeacherPipeline:
                                 if other is not fs:
                                     fs.wait_stream(other)
                         after_alone = fs if alone else None
-                        for t in (xs if ms else [x] if torch.is_tensor(x) else x):     # (a pair: StudentPipeline's (x, alt))
-                            t.record_stream(fs)
+                        # (a pair: StudentPipeline's (x, alt), or the (canvas, sizes) of a mixed batch)
+                        for t in (xs if ms else [x] if torch.is_tensor(x) else x):
+                            if torch.is_tensor(t):
+                                t.record_stream(fs)
                         # lanes off for THIS call only (a per-call flag of the ABI: nothing process-wide is touched,
                         # and nothing stays changed while the generator is suspended or if it is abandoned)
                         prev_slot = set_workspace_slot(1 + k % n_fwd)
@@ -482,7 +495,7 @@ class TeacherPipeline:
                     if ms:
                         st = on_decode_stream(P.ms_topk, st_ms, after=f_done)
                     else:
-                        st = on_decode_stream(self._stream_topk, outs, hw, after=f_done, uses=outs)
+                        st = on_decode_stream(topk, outs, hw, after=f_done, uses=outs)
                     st["records_arg"] = rec_k
                     if refine_done is not None:
                         yield finish(refine_done)
@@ -538,7 +551,9 @@ class StudentPipeline(TeacherPipeline):
     One decode size per batch.  ``match_on`` as for ``TeacherPipeline``; ``gather`` is inherited.
 
     Images of different sizes: ``call_mixed(images)`` runs ONE forward over all of them (``AttentionStudent.forward_mixed``)
-    and decodes each at its own size; ``stream()`` and ``__call__`` take one size per batch and refuse a mixed batch.
+    and ONE decode, every image at its own size, straight from the output canvas (``HeatmapParser.parse_lowres_mixed``);
+    ``stream_mixed(batches)`` is the pipelined loop over such batches and ``mixed_batches`` cuts a list of images into them.
+    ``stream()`` and ``__call__`` take one size per batch and refuse a mixed batch.
 
     There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
 
@@ -560,12 +575,17 @@ class StudentPipeline(TeacherPipeline):
                              "plain protocol only")
         return hw
 
-    def _forward(self, batch):
-        x, alt = (batch, None) if torch.is_tensor(batch) else batch
-        out = self.model(x) if alt is None else self.model(x, alt=alt)
-        if not isinstance(out, (list, tuple)) or len(out) != 2 or out[1].dim() != 4 or out[1].shape[1] < 2:
+    @staticmethod
+    def _att_det(out):
+        """what a student's forward returned, checked: ``(att, det)`` with det (N, J + 1, h, w)"""
+        if not isinstance(out, (list, tuple)) or len(out) != 2 or not torch.is_tensor(out[1]) or out[1].dim() != 4 or \
+                out[1].shape[1] < 2:
             raise TypeError("StudentPipeline: the model must return (att, det) with det (N, J + 1, h, w)")
         return out[0], out[1]
+
+    def _forward(self, batch):
+        x, alt = (batch, None) if torch.is_tensor(batch) else batch
+        return self._att_det(self.model(x) if alt is None else self.model(x, alt=alt))
 
     def _stream_forwards(self, k, x, on_forward):
         att, det = on_forward(k, x) if on_forward is not None else self._forward(x)
@@ -585,22 +605,59 @@ class StudentPipeline(TeacherPipeline):
             return True
         return len(batch) == 2 and not torch.is_tensor(batch[1]) and batch[1] is not None
 
+    def _mixed_begin(self, batch):
+        """a mixed batch as ``forward_mixed`` takes it, checked before the forward: a list of (3, h_n, w_n) images is
+        packed (``pack_mixed``, on the current stream), a ``(canvas, sizes)`` pair checked -> ``((canvas, sizes), sizes)``"""
+        from .students import pack_mixed
+        from .third_party.pose_higher_hrnet import check_mixed_sizes
+        if not hasattr(self.model, "forward_mixed"):
+            raise ValueError("StudentPipeline: the model has no forward_mixed")
+        if not self._is_mixed(batch):
+            raise ValueError("StudentPipeline: a mixed-size batch is a list of (3, h, w) images or a (canvas, sizes) pair")
+        if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
+            canvas, sizes = pack_mixed(batch)
+        else:
+            canvas, sizes = batch
+            if not torch.is_tensor(canvas) or canvas.dim() != 4 or canvas.shape[1] != 3:
+                raise ValueError("StudentPipeline: the canvas of a mixed batch is (N,3,Hc,Wc)")
+            sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])
+        return (canvas, sizes), sizes
+
+    def _mixed_forwards(self, k, batch, on_forward):
+        att, det = self._att_det(on_forward(k, batch) if on_forward is not None else self.model.forward_mixed(*batch))
+        if det.shape[0] != batch[0].shape[0]:
+            raise TypeError("StudentPipeline: det %s is not the canvas of the %d images of the batch"
+                            % (tuple(det.shape), batch[0].shape[0]))
+        return att, det
+
+    def _mixed_topk(self, outs, sizes):
+        return self.parser.lowres_topk_mixed(outs[1].float(), sizes)
+
     @torch.no_grad()
-    def call_mixed(self, images, image_ids=None):
+    def call_mixed(self, images, image_ids=None, decode="batch"):
         """images: a list of (3, h_n, w_n) tensors on the GPU, any sizes >= 32 -> per image what ``self(x_n[None])``
-        returns for it: ``pack_mixed``, ONE ``forward_mixed``, then every image decoded on its own with
-        ``parse_lowres_shared`` at its own (h_n, w_n) from a contiguous copy of its region of ``det``.  (A batched decode
-        of a mixed batch needs a sampler with per-image input extents, which no entry has yet.)  With ``image_ids`` (N
-        ints; ``match_on="device"``): one (1, RECORD_FLOATS) record tensor per image."""
+        returns for it: ``pack_mixed``, ONE ``forward_mixed``, then ONE decode of the whole batch straight from the ``det``
+        canvas, every image at its own (h_n, w_n) from its own region (``HeatmapParser.parse_lowres_mixed``: nothing is
+        copied).  ``decode="per_image"``: every image decoded on its own with ``parse_lowres_shared`` from a contiguous copy
+        of its region - N region copies, N sets of launches and 2N host waits in series; the same bits, kept for A/B
+        measurements and as a fallback.  With ``image_ids`` (N ints; ``match_on="device"``): one (1, RECORD_FLOATS) record
+        tensor per image (``"batch"``: views of the one record tensor of the batch)."""
         from .students import pack_mixed, unpack_mixed
+        if decode not in ("batch", "per_image"):
+            raise ValueError("StudentPipeline.call_mixed: decode must be 'batch' or 'per_image', not %r" % (decode,))
         if not hasattr(self.model, "forward_mixed"):
             raise ValueError("StudentPipeline.call_mixed: the model has no forward_mixed")
         canvas, sizes = pack_mixed(images)
         if image_ids is not None and len(image_ids) != len(sizes):
             raise ValueError("StudentPipeline.call_mixed: %d image ids for %d images" % (len(image_ids), len(sizes)))
+        if decode == "batch":
+            records = None if image_ids is None else self.parser.check_records(len(sizes), (image_ids, None))
+            att, det = self._mixed_forwards(0, (canvas, sizes), None)
+            res = self.parser.parse_lowres_mixed(det.float(), sizes, records=records)
+            return res if records is None else [res[n:n + 1] for n in range(len(sizes))]
         records = [None if image_ids is None else self.parser.check_records(1, ([image_ids[n]], None))
                    for n in range(len(sizes))]
-        att, det = self.model.forward_mixed(canvas, sizes)
+        att, det = self._mixed_forwards(0, (canvas, sizes), None)
         out = []
         for n, (_, d) in enumerate(unpack_mixed(att, det, sizes)):
             d = d.unsqueeze(0).float().contiguous()
@@ -608,6 +665,43 @@ class StudentPipeline(TeacherPipeline):
             res = self.parser.parse_lowres_shared(d[:, :J], d[:, J:], sizes[n], records=records[n])
             out.append(res if records[n] is not None else res[0])
         return out
+
+    def stream_mixed(self, batches, on_forward=None, decode_stream=None, in_flight=None, exclusive=None, records=None):
+        """``stream()`` over mixed-size batches: the same software-pipelined loop F(k) R(k-1) T(k) - decode stream,
+        forward streams and workspace slots, ``exclusive``, early stop, two-step delay of the results - with
+        F = ``forward_mixed`` and T = ``HeatmapParser.lowres_topk_mixed`` on the ``det`` canvas.  Every batch is a list of
+        (3, h_n, w_n) images (packed on the caller's stream) or a ``(canvas, sizes)`` pair (``pack_mixed``); every image is
+        decoded at its own size.  ``on_forward(k, (canvas, sizes))`` may replace the forward and returns ``(att, det)``.
+        Yields per batch what ``call_mixed`` returns for it, or with ``records`` (``k -> (image_ids, None)``; needs
+        ``match_on="device"``) the (N, RECORD_FLOATS) record tensor of the batch."""
+        return self._stream_loop(batches, lambda k, x: self._mixed_begin(x), self._mixed_forwards, self._mixed_topk,
+                                 on_forward, decode_stream, in_flight, exclusive, records)
+
+    @staticmethod
+    def mixed_batches(images, batch_size=32):
+        """cut a list of images of different sizes into batches for ``call_mixed`` / ``stream_mixed``: the images
+        sorted by area (so that a canvas wastes little on its smaller images; ties keep the caller's order), then runs
+        of ``batch_size``.  ``images``: (3, h, w) tensors, or anything with such a ``.shape``.  Returns
+        ``(batches, restore)``: ``batches[b]`` the list of images of batch b, and ``restore(results)`` - ``results[b]`` the
+        per-image list that batch b gave - the results of all images in the caller's order.  Pure host function."""
+        images = list(images)
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("StudentPipeline.mixed_batches: batch_size must be at least 1, not %d" % batch_size)
+        order = sorted(range(len(images)), key=lambda i: int(images[i].shape[-2]) * int(images[i].shape[-1]))
+        cuts = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+        def restore(results):
+            results = list(results)
+            if len(results) != len(cuts) or any(len(r) != len(c) for r, c in zip(results, cuts)):
+                raise ValueError("StudentPipeline.mixed_batches: the results %s do not go with batches of %s images"
+                                 % ([len(r) for r in results], [len(c) for c in cuts]))
+            out = [None] * len(images)
+            for r, c in zip(results, cuts):
+                for i, v in zip(c, r):
+                    out[i] = v
+            return out
+        return [[images[i] for i in c] for c in cuts], restore
 
     @torch.no_grad()
     def __call__(self, images, out_hw=None, alt=None, image_ids=None, xform=None):

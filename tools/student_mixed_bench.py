@@ -15,12 +15,26 @@ Both are run once first (workspaces allocated, the multiple-of-32 shapes of A au
 every image there), then timed A B B A ... (--repeats passes each, a pass = every image once, one synchronisation at its
 end): images/s, medians beside every run, the forward time per batch of B and per image of A, and the canvas waste (canvas
 pixels over the sum of the image pixels).  One more pass of B packs its canvases inside the timed region
-(``pack_mixed``).  Forward only: the decode of a mixed batch runs per image (``StudentPipeline.call_mixed``) and is not
-part of this measurement.
+(``pack_mixed``).  Forward only: the decode is measured by ``--what pipeline``, below.
+
+``--what pipeline``: the step behind the forward.  ``StudentPipeline`` on the same images, batches of --batch cut by
+``StudentPipeline.mixed_batches`` (sorted by area), the images ready on the GPU, one process, everything run once first
+(B and C are compared with A there, row by row, bit for bit):
+
+  A  ``call_mixed(decode="per_image")`` - pack, one forward, then every image decoded on its own from a copy of its region:
+     all there was before the one-pass decode;
+  B  ``call_mixed(decode="batch")`` - pack, one forward, ONE decode of the canvas (``HeatmapParser.parse_lowres_mixed``);
+  C  ``stream_mixed`` over the batches of a pass - the software-pipelined loop.
+
+Timed A B C C B A ... (--repeats passes each): images/s with every run, and the CPU time of the process per batch (all
+threads).  ``people`` says how many people a pass finds: the seeded student's maps on noise images give the parser's maximum
+of 30 in every image (7,680 in 256 images), so the grouping and adjust + refine run at full load - real images have a
+handful of people, and less of that work.
 
 Prints one JSON line per model (--out FILE also writes them).  Needs a GPU; there is no fallback.
 
     python tools/student_mixed_bench.py [--images 256] [--batch 32] [--repeats 4] [--out profiles/student_mixed_bench.json]
+    python tools/student_mixed_bench.py --what pipeline [--match-on host] [--out profiles/student_mixed_decode_bench.json]
 """
 import argparse
 import json
@@ -40,6 +54,9 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=4, help="timed passes per mode, interleaved A B B A ...")
     ap.add_argument("--out", help="also write the JSON lines to this file")
+    ap.add_argument("--what", choices=("forward", "pipeline"), default="forward",
+                    help="forward: forward_mixed against the per-image loop; pipeline: call_mixed / stream_mixed, decode included")
+    ap.add_argument("--match-on", choices=("host", "device"), default="host", help="--what pipeline: where people are grouped")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -76,6 +93,11 @@ def main():
         stu = AttentionStudent(None, "cpu", 100, 17, 1, True, None, False, body_half=body_half).eval()
         stu.load_state_dict(synth.make_state_dict(shapes, 3, "W1"), strict=True)
         stu = stu.to(dev)
+        if args.what == "pipeline":
+            lines.append(pipeline_line(args, stu, images, sizes, body_half, dev, timed))
+            del stu
+            torch.cuda.empty_cache()
+            continue
         packed = [pack_mixed([images[i] for i in c]) for c in chunks]
         canvas_px = sum(c.shape[0] * c.shape[2] * c.shape[3] for c, _ in packed)
 
@@ -136,6 +158,56 @@ def main():
         with open(args.out, "w") as f:
             for ln in lines:
                 f.write(json.dumps(ln) + "\n")
+
+
+def pipeline_line(args, stu, images, sizes, body_half, dev, timed):
+    """--what pipeline for one model -> the JSON line"""
+    import numpy as np
+    import torch
+    from rtpe.engine import StudentPipeline
+    pipe = StudentPipeline(stu, device=dev, match_on=args.match_on)
+    batches, restore = StudentPipeline.mixed_batches(images, args.batch)
+
+    def run(mode):
+        if mode == "C":
+            return list(pipe.stream_mixed(iter(batches)))
+        return [pipe.call_mixed(b, decode="per_image" if mode == "A" else "batch") for b in batches]
+
+    def rows(res):
+        return [(np.asarray(p, np.float32), np.array(sc, np.float32)) for p, sc in restore(res)]
+    first, want = {}, None
+    same = True
+    for m in ("A", "B", "C"):
+        res, first[m] = timed(lambda: run(m))
+        got = rows(res)
+        if want is None:
+            want = got
+        same = same and all(a[0].shape == b[0].shape and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+                            for a, b in zip(got, want))
+    people = int(sum(len(p) if p.ndim == 3 else 0 for p, _ in want))
+    runs = {m: [] for m in "ABC"}
+    cpu = {m: [] for m in "ABC"}
+    for r in range(args.repeats):
+        for m in (("A", "B", "C") if r % 2 == 0 else ("C", "B", "A")):
+            c0 = time.process_time()
+            _, dt = timed(lambda: run(m))
+            cpu[m].append(time.process_time() - c0)
+            runs[m].append(dt)
+    med = {m: float(np.median(v)) for m, v in runs.items()}
+
+    def entry(m):
+        return {"img_s": round(len(images) / med[m], 1), "img_s_runs": [round(len(images) / t, 1) for t in runs[m]],
+                "ms_per_batch": round(med[m] * 1e3 / len(batches), 3),
+                "cpu_ms_per_batch": round(float(np.median(cpu[m])) * 1e3 / len(batches), 3),
+                "first_pass_s": round(first[m], 2)}
+    return {"metric": "student_mixed_batch_pipeline", "model": "AttentionStudent(inplanes=100)", "weights": "W1",
+            "body": "half" if body_half else "fp32", "device": torch.cuda.get_device_name(dev), "images": len(images),
+            "distinct_sizes": len(set(sizes)), "batch": args.batch, "batches_per_pass": len(batches),
+            "repeats": args.repeats, "order": "A B C C B A", "match_on": args.match_on, "people": people,
+            "results_bit_identical": bool(same), "host_threads": torch.get_num_threads(),
+            "A_call_mixed_per_image_decode": entry("A"), "B_call_mixed_batch_decode": entry("B"),
+            "C_stream_mixed": entry("C"), "speedup_B_over_A": round(med["A"] / med["B"], 3),
+            "speedup_C_over_A": round(med["A"] / med["C"], 3)}
 
 
 if __name__ == "__main__":
