@@ -1792,6 +1792,20 @@ struct RefineTail {         // the ending every adjust + refine entry of the bat
   void* stream;
 };
 
+// The two endings, as the entries declare them (the prototypes in include/ spell them out) and as they pass them on.
+// (TOPK_PARAMS: where nothing stands between the top-k arguments; the multi-scale entries have maps_bytes there.)
+#define TOPK_PARAMS                                                                                          \
+  int32_t K, int32_t nms_ksize, int32_t nms_pad, float *val_k, int32_t *ind_k, float *tag_k, void *scratch,  \
+      size_t scratch_bytes, void *stream
+#define TOPK_ARGS K, nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream
+#define REFINE_PARAMS                                                                                        \
+  const float *ans_in, float *ans_out, const int32_t *person_img, int32_t P, int32_t do_adjust,              \
+      int32_t do_refine, float *scores, const float *topk_val, const int32_t *topk_ind, int32_t K,           \
+      void *scratch, size_t scratch_bytes, void *stream
+#define REFINE_TAIL                                                                                          \
+  RefineTail{ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K, scratch,   \
+             scratch_bytes, stream}
+
 // what decode_topk refuses before it launches (rtpe_topk_flip asks first: its prepare kernel goes before the top-k)
 template <class Src>
 static int topk_check(const char* who, Src& src, int K, const TopkTables& t, const void* scratch) {
@@ -1814,12 +1828,15 @@ static int decode_topk(const char* who, Src src, int K, int ksize, int pad, cons
   });
 }
 
-// P_dev null: t.P people.  Not null (the _n entries): the number of people is read on the device and t.P is the
-// capacity of ans_in / ans_out / person_img / scores and of the scratch buffer (adjust_refine_run).
-// need_topk: the entry has no form without the top-k table
+// The forms of an adjust + refine entry.  kNeedTopk: the entry has no form without the top-k table.  kCountOnDevice
+// (the _n entries): the number of people is read on the device, from P_dev, and t.P is the capacity of ans_in /
+// ans_out / person_img / scores and of the scratch buffer (adjust_refine_run); without it P_dev stays null: t.P people.
+enum { kAnyForm = 0, kNeedTopk = 1, kCountOnDevice = 2 };
 template <class Src>
-static int decode_adjust_refine(const char* who, Src src, const RefineTail& t, const int32_t* P_dev,
-                                bool need_topk = false) {
+static int decode_adjust_refine(const char* who, Src src, const RefineTail& t, int form,
+                                const int32_t* P_dev = nullptr) {
+  const bool need_topk = form & kNeedTopk;
+  RTPE_REQUIRE(P_dev != nullptr || !(form & kCountOnDevice), "%s: P_dev is null", who);
   const int rc = src.check(who);
   if (rc != RTPE_OK) return rc;
   RTPE_REQUIRE(((t.ans_in && t.ans_out && t.ans_in != t.ans_out) || t.P == 0) && src.J <= kMaxJ,
@@ -1836,7 +1853,20 @@ static int decode_adjust_refine(const char* who, Src src, const RefineTail& t, c
 }
 
 // ---------------------------------------------------------------------------
-// the network outputs as they are: refined heat maps and per-joint tag maps, align_corners=True to (oh, ow), D = 1
+// The network outputs as they are: J refined heat maps per image and their tag maps, sampled align_corners=True, D = 1.
+// ONE kind with two independent switches (include/rtpe_hip.h and rtpe_hip_shared.h / _sizes.h / _mixdec.h hold the
+// prototypes of the four combinations):
+//   shared  the tag is ONE plane per image, (N, 1, th, tw) at tg_img_stride, shared by the J joints (the dual-head
+//           students; SharedBilinearTag / NetMixedTag) - else one tag map per joint.  Both maps may be channel slices
+//           of one (N, J + 1, h, w) tensor: the strides say where an image's planes start.  Bit for bit the per-joint
+//           decode of the tag plane expanded to J channels.
+//   sized   every image is decoded at its own size, read from a table (SizeEntry, fill_size_table) - else at (oh, ow).
+//           Then (oh, ow) are the largest height and the largest width of the batch - the tile grid, the scratch
+//           buffer and the stripes are sized by them - and w_enc is the width of the flat indices.
+// With both (a mixed-size batch decoded from its canvas) (hh, hw) / (th, tw) are the PITCH of the planes - the canvas
+// extents, which only address.  Image n's own extents, which only clamp, are the n_in of its entry's axes
+// (rtpe_decode_mixed_fill); the axes that make_bilinear derives from the pitch are never read (NetSizesMap,
+// NetMixedTag).  Every heat-map kernel of a sized decode is the NetSizesMap instantiation, shared tag or not.
 // ---------------------------------------------------------------------------
 struct NetSrc {
   const float* hm;
@@ -1846,152 +1876,25 @@ struct NetSrc {
   int32_t th, tw;
   int64_t tg_img_stride;
   int32_t N, J, oh, ow;
-  int check(const char* who) const {
-    RTPE_REQUIRE(hm && tg && N > 0 && J > 0, "%s: bad argument", who);
-    return RTPE_OK;
-  }
-  template <class F>
-  int with_maps(F f) const {
-    return f(make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow),
-             BilinearTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)}, 1);
-  }
-};
-
-extern "C" int rtpe_topk_fused(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
-                               int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J, int32_t oh,
-                               int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
-                               int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_fused", NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow}, K,
-                     nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
-}
-
-extern "C" int rtpe_adjust_refine_fused(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                        const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
-                                        int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
-                                        const int32_t* person_img, int32_t P, int32_t do_adjust,
-                                        int32_t do_refine, float* scores, void* scratch, size_t scratch_bytes,
-                                        void* stream) {
-  return decode_adjust_refine("adjust_refine_fused",
-                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, nullptr, nullptr, 0,
-                               scratch, scratch_bytes, stream}, nullptr);
-}
-
-extern "C" int rtpe_adjust_refine_fused_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                             const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
-                                             int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
-                                             const int32_t* person_img, int32_t P, int32_t do_adjust,
-                                             int32_t do_refine, float* scores, const float* topk_val,
-                                             const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                             void* stream) {
-  return decode_adjust_refine("adjust_refine_fused_topk",
-                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr, true);
-}
-
-// rtpe_adjust_refine_fused_topk with the number of people read on the device: P is the capacity of ans_in /
-// ans_out / person_img / scores and of the scratch buffer, *P_dev (device-visible, written by an earlier
-// command of the stream) the number of people.  The same for the other three pipeline kinds below.
-extern "C" int rtpe_adjust_refine_fused_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                             const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N,
-                                             int32_t J, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
-                                             const int32_t* person_img, int32_t P, int32_t do_adjust,
-                                             int32_t do_refine, float* scores, const float* topk_val,
-                                             const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                             void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_fused_topk_n",
-                              NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev, true);
-}
-
-// ---------------------------------------------------------------------------
-// the outputs of a dual-head student as they are: NetSrc with ONE tag plane per image, (N, 1, th, tw) at
-// tg_img_stride, shared by the J joints (SharedBilinearTag).  Both maps may be channel slices of one (N, J + 1, h, w)
-// tensor: the strides say where an image's planes start.  Bit for bit NetSrc on the tag plane expanded to J channels.
-// ---------------------------------------------------------------------------
-struct NetSharedSrc {
-  const float* hm;
-  int32_t hh, hw;
-  int64_t hm_img_stride;
-  const float* tg;
-  int32_t th, tw;
-  int64_t tg_img_stride;
-  int32_t N, J, oh, ow;
-  int check(const char* who) const {
-    RTPE_REQUIRE(hm && tg, "%s: null argument", who);
-    RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "%s: bad argument (N=%d, J=%d; J <= %d)", who, N, J, kMaxJ);
-    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
-    RTPE_REQUIRE(hm_img_stride >= (int64_t)J * hh * hw && tg_img_stride >= (int64_t)th * tw,
-                 "%s: an image stride is below the size of an image's planes", who);
-    return RTPE_OK;
-  }
-  template <class F>
-  int with_maps(F f) const {
-    return f(make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow),
-             SharedBilinearTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow)}, 1);
-  }
-};
-
-extern "C" int rtpe_topk_fused_shared(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
-                                      int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J, int32_t oh,
-                                      int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
-                                      int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes,
-                                      void* stream) {
-  return decode_topk("topk_fused_shared",
-                     NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow}, K, nms_ksize,
-                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
-}
-
-extern "C" int rtpe_adjust_refine_fused_shared_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                    const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                    int32_t N, int32_t J, int32_t oh, int32_t ow, const float* ans_in,
-                                                    float* ans_out, const int32_t* person_img, int32_t P,
-                                                    int32_t do_adjust, int32_t do_refine, float* scores,
-                                                    const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                    void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_fused_shared_topk",
-                              NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr, true);
-}
-
-extern "C" int rtpe_adjust_refine_fused_shared_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                      const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                      int32_t N, int32_t J, int32_t oh, int32_t ow,
-                                                      const float* ans_in, float* ans_out, const int32_t* person_img,
-                                                      int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                                      const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                      void* scratch, size_t scratch_bytes, void* stream,
-                                                      const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_shared_topk_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_fused_shared_topk_n",
-                              NetSharedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev, true);
-}
-
-// ---------------------------------------------------------------------------
-// the network outputs as they are, every image decoded at its own size: NetSrc with the sizes in a table
-// (SizeEntry, rtpe_decode_sizes_fill).  (oh, ow) are the largest height and the largest width of the batch - the tile
-// grid, the scratch buffer and the stripes are sized by them - and w_enc is the width of the flat indices
-// ---------------------------------------------------------------------------
-struct NetSizesSrc {
-  const float* hm;
-  int32_t hh, hw;
-  int64_t hm_img_stride;
-  const float* tg;
-  int32_t th, tw;
-  int64_t tg_img_stride;
-  int32_t N, J;
-  const void* table;
+  bool shared, sized;
+  const void* table;        // sized only
   size_t table_bytes;
-  int32_t oh, ow, w_enc;
+  int32_t w_enc;
+  // Each switch brings the checks its entries came with, no more: the shared kinds look at J <= kMaxJ (the top-k
+  // too) and at the image strides, the kinds without the switches at neither, nor at the sizes of the maps.
   int check(const char* who) const {
-    RTPE_REQUIRE(hm && tg && table && N > 0 && J > 0, "%s: bad argument", who);
-    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
+    if (shared) {
+      RTPE_REQUIRE(hm && tg && (table || !sized), "%s: null argument", who);
+      RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "%s: bad argument (N=%d, J=%d; J <= %d)", who, N, J, kMaxJ);
+    } else {
+      RTPE_REQUIRE(hm && tg && (table || !sized) && N > 0 && J > 0, "%s: bad argument", who);
+    }
+    if (shared || sized)
+      RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
+    if (shared)
+      RTPE_REQUIRE(hm_img_stride >= (int64_t)J * hh * hw && tg_img_stride >= (int64_t)th * tw,
+                   "%s: an image stride is below the size of an image's planes", who);
+    if (!sized) return RTPE_OK;
     RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "%s: sizes table too small (%zu < %zu bytes)", who,
                  table_bytes, (size_t)N * sizeof(SizeEntry));
     RTPE_REQUIRE(w_enc >= ow, "%s: w_enc=%d is below the largest width %d", who, w_enc, ow);
@@ -2001,18 +1904,116 @@ struct NetSizesSrc {
   }
   template <class F>
   int with_maps(F f) const {
+    const BilinearMap heat = make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow);
+    const BilinearMap tag = make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow);
+    if (!sized) return shared ? f(heat, SharedBilinearTag{tag}, 1) : f(heat, BilinearTag{tag}, 1);
     const SizeEntry* tab = reinterpret_cast<const SizeEntry*>(table);
-    return f(NetSizesMap{make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow), tab, w_enc},
-             NetSizesTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow), tab}, 1);
+    const NetSizesMap m{heat, tab, w_enc};
+    return shared ? f(m, NetMixedTag{tag, tab}, 1) : f(m, NetSizesTag{tag, tab}, 1);
   }
 };
 
+// The leading arguments of the thirteen entries - the maps, then one decode size or the table - and the NetSrc they
+// make.  (The prototypes in the headers spell every list out; these follow them name for name.)
+#define NET_MAPS_PARAMS                                                                                        \
+  const float *hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float *tg, int32_t th, int32_t tw,     \
+      int64_t tg_img_stride, int32_t N, int32_t J
+#define NET_TABLE_PARAMS \
+  const void *sizes_table, size_t table_bytes, int32_t max_oh, int32_t max_ow, int32_t w_enc
+#define NET_ONE_SIZE(shared) \
+  NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, oh, ow, shared, false, nullptr, 0, ow}
+#define NET_SIZED(shared)                                                                                    \
+  NetSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, max_oh, max_ow, shared, true, sizes_table, \
+         table_bytes, w_enc}
+
+extern "C" int rtpe_topk_fused(NET_MAPS_PARAMS, int32_t oh, int32_t ow, TOPK_PARAMS) {
+  return decode_topk("topk_fused", NET_ONE_SIZE(false), TOPK_ARGS);
+}
+
+extern "C" int rtpe_adjust_refine_fused(NET_MAPS_PARAMS, int32_t oh, int32_t ow, const float* ans_in, float* ans_out,
+                                        const int32_t* person_img, int32_t P, int32_t do_adjust,
+                                        int32_t do_refine, float* scores, void* scratch, size_t scratch_bytes,
+                                        void* stream) {
+  // the one entry without the top-k table: null, null, 0 in its place
+  return decode_adjust_refine("adjust_refine_fused", NET_ONE_SIZE(false),
+                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, nullptr, nullptr, 0,
+                               scratch, scratch_bytes, stream}, kAnyForm);
+}
+
+extern "C" int rtpe_adjust_refine_fused_topk(NET_MAPS_PARAMS, int32_t oh, int32_t ow, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_fused_topk", NET_ONE_SIZE(false), REFINE_TAIL, kNeedTopk);
+}
+
+// rtpe_adjust_refine_fused_topk with the number of people read on the device: P is the capacity of ans_in /
+// ans_out / person_img / scores and of the scratch buffer, *P_dev (device-visible, written by an earlier
+// command of the stream) the number of people.  The same for every `_n` entry below.
+extern "C" int rtpe_adjust_refine_fused_topk_n(NET_MAPS_PARAMS, int32_t oh, int32_t ow, REFINE_PARAMS,
+                                               const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_fused_topk_n", NET_ONE_SIZE(false), REFINE_TAIL,
+                              kNeedTopk | kCountOnDevice, P_dev);
+}
+
+// shared: the outputs of a dual-head student as they are (include/rtpe_hip_shared.h)
+extern "C" int rtpe_topk_fused_shared(NET_MAPS_PARAMS, int32_t oh, int32_t ow, TOPK_PARAMS) {
+  return decode_topk("topk_fused_shared", NET_ONE_SIZE(true), TOPK_ARGS);
+}
+
+extern "C" int rtpe_adjust_refine_fused_shared_topk(NET_MAPS_PARAMS, int32_t oh, int32_t ow, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_fused_shared_topk", NET_ONE_SIZE(true), REFINE_TAIL, kNeedTopk);
+}
+
+extern "C" int rtpe_adjust_refine_fused_shared_topk_n(NET_MAPS_PARAMS, int32_t oh, int32_t ow, REFINE_PARAMS,
+                                                      const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_fused_shared_topk_n", NET_ONE_SIZE(true), REFINE_TAIL,
+                              kNeedTopk | kCountOnDevice, P_dev);
+}
+
+// sized: the size tables (HOST functions) and the entries that read them (include/rtpe_hip_sizes.h, rtpe_hip_mixdec.h)
 extern "C" int rtpe_decode_sizes_bytes(int32_t N, size_t* bytes) {
   RTPE_REQUIRE(bytes && N > 0, "decode_sizes_bytes: bad argument");
   *bytes = (size_t)N * sizeof(SizeEntry);
   return RTPE_OK;
 }
 
+// Entry n: the axes of an image decoded at out_hw[n] whose maps span heat_hw[step * n] / tag_hw[step * n] of planes of
+// pitch (hh, hw) / (th, tw); step = 0: the same extents for every image.  Everything is checked before the first entry
+// is written: a wrong entry would make the device read outside the planes.
+static int fill_size_table(const char* who, const int32_t* out_hw, const int32_t* heat_hw, const int32_t* tag_hw,
+                           int step, int N, int hh, int hw, int th, int tw, void* table, int32_t* max_oh,
+                           int32_t* max_ow) {
+  int mh = 0, mw = 0;
+  for (int n = 0; n < N; ++n) {
+    const int32_t *o = out_hw + 2 * n, *he = heat_hw + step * n, *te = tag_hw + step * n;
+    RTPE_REQUIRE(o[0] > 0 && o[1] > 0, "%s: image %d has size %d x %d", who, n, o[0], o[1]);
+    RTPE_REQUIRE(he[0] > 0 && he[1] > 0 && te[0] > 0 && te[1] > 0,
+                 "%s: image %d has map extents %d x %d (heat), %d x %d (tag)", who, n, he[0], he[1], te[0], te[1]);
+    RTPE_REQUIRE(he[0] <= hh && he[1] <= hw, "%s: image %d: heat extent %d x %d is above the pitch %d x %d", who, n,
+                 he[0], he[1], hh, hw);
+    RTPE_REQUIRE(te[0] <= th && te[1] <= tw, "%s: image %d: tag extent %d x %d is above the pitch %d x %d", who, n,
+                 te[0], te[1], th, tw);
+    mh = o[0] > mh ? o[0] : mh;
+    mw = o[1] > mw ? o[1] : mw;
+  }
+  SizeEntry* tab = reinterpret_cast<SizeEntry*>(table);
+  for (int n = 0; n < N; ++n) {
+    const int32_t *he = heat_hw + step * n, *te = tag_hw + step * n;
+    SizeEntry e;
+    memset(&e, 0, sizeof(e));
+    e.oh = out_hw[2 * n];
+    e.ow = out_hw[2 * n + 1];
+    e.hy = make_axis(he[0], e.oh);
+    e.hx = make_axis(he[1], e.ow);
+    e.ty = make_axis(te[0], e.oh);
+    e.tx = make_axis(te[1], e.ow);
+    e.small = small_output(e.oh, e.ow);
+    tab[n] = e;
+  }
+  if (max_oh) *max_oh = mh;
+  if (max_ow) *max_ow = mw;
+  return RTPE_OK;
+}
+
+// every image's maps span the whole planes: extent = pitch
 extern "C" int rtpe_decode_sizes_fill(const int32_t* sizes_hw, int32_t N, int32_t hh, int32_t hw, int32_t th,
                                       int32_t tw, void* table, size_t table_bytes, int32_t* max_oh,
                                       int32_t* max_ow) {
@@ -2020,116 +2021,12 @@ extern "C" int rtpe_decode_sizes_fill(const int32_t* sizes_hw, int32_t N, int32_
   RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0, "decode_sizes_fill: bad shape");
   RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "decode_sizes_fill: sizes table too small (%zu < %zu bytes)",
                table_bytes, (size_t)N * sizeof(SizeEntry));
-  int mh = 0, mw = 0;
-  for (int n = 0; n < N; ++n) {
-    RTPE_REQUIRE(sizes_hw[2 * n] > 0 && sizes_hw[2 * n + 1] > 0, "decode_sizes_fill: image %d has size %d x %d", n,
-                 sizes_hw[2 * n], sizes_hw[2 * n + 1]);
-    mh = sizes_hw[2 * n] > mh ? sizes_hw[2 * n] : mh;
-    mw = sizes_hw[2 * n + 1] > mw ? sizes_hw[2 * n + 1] : mw;
-  }
-  SizeEntry* tab = reinterpret_cast<SizeEntry*>(table);
-  for (int n = 0; n < N; ++n) {
-    SizeEntry e;
-    memset(&e, 0, sizeof(e));
-    e.oh = sizes_hw[2 * n];
-    e.ow = sizes_hw[2 * n + 1];
-    e.hy = make_axis(hh, e.oh);
-    e.hx = make_axis(hw, e.ow);
-    e.ty = make_axis(th, e.oh);
-    e.tx = make_axis(tw, e.ow);
-    e.small = small_output(e.oh, e.ow);
-    tab[n] = e;
-  }
-  if (max_oh) *max_oh = mh;
-  if (max_ow) *max_ow = mw;
-  return RTPE_OK;
+  // step = 0: these two pairs serve as every image's extents (their per-image checks in fill_size_table then repeat
+  // the shape check above and cannot fail)
+  const int32_t heat[2] = {hh, hw}, tag[2] = {th, tw};
+  return fill_size_table("decode_sizes_fill", sizes_hw, heat, tag, 0, N, hh, hw, th, tw, table, max_oh, max_ow);
 }
 
-extern "C" int rtpe_topk_fused_sizes(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
-                                     int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J,
-                                     const void* sizes_table, size_t table_bytes, int32_t max_oh, int32_t max_ow,
-                                     int32_t w_enc, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
-                                     int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_fused_sizes",
-                     NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table, table_bytes,
-                                 max_oh, max_ow, w_enc},
-                     K, nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
-}
-
-extern "C" int rtpe_adjust_refine_fused_topk_sizes(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                   const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                   int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
-                                                   int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
-                                                   float* ans_out, const int32_t* person_img, int32_t P,
-                                                   int32_t do_adjust, int32_t do_refine, float* scores,
-                                                   const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                   void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_fused_topk_sizes",
-                              NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
-                                          table_bytes, max_oh, max_ow, w_enc},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr, true);
-}
-
-extern "C" int rtpe_adjust_refine_fused_topk_sizes_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                     const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                     int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
-                                                     int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
-                                                     float* ans_out, const int32_t* person_img, int32_t P,
-                                                     int32_t do_adjust, int32_t do_refine, float* scores,
-                                                     const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                     void* scratch, size_t scratch_bytes, void* stream,
-                                                     const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_topk_sizes_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_fused_topk_sizes_n",
-                              NetSizesSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
-                                          table_bytes, max_oh, max_ow, w_enc},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev, true);
-}
-
-// ---------------------------------------------------------------------------
-// a mixed-size batch of a dual-head student decoded from its canvas (include/rtpe_hip_mixdec.h): NetSizesSrc with ONE
-// tag plane per image (NetSharedSrc's `tg`) and with (hh, hw) / (th, tw) read as the PITCH of the planes - the canvas
-// extents, which only address.  Image n's own extents, which only clamp, are the n_in of its entry's axes
-// (rtpe_decode_mixed_fill); the axes that make_bilinear derives from the pitch are never read (NetSizesMap,
-// NetMixedTag).  Every heat-map kernel is the NetSizesMap instantiation that the `_sizes` entries launch.
-// ---------------------------------------------------------------------------
-struct NetMixedSrc {
-  const float* hm;
-  int32_t hh, hw;
-  int64_t hm_img_stride;
-  const float* tg;
-  int32_t th, tw;
-  int64_t tg_img_stride;
-  int32_t N, J;
-  const void* table;
-  size_t table_bytes;
-  int32_t oh, ow, w_enc;
-  int check(const char* who) const {
-    RTPE_REQUIRE(hm && tg && table, "%s: null argument", who);
-    RTPE_REQUIRE(N > 0 && J > 0 && J <= kMaxJ, "%s: bad argument (N=%d, J=%d; J <= %d)", who, N, J, kMaxJ);
-    RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0 && oh > 0 && ow > 0, "%s: bad shape", who);
-    RTPE_REQUIRE(hm_img_stride >= (int64_t)J * hh * hw && tg_img_stride >= (int64_t)th * tw,
-                 "%s: an image stride is below the size of an image's planes", who);
-    RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "%s: sizes table too small (%zu < %zu bytes)", who,
-                 table_bytes, (size_t)N * sizeof(SizeEntry));
-    RTPE_REQUIRE(w_enc >= ow, "%s: w_enc=%d is below the largest width %d", who, w_enc, ow);
-    RTPE_REQUIRE((int64_t)oh * w_enc <= 0x7fffffff, "%s: y * w_enc + x exceeds 32 bits (max_oh=%d, w_enc=%d)", who, oh,
-                 w_enc);
-    return RTPE_OK;
-  }
-  template <class F>
-  int with_maps(F f) const {
-    const SizeEntry* tab = reinterpret_cast<const SizeEntry*>(table);
-    return f(NetSizesMap{make_bilinear(hm, hh, hw, hm_img_stride, J, oh, ow), tab, w_enc},
-             NetMixedTag{make_bilinear(tg, th, tw, tg_img_stride, J, oh, ow), tab}, 1);
-  }
-};
-
-// HOST function.  Entry n: the axes of an image whose maps span heat_hw[n] / tag_hw[n] of planes of pitch (hh, hw) /
-// (th, tw), decoded at out_hw[n].  Everything is checked before the first entry is written: a wrong entry would make
-// the device read outside the planes.
 extern "C" int rtpe_decode_mixed_fill(const int32_t* out_hw, const int32_t* heat_hw, const int32_t* tag_hw, int32_t N,
                                       int32_t hh, int32_t hw, int32_t th, int32_t tw, void* table, size_t table_bytes,
                                       int32_t* max_oh, int32_t* max_ow) {
@@ -2137,82 +2034,38 @@ extern "C" int rtpe_decode_mixed_fill(const int32_t* out_hw, const int32_t* heat
   RTPE_REQUIRE(hh > 0 && hw > 0 && th > 0 && tw > 0, "decode_mixed_fill: bad shape");
   RTPE_REQUIRE(table_bytes >= (size_t)N * sizeof(SizeEntry), "decode_mixed_fill: sizes table too small (%zu < %zu bytes)",
                table_bytes, (size_t)N * sizeof(SizeEntry));
-  if (tag_hw == nullptr) tag_hw = heat_hw;                  // the tag extents are the heat extents
-  int mh = 0, mw = 0;
-  for (int n = 0; n < N; ++n) {
-    RTPE_REQUIRE(out_hw[2 * n] > 0 && out_hw[2 * n + 1] > 0, "decode_mixed_fill: image %d has size %d x %d", n,
-                 out_hw[2 * n], out_hw[2 * n + 1]);
-    RTPE_REQUIRE(heat_hw[2 * n] > 0 && heat_hw[2 * n + 1] > 0 && tag_hw[2 * n] > 0 && tag_hw[2 * n + 1] > 0,
-                 "decode_mixed_fill: image %d has map extents %d x %d (heat), %d x %d (tag)", n, heat_hw[2 * n],
-                 heat_hw[2 * n + 1], tag_hw[2 * n], tag_hw[2 * n + 1]);
-    RTPE_REQUIRE(heat_hw[2 * n] <= hh && heat_hw[2 * n + 1] <= hw,
-                 "decode_mixed_fill: image %d: heat extent %d x %d is above the pitch %d x %d", n, heat_hw[2 * n],
-                 heat_hw[2 * n + 1], hh, hw);
-    RTPE_REQUIRE(tag_hw[2 * n] <= th && tag_hw[2 * n + 1] <= tw,
-                 "decode_mixed_fill: image %d: tag extent %d x %d is above the pitch %d x %d", n, tag_hw[2 * n],
-                 tag_hw[2 * n + 1], th, tw);
-    mh = out_hw[2 * n] > mh ? out_hw[2 * n] : mh;
-    mw = out_hw[2 * n + 1] > mw ? out_hw[2 * n + 1] : mw;
-  }
-  SizeEntry* tab = reinterpret_cast<SizeEntry*>(table);
-  for (int n = 0; n < N; ++n) {
-    SizeEntry e;
-    memset(&e, 0, sizeof(e));
-    e.oh = out_hw[2 * n];
-    e.ow = out_hw[2 * n + 1];
-    e.hy = make_axis(heat_hw[2 * n], e.oh);
-    e.hx = make_axis(heat_hw[2 * n + 1], e.ow);
-    e.ty = make_axis(tag_hw[2 * n], e.oh);
-    e.tx = make_axis(tag_hw[2 * n + 1], e.ow);
-    e.small = small_output(e.oh, e.ow);
-    tab[n] = e;
-  }
-  if (max_oh) *max_oh = mh;
-  if (max_ow) *max_ow = mw;
-  return RTPE_OK;
+  // (tag_hw null: the tag extents are the heat extents)
+  return fill_size_table("decode_mixed_fill", out_hw, heat_hw, tag_hw ? tag_hw : heat_hw, 2, N, hh, hw, th, tw, table,
+                         max_oh, max_ow);
 }
 
-extern "C" int rtpe_topk_fused_mixed(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride, const float* tg,
-                                     int32_t th, int32_t tw, int64_t tg_img_stride, int32_t N, int32_t J,
-                                     const void* sizes_table, size_t table_bytes, int32_t max_oh, int32_t max_ow,
-                                     int32_t w_enc, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
-                                     int32_t* ind_k, float* tag_k, void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_fused_mixed",
-                     NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table, table_bytes,
-                                 max_oh, max_ow, w_enc},
-                     K, nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+extern "C" int rtpe_topk_fused_sizes(NET_MAPS_PARAMS, NET_TABLE_PARAMS, TOPK_PARAMS) {
+  return decode_topk("topk_fused_sizes", NET_SIZED(false), TOPK_ARGS);
 }
 
-extern "C" int rtpe_adjust_refine_fused_mixed_topk(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                   const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                   int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
-                                                   int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
-                                                   float* ans_out, const int32_t* person_img, int32_t P,
-                                                   int32_t do_adjust, int32_t do_refine, float* scores,
-                                                   const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                   void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_fused_mixed_topk",
-                              NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
-                                          table_bytes, max_oh, max_ow, w_enc},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr, true);
+extern "C" int rtpe_adjust_refine_fused_topk_sizes(NET_MAPS_PARAMS, NET_TABLE_PARAMS, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_fused_topk_sizes", NET_SIZED(false), REFINE_TAIL, kNeedTopk);
 }
 
-extern "C" int rtpe_adjust_refine_fused_mixed_topk_n(const float* hm, int32_t hh, int32_t hw, int64_t hm_img_stride,
-                                                     const float* tg, int32_t th, int32_t tw, int64_t tg_img_stride,
-                                                     int32_t N, int32_t J, const void* sizes_table, size_t table_bytes,
-                                                     int32_t max_oh, int32_t max_ow, int32_t w_enc, const float* ans_in,
-                                                     float* ans_out, const int32_t* person_img, int32_t P,
-                                                     int32_t do_adjust, int32_t do_refine, float* scores,
-                                                     const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                                     void* scratch, size_t scratch_bytes, void* stream,
+extern "C" int rtpe_adjust_refine_fused_topk_sizes_n(NET_MAPS_PARAMS, NET_TABLE_PARAMS, REFINE_PARAMS,
                                                      const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_fused_mixed_topk_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_fused_mixed_topk_n",
-                              NetMixedSrc{hm, hh, hw, hm_img_stride, tg, th, tw, tg_img_stride, N, J, sizes_table,
-                                          table_bytes, max_oh, max_ow, w_enc},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev, true);
+  return decode_adjust_refine("adjust_refine_fused_topk_sizes_n", NET_SIZED(false), REFINE_TAIL,
+                              kNeedTopk | kCountOnDevice, P_dev);
+}
+
+// shared and sized: a mixed-size batch of a dual-head student decoded from its canvas (include/rtpe_hip_mixdec.h)
+extern "C" int rtpe_topk_fused_mixed(NET_MAPS_PARAMS, NET_TABLE_PARAMS, TOPK_PARAMS) {
+  return decode_topk("topk_fused_mixed", NET_SIZED(true), TOPK_ARGS);
+}
+
+extern "C" int rtpe_adjust_refine_fused_mixed_topk(NET_MAPS_PARAMS, NET_TABLE_PARAMS, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_fused_mixed_topk", NET_SIZED(true), REFINE_TAIL, kNeedTopk);
+}
+
+extern "C" int rtpe_adjust_refine_fused_mixed_topk_n(NET_MAPS_PARAMS, NET_TABLE_PARAMS, REFINE_PARAMS,
+                                                     const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_fused_mixed_topk_n", NET_SIZED(true), REFINE_TAIL,
+                              kNeedTopk | kCountOnDevice, P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -2279,6 +2132,7 @@ struct FlipSrc {
     return f(FlipHeatMap{maps, maps + n, a}, FlipTag{maps + 2 * n, maps + 3 * n, a}, 2);
   }
 };
+#define FLIP_SRC FlipSrc{maps, h2, w2, N, J, oh, ow}
 
 extern "C" int rtpe_flip_maps_bytes(int32_t N, int32_t J, int32_t h2, int32_t w2, size_t* bytes) {
   RTPE_REQUIRE(bytes && N > 0 && J > 0 && h2 > 0 && w2 > 0, "flip_maps_bytes: bad argument");
@@ -2293,7 +2147,7 @@ extern "C" int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_
                               int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize, int32_t nms_pad, float* val_k,
                               int32_t* ind_k, float* tag_k, float* maps, size_t maps_bytes, void* scratch,
                               size_t scratch_bytes, void* stream) {
-  FlipSrc src{maps, h2, w2, N, J, oh, ow};
+  FlipSrc src = FLIP_SRC;
   const TopkTables tables{val_k, ind_k, tag_k};
   int rc = topk_check("topk_flip", src, K, tables, scratch);
   if (rc != RTPE_OK) return rc;
@@ -2314,24 +2168,13 @@ extern "C" int rtpe_topk_flip(const float* preds, int32_t h4, int32_t w4, int64_
 }
 
 extern "C" int rtpe_adjust_refine_flip(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
-                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                       size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_flip", FlipSrc{maps, h2, w2, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr);
+                                       int32_t ow, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_flip", FLIP_SRC, REFINE_TAIL, kAnyForm);
 }
 
 extern "C" int rtpe_adjust_refine_flip_n(const float* maps, int32_t h2, int32_t w2, int32_t N, int32_t J, int32_t oh,
-                                       int32_t ow, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                       int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                       const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                       size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_flip_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_flip_n", FlipSrc{maps, h2, w2, N, J, oh, ow},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev);
+                                         int32_t ow, REFINE_PARAMS, const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_flip_n", FLIP_SRC, REFINE_TAIL, kCountOnDevice, P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -2420,6 +2263,7 @@ struct MsSrc {
     return f(m, FlipTag{maps + L.to, flip ? maps + L.tf : nullptr, nc_axes(h2[base], w2[base], oh, ow)}, 1 + flip);
   }
 };
+#define MS_SRC(ags) MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, ags}
 
 static int ms_maps_bytes(const char* who, int N, int J, int S, const int32_t* h2, const int32_t* w2, int base,
                          int flip, int ags, size_t* bytes, int oh = 0, int ow = 0) {
@@ -2515,64 +2359,38 @@ extern "C" int rtpe_topk_ms(const float* maps, int32_t N, int32_t J, int32_t S, 
                             int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K, int32_t nms_ksize,
                             int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
                             void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_ms", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false}, K, nms_ksize,
-                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+  return decode_topk("topk_ms", MS_SRC(kTagPerJoint), TOPK_ARGS);
 }
 
 extern "C" int rtpe_topk_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                 const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K,
                                 int32_t nms_ksize, int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k,
                                 size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_ms_ags", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true}, K, nms_ksize,
-                     nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+  return decode_topk("topk_ms_ags", MS_SRC(kTagFirst), TOPK_ARGS);
 }
 
 extern "C" int rtpe_adjust_refine_ms(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                      const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_ms", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr);
+                                     size_t maps_bytes, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_ms", MS_SRC(kTagPerJoint), REFINE_TAIL, kAnyForm);
 }
 
 extern "C" int rtpe_adjust_refine_ms_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                     const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                     size_t maps_bytes, const float* ans_in, float* ans_out, const int32_t* person_img,
-                                     int32_t P, int32_t do_adjust, int32_t do_refine, float* scores,
-                                     const float* topk_val, const int32_t* topk_ind, int32_t K, void* scratch,
-                                     size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_ms_n", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, false},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev);
+                                       const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                       size_t maps_bytes, REFINE_PARAMS, const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_ms_n", MS_SRC(kTagPerJoint), REFINE_TAIL, kCountOnDevice, P_dev);
 }
 
 extern "C" int rtpe_adjust_refine_ms_ags(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                          const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                         size_t maps_bytes, const float* ans_in, float* ans_out,
-                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
-                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                         void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_ms_ags",
-                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr);
+                                         size_t maps_bytes, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_ms_ags", MS_SRC(kTagFirst), REFINE_TAIL, kAnyForm);
 }
 
 extern "C" int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                         const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                         size_t maps_bytes, const float* ans_in, float* ans_out,
-                                         const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
-                                         float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                         void* scratch, size_t scratch_bytes, void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_ags_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_ms_ags_n",
-                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, true},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev);
+                                           const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
+                                           size_t maps_bytes, REFINE_PARAMS, const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_ms_ags_n", MS_SRC(kTagFirst), REFINE_TAIL, kCountOnDevice, P_dev);
 }
 
 // averaged tag (include/rtpe_hip_tagmean.h): the `_ags` entries with the layout that holds T and M
@@ -2591,34 +2409,19 @@ extern "C" int rtpe_topk_ms_mean(const float* maps, int32_t N, int32_t J, int32_
                                  const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow, int32_t K,
                                  int32_t nms_ksize, int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k,
                                  size_t maps_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_ms_mean", MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean}, K,
-                     nms_ksize, nms_pad, {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+  return decode_topk("topk_ms_mean", MS_SRC(kTagMean), TOPK_ARGS);
 }
 
 extern "C" int rtpe_adjust_refine_ms_mean(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                           const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                          size_t maps_bytes, const float* ans_in, float* ans_out,
-                                          const int32_t* person_img, int32_t P, int32_t do_adjust, int32_t do_refine,
-                                          float* scores, const float* topk_val, const int32_t* topk_ind, int32_t K,
-                                          void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_adjust_refine("adjust_refine_ms_mean",
-                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr);
+                                          size_t maps_bytes, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_ms_mean", MS_SRC(kTagMean), REFINE_TAIL, kAnyForm);
 }
 
 extern "C" int rtpe_adjust_refine_ms_mean_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
                                             const int32_t* w2, int32_t base, int32_t flip, int32_t oh, int32_t ow,
-                                            size_t maps_bytes, const float* ans_in, float* ans_out,
-                                            const int32_t* person_img, int32_t P, int32_t do_adjust,
-                                            int32_t do_refine, float* scores, const float* topk_val,
-                                            const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                            void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_mean_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_ms_mean_n",
-                              MsSrc{maps, N, J, S, h2, w2, base, flip, oh, ow, maps_bytes, kTagMean},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev);
+                                            size_t maps_bytes, REFINE_PARAMS, const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_ms_mean_n", MS_SRC(kTagMean), REFINE_TAIL, kCountOnDevice, P_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -2680,6 +2483,7 @@ struct NpSrc {
              FlipTag{maps + L.to, flip ? maps + L.tf : nullptr, nc_axes(h2[base], w2[base], oh, ow)}, 1 + flip);
   }
 };
+#define NP_SRC NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes}
 
 extern "C" int rtpe_ms_np_maps_bytes(int32_t N, int32_t J, int32_t S, const int32_t* h2, const int32_t* w2,
                                      int32_t base, int32_t flip, size_t* bytes) {
@@ -2744,29 +2548,17 @@ extern "C" int rtpe_topk_ms_np(const float* maps, int32_t N, int32_t J, int32_t 
                                const int32_t* w2, int32_t base, int32_t flip, int32_t K, int32_t nms_ksize,
                                int32_t nms_pad, float* val_k, int32_t* ind_k, float* tag_k, size_t maps_bytes,
                                void* scratch, size_t scratch_bytes, void* stream) {
-  return decode_topk("topk_ms_np", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes}, K, nms_ksize, nms_pad,
-                     {val_k, ind_k, tag_k}, scratch, scratch_bytes, stream);
+  return decode_topk("topk_ms_np", NP_SRC, TOPK_ARGS);
 }
 
 extern "C" int rtpe_adjust_refine_ms_np(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                        const int32_t* w2, int32_t base, int32_t flip, size_t maps_bytes,
-                                        const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
-                                        int32_t do_adjust, int32_t do_refine, float* scores, const float* topk_val,
-                                        const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                        void* stream) {
-  return decode_adjust_refine("adjust_refine_ms_np", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, nullptr);
+                                        const int32_t* w2, int32_t base, int32_t flip,
+                                        size_t maps_bytes, REFINE_PARAMS) {
+  return decode_adjust_refine("adjust_refine_ms_np", NP_SRC, REFINE_TAIL, kAnyForm);
 }
 
 extern "C" int rtpe_adjust_refine_ms_np_n(const float* maps, int32_t N, int32_t J, int32_t S, const int32_t* h2,
-                                          const int32_t* w2, int32_t base, int32_t flip, size_t maps_bytes,
-                                          const float* ans_in, float* ans_out, const int32_t* person_img, int32_t P,
-                                          int32_t do_adjust, int32_t do_refine, float* scores, const float* topk_val,
-                                          const int32_t* topk_ind, int32_t K, void* scratch, size_t scratch_bytes,
-                                          void* stream, const int32_t* P_dev) {
-  RTPE_REQUIRE(P_dev != nullptr, "adjust_refine_ms_np_n: P_dev is null");
-  return decode_adjust_refine("adjust_refine_ms_np_n", NpSrc{maps, N, J, S, h2, w2, base, flip, maps_bytes},
-                              {ans_in, ans_out, person_img, P, do_adjust, do_refine, scores, topk_val, topk_ind, K,
-                               scratch, scratch_bytes, stream}, P_dev);
+                                          const int32_t* w2, int32_t base, int32_t flip,
+                                          size_t maps_bytes, REFINE_PARAMS, const int32_t* P_dev) {
+  return decode_adjust_refine("adjust_refine_ms_np_n", NP_SRC, REFINE_TAIL, kCountOnDevice, P_dev);
 }

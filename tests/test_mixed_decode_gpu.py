@@ -310,6 +310,34 @@ def test_parse_lowres_mixed_of_equal_sizes_equals_parse_lowres_shared_on_the_bat
         assert sum(_n_people(g[0]) for g in got) >= 9
 
 
+# (maps, decode size): the small-output sampler (oh + ow <= 128) with one boundary of the 32 x 64 top-k tile in each direction;
+# the other sampler with more than one tile both ways
+FOUR_PATHS = [((10, 18), (40, 72)), ((18, 34), (72, 136))]
+
+
+@pytest.mark.parametrize("match_on", ["host", "device"])
+@pytest.mark.parametrize("src,hw", FOUR_PATHS, ids=["40x72_small_output", "72x136"])
+def test_the_four_public_paths_agree_on_equal_sizes_with_one_tag_plane(nat, src, hw, match_on):
+    """the two switches of the network-output kind (one tag plane per image; sizes from the table), all four
+    combinations on the same maps: every image has the same size and every extent is the pitch, so each path must return
+    the rows and scores of the plain decode of the tag plane expanded to J channels"""
+    sets = [synth.make_decode_maps(3, src[0], src[1], seed=s, sigma=1.0) for s in (61, 62, 63)]
+    heat = torch.from_numpy(np.concatenate([s[0] for s in sets]))
+    tag = torch.from_numpy(np.concatenate([s[1][..., 0] for s in sets])).amax(1, keepdim=True)
+    det = torch.cat([heat, tag], 1).contiguous().to(DEV)
+    heat, tag = det[:, :J].contiguous(), det[:, J:]
+    expanded = tag.expand(-1, J, -1, -1).contiguous()
+    want = _parser(match_on).parse_lowres(heat, expanded, hw)
+    assert len(want) == 3 and all(_n_people(w[0]) >= 1 for w in want)
+    paths = {"sizes": _parser(match_on).parse_lowres(heat, expanded, [hw] * 3),
+             "shared": _parser(match_on).parse_lowres_shared(det[:, :J], tag, hw),
+             "mixed": _parser(match_on).parse_lowres_mixed(det, [hw] * 3)}
+    for name, got in paths.items():
+        assert len(got) == 3, name
+        for g, w in zip(got, want):
+            _same(g, w)
+
+
 def test_parse_lowres_mixed_records_equal_the_records_of_every_image(nat):
     from rtpe.engine import RECORD_FLOATS, unpack_records
     ids = [7, 1 << 24, 0, 12, 99, 5]
