@@ -50,9 +50,9 @@ struct OpState {
 using namespace rtpe;
 
 // ---- routing: which launch computes each op of one forward ------------------------------------------------------------
-// route_ops() decides it in one pass over the ops, from the options as they are at that moment; run() launches what the routes
-// say, rtpe_hrnet_op_tile reports them, the per-op times and the autotuner read them.  A new fused launch is one more kind
-// here: its conditions in route_ops(), its launch in run()'s switch, its mark in route_label().
+// route_ops() decides it in one pass over the ops, from the options as they are at that moment; launch_op() launches what the
+// routes say, rtpe_hrnet_op_tile reports them, the per-op times and the autotuner read them.  A new fused launch is one more
+// kind here: its conditions in route_ops(), its case in launch_op(), its mark in route_label().
 enum {
   kRouteNone = 0,                                        // no conv (an elementwise / student op)
   kRouteTile, kRouteStream, kRouteDirect, kRouteConv64,  // conv_launch on tile[k], one launch per parity class: ConvTile::kind 0 / 2 / 4 / 5
@@ -154,23 +154,12 @@ extern "C" int rtpe_device_count(void) {
   return n;
 }
 
-extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
-                                 const rtpe_tensor_desc* tensors, int32_t n_tensors,
-                                 const void* weights, size_t weights_bytes, int32_t device,
-                                 rtpe_hrnet** out) {
-  RTPE_REQUIRE(ops && tensors && weights && out && n_ops > 0 && n_tensors > 0, "hrnet_create: null argument");
-  DeviceGuard guard(device);               // the caller's current device is restored on return
-  RTPE_HIP_CHECK(guard.err);
-  rtpe_hrnet* h = new rtpe_hrnet();
-  h->device = device;
-  h->tensors.assign(tensors, tensors + n_tensors);
-  h->n_slots = 0;
-  for (auto& t : h->tensors) h->n_slots = t.slot + 1 > h->n_slots ? t.slot + 1 : h->n_slots;
-  h->n_preds = h->n_refined = 0;
-  h->arena = nullptr;
-  const char* wb = reinterpret_cast<const char*>(weights);
+// ---- rtpe_hrnet_create: one function per pass over the ops, called in this order.  Together they produce every OpState field
+// and every table of the handle that a forward reads ---------------------------------------------------------------------
 
-  // pass 1: plans + arena layout
+// plans + arena layout: the op descriptors checked, a plan per conv class, the place of every op's weights in the arena
+static int plan_ops(rtpe_hrnet* h, const rtpe_op_desc* ops, int n_ops, size_t weights_bytes) {
+  const int n_tensors = (int)h->tensors.size();
   size_t off = 0;
   h->ops.resize(n_ops);
   for (int i = 0; i < n_ops; ++i) {
@@ -180,10 +169,10 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     const rtpe_op_desc& d = o.d;
     auto bad_t = [&](int t) { return t < 0 || t >= n_tensors; };
     if (d.kind != RTPE_OP_FUSE && d.kind != RTPE_OP_STEM && d.kind != RTPE_OP_AUX_PACK && bad_t(d.in_t)) {
-      set_error("op %d: bad input tensor", i); delete h; return RTPE_E_INVALID;
+      set_error("op %d: bad input tensor", i); return RTPE_E_INVALID;
     }
     if (bad_t(d.out_t) && !(d.flags & RTPE_F_NO_NHWC)) {
-      set_error("op %d: bad output tensor", i); delete h; return RTPE_E_INVALID;
+      set_error("op %d: bad output tensor", i); return RTPE_E_INVALID;
     }
     if (d.flags & RTPE_F_OUT_PREDS) h->n_preds = d.cout;
     if (d.flags & RTPE_F_OUT_REFINED) h->n_refined = d.cout;
@@ -201,20 +190,20 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
       const size_t wbytes = (size_t)d.cin * d.cout * d.ksize * d.ksize * ((d.flags & RTPE_F_F32) ? 4 : 2);
       if (d.w_off < 0 || (size_t)d.w_off + wbytes > weights_bytes ||
           d.ab_off < 0 || (size_t)d.ab_off + 8 * (size_t)d.cout > weights_bytes) {
-        set_error("op %d: weight offsets out of range", i); delete h; return RTPE_E_INVALID;
+        set_error("op %d: weight offsets out of range", i); return RTPE_E_INVALID;
       }
     } else if (d.kind == RTPE_OP_STEM) {
       o.w_dev_off[0] = off;
       off = align_up(off + 27 * 64 * 4, 256);
       o.ab_dev_off = off;
       off = align_up(off + 2 * sizeof(float) * 64, 256);
-      if (d.cout != 64 || d.cin != 3) { set_error("stem must be 3->64"); delete h; return RTPE_E_INVALID; }
+      if (d.cout != 64 || d.cin != 3) { set_error("stem must be 3->64"); return RTPE_E_INVALID; }
     } else if (d.kind == RTPE_OP_FUSE) {
-      if (d.n_terms < 1 || d.n_terms > 4) { set_error("op %d: fuse terms", i); delete h; return RTPE_E_INVALID; }
+      if (d.n_terms < 1 || d.n_terms > 4) { set_error("op %d: fuse terms", i); return RTPE_E_INVALID; }
     } else if (d.kind == RTPE_OP_SE) {
       const size_t wbytes = ((size_t)d.cout * d.cin * 2 + d.cout + d.cin) * 4;
       if (d.w_off < 0 || (size_t)d.w_off + wbytes > weights_bytes) {
-        set_error("op %d: SE weights out of range", i); delete h; return RTPE_E_INVALID;
+        set_error("op %d: SE weights out of range", i); return RTPE_E_INVALID;
       }
       o.w_dev_off[0] = off;
       off = align_up(off + wbytes, 256);
@@ -222,18 +211,23 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
                d.kind == RTPE_OP_SIGMOID_ADD || d.kind == RTPE_OP_RESIZE || d.kind == RTPE_OP_GATE_MUL) {
       if ((d.kind == RTPE_OP_CAM_COMBINE && (bad_t(d.res_t) || bad_t(d.term_t[0]))) ||
           ((d.kind == RTPE_OP_SIGMOID_ADD || d.kind == RTPE_OP_GATE_MUL) && bad_t(d.res_t))) {
-        set_error("op %d: missing operand tensor", i); delete h; return RTPE_E_INVALID;
+        set_error("op %d: missing operand tensor", i); return RTPE_E_INVALID;
       }
     } else if (d.kind == RTPE_OP_AUX_PACK) {
       if (h->tensors[d.out_t].reserved != 4 || h->tensors[d.out_t].channels < 4) {
-        set_error("op %d: the packed second input must be an fp32 tensor of >= 4 channels", i); delete h; return RTPE_E_INVALID;
+        set_error("op %d: the packed second input must be an fp32 tensor of >= 4 channels", i); return RTPE_E_INVALID;
       }
     } else {
-      set_error("op %d: unknown kind %d", i, d.kind); delete h; return RTPE_E_INVALID;
+      set_error("op %d: unknown kind %d", i, d.kind); return RTPE_E_INVALID;
     }
   }
-  // BasicBlock fusion (conv_block.hip): conv 48->48 k3 s1 +relu, then conv 48->48 k3 s1 +residual(+relu)
-  // whose residual is the first conv's input and whose input is read by nobody else
+  h->arena_bytes = off;
+  return RTPE_OK;
+}
+
+// BasicBlock fusion (conv_block.hip): conv 48->48 k3 s1 +relu, then conv 48->48 k3 s1 +residual(+relu)
+// whose residual is the first conv's input and whose input is read by nobody else
+static void mark_blocks(rtpe_hrnet* h) {
   static const int fuse_blocks = getenv("RTPE_FUSE_BLOCKS") ? atoi(getenv("RTPE_FUSE_BLOCKS")) : 1;
   for (size_t i = 0; fuse_blocks && i + 2 < h->ops.size(); ++i) {     // (the last op keeps its own event)
     OpState& a1 = h->ops[i];
@@ -258,7 +252,10 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     a1.fuse = 1;
     a2.fuse = 2;
   }
-  // fused stem (stem_fused.hip): the stem op, then conv 64->64 k3 s2 (+relu) that is the only reader of its output
+}
+
+// fused stem (stem_fused.hip): the stem op, then conv 64->64 k3 s2 (+relu) that is the only reader of its output
+static void mark_stems(rtpe_hrnet* h) {
   for (OpState& o : h->ops) o.stem2 = 0;
   for (size_t i = 0; i + 1 < h->ops.size(); ++i) {
     OpState& a1 = h->ops[i];
@@ -282,8 +279,11 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     a1.stem2 = 1;
     a2.stem2 = 2;
   }
-  // 1x1 pairs (conv_pair.hip): the flags are the program's promise that the head's input and residual stay alive over the
-  // tail; whether the two ops ARE such a pair is checked here (anything else: the flags are ignored)
+}
+
+// 1x1 pairs (conv_pair.hip): the flags are the program's promise that the head's input and residual stay alive over the
+// tail; whether the two ops ARE such a pair is checked here (anything else: the flags are ignored)
+static void mark_pairs(rtpe_hrnet* h) {
   for (OpState& o : h->ops) o.pair = 0;
   for (size_t i = 0; i < h->ops.size(); ++i) {
     OpState& a1 = h->ops[i];
@@ -299,9 +299,12 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     a1.pair = 1;
     h->ops[i + 1].pair = 2;
   }
-  // the skip projection of a pair's head (conv_pair.hip, PROJ): the one op p that writes the head's residual, a conv 1x1
-  // 64 -> 256 + bn of a tensor of the same map size, flagged RTPE_F_PAIR_PROJ (the program's promise that p's INPUT stays
-  // alive over the tail), whose output nobody else reads: the pair kernel computes it from p's input and p launches nothing
+}
+
+// the skip projection of a pair's head (conv_pair.hip, PROJ): the one op p that writes the head's residual, a conv 1x1
+// 64 -> 256 + bn of a tensor of the same map size, flagged RTPE_F_PAIR_PROJ (the program's promise that p's INPUT stays
+// alive over the tail), whose output nobody else reads: the pair kernel computes it from p's input and p launches nothing
+static void mark_projections(rtpe_hrnet* h) {
   for (OpState& o : h->ops) { o.proj_head = 0; o.proj_op = -1; }
   for (size_t i = 0; i < h->ops.size(); ++i) {
     if (h->ops[i].pair != 1) continue;
@@ -333,108 +336,118 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     op.proj_head = (int)i;
     h->ops[i].proj_op = pi;
   }
-  // neighbouring downsampling convs that read the same 48-channel tensor (the first convs of a fuse layer's chains from branch 0,
-  // pose_higher_hrnet.py:213-230: 48 -> 96 to branch 1, 48 -> 48 towards branches 2 and 3): one launch of conv48s2.hip reads the
-  // input once for all of them.  Static conditions here, the launch's own (sizes, layouts, option) in route_ops()
+}
+
+// neighbouring downsampling convs that read the same 48-channel tensor (the first convs of a fuse layer's chains from branch 0,
+// pose_higher_hrnet.py:213-230: 48 -> 96 to branch 1, 48 -> 48 towards branches 2 and 3): one launch of conv48s2.hip reads the
+// input once for all of them.  Static conditions here, the launch's own (sizes, layouts, option) in route_ops()
+static void mark_s2_groups(rtpe_hrnet* h) {
   for (OpState& o : h->ops) o.s2g = 0;
-  {
-    auto s2_static = [&](const OpState& o) {
-      const rtpe_op_desc& d = o.d;
-      return d.kind == RTPE_OP_CONV && d.ksize == 3 && d.stride == 2 && d.cin == 48 && (d.cout == 48 || d.cout == 96) && d.res_t < 0 &&
-             !(d.flags & (RTPE_F_NO_NHWC | RTPE_F_F32 | RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED)) && o.n_geom == 1 && o.plan[0].esize == 2 &&
-             o.plan[0].cout_pad == d.cout && d.reserved[2] <= 0;
-    };
-    static const int s2_groups = env_int("RTPE_S2_GROUPS", 1);
-    for (size_t i = 0; s2_groups && i < h->ops.size(); ++i) {
-      if (h->ops[i].s2g != 0 || !s2_static(h->ops[i])) continue;
-      const rtpe_op_desc& d0 = h->ops[i].d;
-      int n = 1, groups = d0.cout / 48;
-      while (i + n < h->ops.size() && n < 3) {
-        const OpState& on = h->ops[i + n];
-        const rtpe_op_desc& dn = on.d;
-        bool ok = s2_static(on) && dn.in_t == d0.in_t && dn.in_coff == d0.in_coff && dn.lane == d0.lane && dn.region == d0.region &&
-                  (dn.flags & RTPE_F_ROUND_CONV) == (d0.flags & RTPE_F_ROUND_CONV) && groups + dn.cout / 48 <= 4;
-        for (int m = 0; m < n && ok; ++m) ok = h->ops[i + m].d.out_t != dn.out_t && dn.out_t != d0.in_t;
-        if (!ok) break;
-        groups += dn.cout / 48;
-        ++n;
-      }
-      if (n < 2) continue;
-      h->ops[i].s2g = n;
-      for (int m = 1; m < n; ++m) h->ops[i + m].s2g = -1;
+  auto s2_static = [&](const OpState& o) {
+    const rtpe_op_desc& d = o.d;
+    return d.kind == RTPE_OP_CONV && d.ksize == 3 && d.stride == 2 && d.cin == 48 && (d.cout == 48 || d.cout == 96) && d.res_t < 0 &&
+           !(d.flags & (RTPE_F_NO_NHWC | RTPE_F_F32 | RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED)) && o.n_geom == 1 && o.plan[0].esize == 2 &&
+           o.plan[0].cout_pad == d.cout && d.reserved[2] <= 0;
+  };
+  static const int s2_groups = env_int("RTPE_S2_GROUPS", 1);
+  for (size_t i = 0; s2_groups && i < h->ops.size(); ++i) {
+    if (h->ops[i].s2g != 0 || !s2_static(h->ops[i])) continue;
+    const rtpe_op_desc& d0 = h->ops[i].d;
+    int n = 1, groups = d0.cout / 48;
+    while (i + n < h->ops.size() && n < 3) {
+      const OpState& on = h->ops[i + n];
+      const rtpe_op_desc& dn = on.d;
+      bool ok = s2_static(on) && dn.in_t == d0.in_t && dn.in_coff == d0.in_coff && dn.lane == d0.lane && dn.region == d0.region &&
+                (dn.flags & RTPE_F_ROUND_CONV) == (d0.flags & RTPE_F_ROUND_CONV) && groups + dn.cout / 48 <= 4;
+      for (int m = 0; m < n && ok; ++m) ok = h->ops[i + m].d.out_t != dn.out_t && dn.out_t != d0.in_t;
+      if (!ok) break;
+      groups += dn.cout / 48;
+      ++n;
     }
+    if (n < 2) continue;
+    h->ops[i].s2g = n;
+    for (int m = 1; m < n; ++m) h->ops[i + m].s2g = -1;
   }
-  h->arena_bytes = off;
-  {
-    // cross-lane dependencies inside parallel regions: the last writer of every tensor an op reads, when it ran on
-    // another lane of the same region (a region starts with a fork from and ends with a join into the caller's stream,
-    // so nothing outside it needs an event)
-    h->needs_event.assign(n_ops, 0);
-    h->wait_ops.assign(n_ops, std::vector<int>());
-    std::vector<int> writer(h->tensors.size(), -1);
-    std::vector<std::vector<int>> readers(h->tensors.size());     // ops that read a tensor since its last writer
-    for (int i = 0; i < n_ops; ++i) {
-      const rtpe_op_desc& d = h->ops[i].d;
-      if (d.lane < 0 || d.lane > 3 || d.region < 0) { set_error("op %d: lane %d region %d", i, d.lane, d.region); delete h; return RTPE_E_INVALID; }
-      if (d.region > 0) h->has_regions = true;
-      if (d.region == 0 && d.lane != 0) { set_error("op %d: a lane outside a region", i); delete h; return RTPE_E_INVALID; }
-      std::vector<int> reads;
-      if (d.kind != RTPE_OP_FUSE && d.in_t >= 0) reads.push_back(d.in_t);
-      if (d.res_t >= 0) reads.push_back(d.res_t);
-      for (int t = 0; t < d.n_terms; ++t) reads.push_back(d.term_t[t]);
-      if (d.out_t >= 0) reads.push_back(d.out_t);          // (a second writer of a shared buffer: ordered behind the first)
-      for (int t : reads) {
-        const int j = writer[t];
-        if (j >= 0 && h->ops[j].d.region == d.region && d.region > 0 && h->ops[j].d.lane != d.lane) {
+}
+
+// cross-lane dependencies inside parallel regions: the last writer of every tensor an op reads, when it ran on
+// another lane of the same region (a region starts with a fork from and ends with a join into the caller's stream,
+// so nothing outside it needs an event)
+static int mark_lane_waits(rtpe_hrnet* h) {
+  const int n_ops = (int)h->ops.size();
+  h->needs_event.assign(n_ops, 0);
+  h->wait_ops.assign(n_ops, std::vector<int>());
+  std::vector<int> writer(h->tensors.size(), -1);
+  std::vector<std::vector<int>> readers(h->tensors.size());     // ops that read a tensor since its last writer
+  for (int i = 0; i < n_ops; ++i) {
+    const rtpe_op_desc& d = h->ops[i].d;
+    if (d.lane < 0 || d.lane > 3 || d.region < 0) { set_error("op %d: lane %d region %d", i, d.lane, d.region); return RTPE_E_INVALID; }
+    if (d.region > 0) h->has_regions = true;
+    if (d.region == 0 && d.lane != 0) { set_error("op %d: a lane outside a region", i); return RTPE_E_INVALID; }
+    std::vector<int> reads;
+    if (d.kind != RTPE_OP_FUSE && d.in_t >= 0) reads.push_back(d.in_t);
+    if (d.res_t >= 0) reads.push_back(d.res_t);
+    for (int t = 0; t < d.n_terms; ++t) reads.push_back(d.term_t[t]);
+    if (d.out_t >= 0) reads.push_back(d.out_t);          // (a second writer of a shared buffer: ordered behind the first)
+    for (int t : reads) {
+      const int j = writer[t];
+      if (j >= 0 && h->ops[j].d.region == d.region && d.region > 0 && h->ops[j].d.lane != d.lane) {
+        h->needs_event[j] = 1;
+        h->wait_ops[i].push_back(j);
+      }
+    }
+    // write after read: a lane that overwrites a tensor (an in-place op, a shared slot written through `into=`) waits
+    // for the ops of OTHER lanes that read the previous contents
+    if (d.out_t >= 0) {
+      for (int j : readers[d.out_t]) {
+        if (j != i && h->ops[j].d.region == d.region && d.region > 0 && h->ops[j].d.lane != d.lane) {
           h->needs_event[j] = 1;
           h->wait_ops[i].push_back(j);
         }
       }
-      // write after read: a lane that overwrites a tensor (an in-place op, a shared slot written through `into=`) waits
-      // for the ops of OTHER lanes that read the previous contents
-      if (d.out_t >= 0) {
-        for (int j : readers[d.out_t]) {
-          if (j != i && h->ops[j].d.region == d.region && d.region > 0 && h->ops[j].d.lane != d.lane) {
-            h->needs_event[j] = 1;
-            h->wait_ops[i].push_back(j);
-          }
-        }
-        readers[d.out_t].clear();
-      }
-      if (d.kind != RTPE_OP_FUSE && d.in_t >= 0) readers[d.in_t].push_back(i);
-      if (d.res_t >= 0) readers[d.res_t].push_back(i);
-      for (int t = 0; t < d.n_terms; ++t) readers[d.term_t[t]].push_back(i);
-      if (d.out_t >= 0) writer[d.out_t] = i;
+      readers[d.out_t].clear();
     }
+    if (d.kind != RTPE_OP_FUSE && d.in_t >= 0) readers[d.in_t].push_back(i);
+    if (d.res_t >= 0) readers[d.res_t].push_back(i);
+    for (int t = 0; t < d.n_terms; ++t) readers[d.term_t[t]].push_back(i);
+    if (d.out_t >= 0) writer[d.out_t] = i;
   }
-  {
-    static const int plane_major = getenv("RTPE_PLANE_MAJOR") ? atoi(getenv("RTPE_PLANE_MAJOR")) : 1;
-    h->plane_ok.assign(h->tensors.size(), 0);
-    for (size_t t = 0; plane_major && t < h->tensors.size(); ++t) {
-      const rtpe_tensor_desc& td = h->tensors[t];
-      if (td.reserved == 4 || td.channels < 96 || td.channels % 48 != 0) continue;
-      bool ok = true, touched = false;
-      for (const OpState& o : h->ops) {
-        const rtpe_op_desc& d = o.d;
-        bool uses = d.in_t == (int)t || d.out_t == (int)t || d.res_t == (int)t;
-        for (int k = 0; k < d.n_terms; ++k) uses |= d.term_t[k] == (int)t;
-        if (!uses) continue;
-        touched = true;
-        const int clean = RTPE_F_RELU | RTPE_F_ROUND_CONV;
-        if (d.kind != RTPE_OP_CONV || o.n_geom != 1 || d.n_terms != 0 || (d.flags & ~clean) || d.ksize != 3 ||
-            d.stride != 1 || !conv_stream_supports(o.plan[0]) || o.plan[0].mt != 3 || d.cout % 48 != 0 ||
-            d.in_coff != 0 || d.out_coff != 0 || (d.res_t >= 0 && d.res_coff != 0) || d.reserved[2] != 0 ||
-            d.cin != h->tensors[d.in_t].channels || d.cout != h->tensors[d.out_t].channels ||
-            (d.res_t >= 0 && h->tensors[d.res_t].channels != d.cout)) {
-          ok = false;
-          break;
-        }
-      }
-      h->plane_ok[t] = ok && touched;
-    }
-  }
+  return RTPE_OK;
+}
 
-  // pass 2: pack on the host, one upload
+// tensors that may be kept plane-major (rtpe_hrnet::plane_ok)
+static void mark_plane_major(rtpe_hrnet* h) {
+  static const int plane_major = getenv("RTPE_PLANE_MAJOR") ? atoi(getenv("RTPE_PLANE_MAJOR")) : 1;
+  h->plane_ok.assign(h->tensors.size(), 0);
+  for (size_t t = 0; plane_major && t < h->tensors.size(); ++t) {
+    const rtpe_tensor_desc& td = h->tensors[t];
+    if (td.reserved == 4 || td.channels < 96 || td.channels % 48 != 0) continue;
+    bool ok = true, touched = false;
+    for (const OpState& o : h->ops) {
+      const rtpe_op_desc& d = o.d;
+      bool uses = d.in_t == (int)t || d.out_t == (int)t || d.res_t == (int)t;
+      for (int k = 0; k < d.n_terms; ++k) uses |= d.term_t[k] == (int)t;
+      if (!uses) continue;
+      touched = true;
+      const int clean = RTPE_F_RELU | RTPE_F_ROUND_CONV;
+      if (d.kind != RTPE_OP_CONV || o.n_geom != 1 || d.n_terms != 0 || (d.flags & ~clean) || d.ksize != 3 ||
+          d.stride != 1 || !conv_stream_supports(o.plan[0]) || o.plan[0].mt != 3 || d.cout % 48 != 0 ||
+          d.in_coff != 0 || d.out_coff != 0 || (d.res_t >= 0 && d.res_coff != 0) || d.reserved[2] != 0 ||
+          d.cin != h->tensors[d.in_t].channels || d.cout != h->tensors[d.out_t].channels ||
+          (d.res_t >= 0 && h->tensors[d.res_t].channels != d.cout)) {
+        ok = false;
+        break;
+      }
+    }
+    h->plane_ok[t] = ok && touched;
+  }
+}
+
+// pack on the host, one upload
+static int pack_and_upload(rtpe_hrnet* h, const void* weights) {
+  const char* wb = reinterpret_cast<const char*>(weights);
+  const int n_ops = (int)h->ops.size();
+  const size_t off = h->arena_bytes;
   std::vector<char> host(off, 0);
   for (int i = 0; i < n_ops; ++i) {
     OpState& o = h->ops[i];
@@ -462,9 +475,44 @@ extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
     }
   }
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->arena), off ? off : 256);
-  if (e != hipSuccess) { delete h; return hip_fail(e, "hipMalloc(arena)", __FILE__, __LINE__); }
+  if (e != hipSuccess) { h->arena = nullptr; return hip_fail(e, "hipMalloc(arena)", __FILE__, __LINE__); }
   e = hipMemcpy(h->arena, host.data(), off, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(h->arena); delete h; return hip_fail(e, "hipMemcpy(arena)", __FILE__, __LINE__); }
+  if (e != hipSuccess) return hip_fail(e, "hipMemcpy(arena)", __FILE__, __LINE__);     // (the caller frees the arena)
+  return RTPE_OK;
+}
+
+extern "C" int rtpe_hrnet_create(const rtpe_op_desc* ops, int32_t n_ops,
+                                 const rtpe_tensor_desc* tensors, int32_t n_tensors,
+                                 const void* weights, size_t weights_bytes, int32_t device,
+                                 rtpe_hrnet** out) {
+  RTPE_REQUIRE(ops && tensors && weights && out && n_ops > 0 && n_tensors > 0, "hrnet_create: null argument");
+  DeviceGuard guard(device);               // the caller's current device is restored on return
+  RTPE_HIP_CHECK(guard.err);
+  rtpe_hrnet* h = new rtpe_hrnet();
+  h->device = device;
+  h->tensors.assign(tensors, tensors + n_tensors);
+  h->n_slots = 0;
+  for (auto& t : h->tensors) h->n_slots = t.slot + 1 > h->n_slots ? t.slot + 1 : h->n_slots;
+  h->n_preds = h->n_refined = 0;
+  h->arena = nullptr;
+  int rc = plan_ops(h, ops, n_ops, weights_bytes);
+  if (rc == RTPE_OK) {
+    mark_blocks(h);
+    mark_stems(h);
+    mark_pairs(h);
+    mark_projections(h);
+    mark_s2_groups(h);
+    rc = mark_lane_waits(h);
+  }
+  if (rc == RTPE_OK) {
+    mark_plane_major(h);
+    rc = pack_and_upload(h, weights);
+  }
+  if (rc != RTPE_OK) {                     // (the message of the pass that failed stands)
+    if (h->arena) hipFree(h->arena);
+    delete h;
+    return rc;
+  }
   *out = h;
   return RTPE_OK;
 }
@@ -906,46 +954,47 @@ static int read_op_times(const std::vector<Route>& r, const std::vector<hipEvent
   return RTPE_OK;
 }
 
-static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, void* preds, void* refined,
-               int out_dtype, void* ws, size_t ws_bytes, hipStream_t s_main, float* op_ms, int n_ms,
-               rtpe_record* rec = nullptr, const void* aux = nullptr, uint32_t fwd_flags = 0, const int32_t* ext = nullptr) {
-  RTPE_REQUIRE(h && x && ws, "forward: null argument");
-  static const int host_prof = env_int("RTPE_HOST_PROF", 0);       // host time of a forward: where it goes (stderr)
-  typedef std::chrono::steady_clock hclock;
-  const hclock::time_point hp0 = hclock::now();
-  double hp_launch = 0.0;
-#define RTPE_HP_LAUNCH(stmt)                                                                   \
-  do {                                                                                         \
-    if (host_prof) {                                                                           \
-      const hclock::time_point t_ = hclock::now();                                             \
-      stmt;                                                                                    \
-      hp_launch += std::chrono::duration<double, std::micro>(hclock::now() - t_).count();      \
-    } else {                                                                                   \
-      stmt;                                                                                    \
-    }                                                                                          \
-  } while (0)
-  // kernels, events and function attributes act on HIP's CURRENT device: make the handle's device current for
-  // the call (the stream and every buffer must belong to it) and give the caller's device back afterwards
-  DeviceGuard guard(h->device);
-  RTPE_HIP_CHECK(guard.err);
-  {
-    const int rc = check_shape(h, N, H, W, "forward", ext != nullptr);
-    if (rc != RTPE_OK) return rc;
-  }
-  RTPE_REQUIRE(x_dtype == RTPE_DTYPE_F16 || x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
-  RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F16 || out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
-  const Fwd f(h, N, H, W, ws, preds, refined, out_dtype, ext);
-  if (f.ws_need > ws_bytes) { set_error("forward: workspace %zu < %zu", ws_bytes, f.ws_need); return RTPE_E_NOMEM; }
-  RTPE_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
-  // Shapes an op cannot take are refused here, before the first launch, so that no half-run forward is left behind.
+// ---- one forward: run() and its parts ------------------------------------------------------------------------------------
+namespace {   // (the classes below are the executor's own: nothing of them is exported)
+
+// What a forward is called with.  The entries fill the bound part through fwd_call() and set the rest where they are about it
+struct FwdCall {
+  const void* x = nullptr;                       // the images, NCHW
+  int x_dtype = 0, N = 0, H = 0, W = 0;
+  void *preds = nullptr, *refined = nullptr;     // the two NCHW outputs
+  int out_dtype = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  hipStream_t stream = nullptr;                  // the caller's stream
+  const void* aux = nullptr;                     // the second input (rtpe_hrnet_forward_aux)
+  uint32_t flags = 0;                            // RTPE_FWD_*
+  const int32_t* ext = nullptr;                  // a mixed-size batch: the extent table on the device
+  float* op_ms = nullptr;                        // a timed forward (host-returning): the per-op times, room for n_ms of them
+  int n_ms = 0;
+  rtpe_record* rec = nullptr;                    // a recorded forward: the events stay with the handle
+};
+
+static FwdCall fwd_call(const void* x, int x_dtype, int N, int H, int W, void* preds, void* refined, int out_dtype, void* ws,
+                        size_t ws_bytes, void* stream) {
+  FwdCall c;
+  c.x = x; c.x_dtype = x_dtype; c.N = N; c.H = H; c.W = W;
+  c.preds = preds; c.refined = refined; c.out_dtype = out_dtype;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = reinterpret_cast<hipStream_t>(stream);
+  return c;
+}
+
+// What the ops cannot take is refused here, before the first launch, so that no half-run forward is left behind
+static int check_ops(const Fwd& f, const FwdCall& c) {
+  const rtpe_hrnet* h = f.h;
+  RTPE_REQUIRE(c.op_ms == nullptr || c.n_ms >= (int)h->ops.size(), "forward_timed: op_ms too small");
   // avgpool: the kernel writes ceil(Hi / 2) x ceil(Wi / 2) pixels, the output tensor holds extent(H, ds) x extent(W, ds): a
   // map with an odd side (1 x 1, 2 x 1) of an input that is a multiple of 32 would be written beyond its tensor (a ragged
   // input's tensors hold the ceil)
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const rtpe_op_desc& d = h->ops[i].d;
     if (d.kind != RTPE_OP_AVGPOOL) continue;
-    const int Hi = extent(H, h->tensors[d.in_t].ds_log2), Wi = extent(W, h->tensors[d.in_t].ds_log2);
-    const int Ho = extent(H, h->tensors[d.out_t].ds_log2), Wo = extent(W, h->tensors[d.out_t].ds_log2);
+    const int Hi = extent(f.H, h->tensors[d.in_t].ds_log2), Wi = extent(f.W, h->tensors[d.in_t].ds_log2);
+    const int Ho = extent(f.H, h->tensors[d.out_t].ds_log2), Wo = extent(f.W, h->tensors[d.out_t].ds_log2);
     RTPE_REQUIRE((Hi + 1) / 2 == Ho && (Wi + 1) / 2 == Wo,
                  "avgpool: a %d x %d map does not pool into the %d x %d output tensor", Hi, Wi, Ho, Wo);
   }
@@ -977,327 +1026,446 @@ static int run(rtpe_hrnet* h, const void* x, int x_dtype, int N, int H, int W, v
       RTPE_REQUIRE(d.cout > 0 && d.cout % 8 == 0, "op %zu: the fp16 form of this op needs a channel count that is a multiple of 8 (%d)", i, d.cout);
     }
   }
-  std::vector<Route> routes;
-  std::vector<ConvArgs> args;
-  {
-    const int rc = route_ops(f, &routes, &args);
-    if (rc != RTPE_OK) return rc;
-  }
-  auto tptr = [&](int t, int coff) { return f.tptr(t, coff); };
-  std::vector<hipEvent_t> ev;
-  const bool timed = op_ms != nullptr;
-  if (timed) {
-    RTPE_REQUIRE(n_ms >= (int)h->ops.size(), "forward_timed: op_ms too small");
-    ev.resize(h->ops.size() + 1);
-    for (auto& e : ev) RTPE_HIP_CHECK(hipEventCreate(&e));
-    RTPE_HIP_CHECK(hipEventRecord(ev[0], s_main));
-  }
-  if (rec) {                         // non-blocking recording into caller-kept events
-    if (rec->ev.size() != h->ops.size() + 1) {
-      for (auto& e : rec->ev) hipEventDestroy(e);
-      rec->ev.resize(h->ops.size() + 1);
-      for (auto& e : rec->ev) RTPE_HIP_CHECK(hipEventCreate(&e));
-    }
-    rec->routes = routes;
-    RTPE_HIP_CHECK(hipEventRecord(rec->ev[0], s_main));
-  }
-  // Parallel regions (the branches of a HighResolutionModule, pose_higher_hrnet.py:242-243, and the conversion convs of
-  // its fuse layers are independent): with lanes on, the ops of lane k > 0 go to an internal stream that forks from the
-  // caller's stream at the region's first op and joins it behind its last; an op waits for the events of the ops of
-  // other lanes whose output it reads.  Timed / recorded runs stay on one stream (one op after another).
-  bool lanes_on = false;
-  if (h->has_regions && !timed && rec == nullptr && !(fwd_flags & RTPE_FWD_NO_LANES)) {
-    const int opt = get_option(kOptLanes);
-    lanes_on = opt == 1 || (opt == 2 && (long long)N * H * W <= 4ll * 640 * 640);
-  }
-  std::unique_lock<std::mutex> lane_lock;
-  if (lanes_on) lane_lock = std::unique_lock<std::mutex>(h->lane_mu);   // held until the last region has joined (return)
-  if (lanes_on && h->fork_event == nullptr) {
-    for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking));
-    h->op_event.assign(h->ops.size() + 4, nullptr);
-    for (size_t i = 0; i < h->ops.size(); ++i)
-      if (h->needs_event[i]) RTPE_HIP_CHECK(hipEventCreateWithFlags(&h->op_event[i], hipEventDisableTiming));
-    for (size_t l = 0; l < 4; ++l) RTPE_HIP_CHECK(hipEventCreateWithFlags(&h->op_event[h->ops.size() + l], hipEventDisableTiming));
-    RTPE_HIP_CHECK(hipEventCreateWithFlags(&h->fork_event, hipEventDisableTiming));
-  }
-  int cur_region = 0;
-  bool lane_used[4] = {false, false, false, false};
-  auto join_lanes = [&]() -> hipError_t {
-    for (int l = 1; l < 4; ++l) {
-      if (!lane_used[l]) continue;
-      hipEvent_t e = h->op_event[h->ops.size() + l];
-      hipError_t er = hipEventRecord(e, h->lane_stream[l]);
-      if (er == hipSuccess) er = hipStreamWaitEvent(s_main, e, 0);
-      if (er != hipSuccess) return er;
-      lane_used[l] = false;
-    }
-    return hipSuccess;
-  };
-  for (size_t i = 0; i < h->ops.size(); ++i) {
-    const OpState& o = h->ops[i];
+  // what the call must bring for an op: the second input, and an fp32 `preds` for the sigmoid map that sigmoid_add and
+  // gate_mul emit
+  for (const OpState& o : h->ops) {
     const rtpe_op_desc& d = o.d;
-    const Route& r = routes[i];
-    int rc = RTPE_OK;
-    hipStream_t s = s_main;
-    if (lanes_on) {
-      if (d.region != cur_region) {
-        if (cur_region > 0) RTPE_HIP_CHECK(join_lanes());
-        cur_region = d.region;
-        if (cur_region > 0) {                            // fork: every lane starts behind what the caller's stream holds
-          RTPE_HIP_CHECK(hipEventRecord(h->fork_event, s_main));
-          for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamWaitEvent(h->lane_stream[l], h->fork_event, 0));
-        }
-      }
-      if (cur_region > 0) {
-        if (d.lane > 0) { s = h->lane_stream[d.lane]; lane_used[d.lane] = true; }
-        // the op's own waits and those of the ops behind it that this launch computes (a block's second conv, the stem's
-        // conv2, the other convs of a stride-2 group)
-        for (size_t j = i; j == i || (j < routes.size() && routes[j].how == kRouteDoneBy && routes[j].by == (int)i); ++j)
-          for (int w : h->wait_ops[j]) RTPE_HIP_CHECK(hipStreamWaitEvent(s, h->op_event[w], 0));
-      }
-    }
-    switch (r.how) {
-      case kRouteDoneBy: case kRoutePairHead: case kRoutePairProj:      // computed by the launch at op r.by
-        break;
-      case kRouteStemFused: case kRouteStemConv1: {
-        // conv1 + bn1 + relu + conv2 + bn2 + relu in one kernel: the half-resolution map stays in LDS (stem_fused.hip); or,
-        // option "fused_stem" = 2, the stem op alone on that kernel's conv1 code (the chain on the matrix pipe), output to
-        // memory - the bit-identity test of that chain against the VALU kernel
-        StemFusedArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
-        a.w1 = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
-        a.alpha1 = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-        a.beta1 = a.alpha1 + 64;
-        a.N = N; a.H = H; a.W = W;
-        if (r.how == kRouteStemFused) {
-          const OpState& o2 = h->ops[i + 1];
-          const rtpe_op_desc& d2 = o2.d;
-          a.w2 = reinterpret_cast<const _Float16*>(h->arena + o2.w_dev_off[0]);
-          a.alpha2 = reinterpret_cast<const float*>(h->arena + o2.ab_dev_off);
-          a.beta2 = a.alpha2 + o2.plan[0].cout_pad;
-          a.y = tptr(d2.out_t, d2.out_coff);
-          a.out_ld = h->tensors[d2.out_t].channels;
-          a.relu = (d2.flags & RTPE_F_RELU) ? 1 : 0;
-          a.round_conv = (d2.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
-        } else {
-          a.y1 = tptr(d.out_t, d.out_coff);
-          a.out_ld = h->tensors[d.out_t].channels;
-        }
-        RTPE_HP_LAUNCH(rc = stem_fused_launch(a, s));
-        break;
-      }
-      case kRouteStemPlain: {
-        StemArgs a;
-        a.x = x; a.x_f32 = x_dtype == RTPE_DTYPE_F32;
-        a.w = reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]);
-        a.alpha = reinterpret_cast<const float*>(h->arena + o.ab_dev_off);
-        a.beta = a.alpha + 64;
-        a.y = tptr(d.out_t, d.out_coff);
-        a.N = N; a.H = H; a.W = W; a.out_ld = h->tensors[d.out_t].channels;
-        a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
-        a.ext = ext ? f.level(0) : nullptr;
-        RTPE_HP_LAUNCH(rc = stem_launch(a, s));
-        break;
-      }
-      case kRouteBlock: {
-        const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-        const int Hi = extent(H, ti.ds_log2), Wi = extent(W, ti.ds_log2);
-        const OpState& o2 = h->ops[i + 1];
-        RTPE_HP_LAUNCH(rc = conv_block_launch(tptr(d.in_t, d.in_coff), ti.channels,
-                               ((size_t)N * Hi * Wi * ti.channels - (size_t)d.in_coff) * 2,
-                               tptr(o2.d.out_t, o2.d.out_coff), h->tensors[o2.d.out_t].channels,
-                               reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]),
-                               reinterpret_cast<const float*>(h->arena + o.ab_dev_off),
-                               reinterpret_cast<const _Float16*>(h->arena + o2.w_dev_off[0]),
-                               reinterpret_cast<const float*>(h->arena + o2.ab_dev_off), N, Hi, Wi, s));
-        break;
-      }
-      case kRouteS2Group: {
-        const ConvPlan* plans[3];
-        for (int m = 0; m < r.by; ++m) plans[m] = &h->ops[i + m].plan[0];
-        RTPE_HP_LAUNCH(rc = conv48s2_launch_group(plans, &args[i], r.by, s));
-        break;
-      }
-      case kRoutePairTail: {   // with the head and, where it is folded, the head's skip projection
-        const OpState& oh = h->ops[r.by];
-        const bool proj = oh.proj_op >= 0 && routes[oh.proj_op].how == kRoutePairProj;
-        RTPE_HP_LAUNCH(rc = conv_pair_launch(oh.plan[0], args[r.by], o.plan[0], args[i], s, proj ? &h->ops[oh.proj_op].plan[0] : nullptr,
-                                             proj ? &args[oh.proj_op] : nullptr));
-        break;
-      }
-      case kRouteDeconvMerged: case kRouteDeconv48:
-        RTPE_HP_LAUNCH(rc = launch_conv(r.how, o.plan[0], r.tile[0], args[i], s));
-        break;
-      case kRouteTile: case kRouteStream: case kRouteDirect: case kRouteConv64: case kRouteHead: case kRouteS2:
-        // a conv on the kernel of its launch shape (a launch per class) or on the head / stride-2 kernel
-        for (int k = 0; k < o.n_geom && rc == RTPE_OK; ++k)
-          RTPE_HP_LAUNCH(rc = launch_conv(r.how, o.plan[k], r.tile[k], k ? conv_op_args(f, i, k, r.tile[k]) : args[i], s));
-        break;
-      default: {   // kRouteNone: the elementwise and student ops
-        if (d.kind == RTPE_OP_AUX_PACK) {
-          if (aux == nullptr) { set_error("forward: this program has a second input (use rtpe_hrnet_forward_aux)"); return RTPE_E_INVALID; }
-          const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          rc = aux_pack_launch(reinterpret_cast<const float*>(aux), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)),
-                               to.channels, N, extent(H, to.ds_log2), extent(W, to.ds_log2), s);
-        } else if (d.kind == RTPE_OP_RESIZE) {
-          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-          const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          rc = resize_nhwc_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, extent(H, ti.ds_log2),
-                                  extent(W, ti.ds_log2), reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels,
-                                  extent(H, to.ds_log2), extent(W, to.ds_log2), d.cout, N, s);
-        } else if (d.kind == RTPE_OP_GATE_MUL) {
-          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-          const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          const size_t pixels = (size_t)N * extent(H, ti.ds_log2) * extent(W, ti.ds_log2);
-          float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
-          if ((d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
-            set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
-          }
-          float div;
-          memcpy(&div, &d.reserved[0], sizeof(float));
-          rc = gate_mul_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                               reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                               reinterpret_cast<float*>(tptr(d.out_t, d.out_coff)), to.channels, d.cout, pixels, div, att_out, s);
-        } else if (d.kind == RTPE_OP_CAST || d.kind == RTPE_OP_AVGPOOL || d.kind == RTPE_OP_SE ||
-                   d.kind == RTPE_OP_CAM_COMBINE || d.kind == RTPE_OP_SIGMOID_ADD) {
-          const rtpe_tensor_desc& ti = h->tensors[d.in_t];
-          const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          const int Hi = extent(H, ti.ds_log2), Wi = extent(W, ti.ds_log2);
-          const size_t pixels = (size_t)N * Hi * Wi;
-          float* yo = reinterpret_cast<float*>(tptr(d.out_t, d.out_coff));
-          const bool h16 = !(d.flags & RTPE_F_F32) && d.kind != RTPE_OP_CAST;    // the fp16 forms (checked before the first launch)
-          const int* ext_in = ext ? f.level(ti.ds_log2) : nullptr;            // avgpool, se: image n's own part of the map
-          float* att_out = (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(preds) : nullptr;
-          if (d.kind == RTPE_OP_SIGMOID_ADD && (d.flags & RTPE_F_OUT_PREDS) && (!preds || out_dtype != RTPE_DTYPE_F32)) {
-            set_error("forward: the sigmoid map output must be a float32 buffer"); return RTPE_E_INVALID;
-          }
-          if (d.kind == RTPE_OP_CAST) {
-            rc = cast_launch(tptr(d.in_t, d.in_coff), ti.channels, yo, to.channels, d.cout, pixels, s);
-          } else if (h16 && d.kind == RTPE_OP_AVGPOOL) {
-            rc = avgpool_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.out_t, d.out_coff), to.channels, d.cout, N, Hi, Wi, s, ext_in);
-          } else if (h16 && d.kind == RTPE_OP_SE) {
-            rc = se_launch(tptr(d.in_t, d.in_coff), ti.channels, d.cin, d.cout, N, Hi * Wi,
-                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), tptr(d.out_t, d.out_coff), to.channels, s, ext_in, Wi);
-          } else if (h16 && d.kind == RTPE_OP_CAM_COMBINE) {
-            rc = cam_combine_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.res_t, d.res_coff), h->tensors[d.res_t].channels,
-                                    tptr(d.term_t[0], 0), h->tensors[d.term_t[0]].channels, tptr(d.out_t, d.out_coff),
-                                    to.channels, d.cout, N, (size_t)Hi * Wi, s);
-          } else if (h16) {
-            rc = sigmoid_add_launch(tptr(d.in_t, d.in_coff), ti.channels, tptr(d.res_t, d.res_coff), h->tensors[d.res_t].channels,
-                                    tptr(d.out_t, d.out_coff), to.channels, d.cout, pixels, att_out, s);
-          } else if (d.kind == RTPE_OP_AVGPOOL) {
-            rc = avgpool_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, yo, to.channels,
-                                d.cout, N, Hi, Wi, s, ext_in);
-          } else if (d.kind == RTPE_OP_SE) {
-            rc = se_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels, d.cin, d.cout, N, Hi * Wi,
-                           reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), yo, to.channels, s, ext_in, Wi);
-          } else if (d.kind == RTPE_OP_CAM_COMBINE) {
-            rc = cam_combine_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                                    reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                                    reinterpret_cast<const float*>(tptr(d.term_t[0], 0)), h->tensors[d.term_t[0]].channels,
-                                    yo, to.channels, d.cout, N, (size_t)Hi * Wi, s);
-          } else {
-            rc = sigmoid_add_launch(reinterpret_cast<const float*>(tptr(d.in_t, d.in_coff)), ti.channels,
-                                    reinterpret_cast<const float*>(tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels,
-                                    yo, to.channels, d.cout, pixels, att_out, s);
-          }
-        } else {  // FUSE
-          const rtpe_tensor_desc& to = h->tensors[d.out_t];
-          FuseArgs a;
-          memset(&a, 0, sizeof(a));
-          a.n_terms = d.n_terms;
-          for (int t = 0; t < d.n_terms; ++t) {
-            a.term[t] = tptr(d.term_t[t], 0);
-            a.term_ld[t] = h->tensors[d.term_t[t]].channels;
-            a.term_up[t] = d.term_up[t];
-          }
-          a.y = tptr(d.out_t, d.out_coff);
-          a.out_ld = to.channels; a.C = d.cout;
-          a.N = N; a.H = extent(H, to.ds_log2); a.W = extent(W, to.ds_log2);
-          a.nearest = f.rag ? 1 : 0;
-          for (int t = 0; t < d.n_terms; ++t) {
-            a.term_h[t] = extent(H, h->tensors[d.term_t[t]].ds_log2);
-            a.term_w[t] = extent(W, h->tensors[d.term_t[t]].ds_log2);
-            if (ext) a.ext_term[t] = f.level(h->tensors[d.term_t[t]].ds_log2);
-          }
-          if (ext) a.ext_out = f.level(to.ds_log2);
-          a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
-          a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
-          RTPE_HP_LAUNCH(rc = fuse_launch(a, s));
-        }
-        break;
-      }
-    }
-    if (rc != RTPE_OK) return rc;
-    if (lanes_on && cur_region > 0) {
-      // (a 1x1 pair is ONE kernel, launched at the tail's place: the head's output exists behind that launch)
-      if (h->needs_event[i] && r.how != kRoutePairHead) RTPE_HIP_CHECK(hipEventRecord(h->op_event[i], s));
-      if (r.how == kRoutePairTail && h->needs_event[r.by]) RTPE_HIP_CHECK(hipEventRecord(h->op_event[r.by], s));
-    }
-    const bool has_event = op_has_event(routes, i);
-    if (timed && has_event) RTPE_HIP_CHECK(hipEventRecord(ev[i + 1], s));
-    if (rec && has_event) RTPE_HIP_CHECK(hipEventRecord(rec->ev[i + 1], s));
-  }
-  if (lanes_on && cur_region > 0) RTPE_HIP_CHECK(join_lanes());
-  if (ext != nullptr) {
-    // a mixed-size batch: whatever the forward left outside an image's own region of the two outputs becomes 0.0
-    float* y[2] = {nullptr, nullptr};
-    int C[2] = {0, 0}, lv[2] = {0, 0};
-    for (const OpState& o : h->ops) {
-      const rtpe_op_desc& d = o.d;
-      if (!(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))) continue;
-      const int k = (d.flags & RTPE_F_OUT_REFINED) ? 1 : 0;
-      y[k] = reinterpret_cast<float*>(k ? refined : preds);
-      C[k] = d.kind == RTPE_OP_SIGMOID_ADD ? 1 : d.cout;
-      lv[k] = h->tensors[d.in_t].ds_log2 + (d.kind == RTPE_OP_CONV && d.stride == 2 ? 1 : 0);
-    }
-    for (int k = 0; k < 2; ++k) if (y[k] == nullptr) C[k] = 0;
-    const int rc = mask_outputs_launch(y[0], C[0], extent(H, lv[0]), extent(W, lv[0]), f.level(lv[0]), y[1], C[1], extent(H, lv[1]),
-                                       extent(W, lv[1]), f.level(lv[1]), N, s_main);
-    if (rc != RTPE_OK) return rc;
-  }
-  if (host_prof) {
-    static double sum_total = 0.0, sum_launch = 0.0;
-    static int n_calls = 0;
-    sum_total += std::chrono::duration<double, std::micro>(hclock::now() - hp0).count();
-    sum_launch += hp_launch;
-    if (++n_calls % host_prof == 0) {
-      fprintf(stderr, "rtpe host profile (N=%d, %zu ops, lanes %d): %.0f us per forward on the host, %.0f us of it inside the kernel "
-              "launch helpers (mean of %d calls)\n", N, h->ops.size(), (int)lanes_on, sum_total / n_calls, sum_launch / n_calls, n_calls);
-    }
-  }
-#undef RTPE_HP_LAUNCH
-  if (timed) {
-    RTPE_HIP_CHECK(hipEventSynchronize(ev.back()));
-    const int rc2 = read_op_times(routes, ev, op_ms);
-    for (auto& e : ev) hipEventDestroy(e);
-    if (rc2 != RTPE_OK) return rc2;
+    RTPE_REQUIRE(d.kind != RTPE_OP_AUX_PACK || c.aux != nullptr, "forward: this program has a second input (use rtpe_hrnet_forward_aux)");
+    const bool emits = (d.kind == RTPE_OP_SIGMOID_ADD || d.kind == RTPE_OP_GATE_MUL) && (d.flags & RTPE_F_OUT_PREDS);
+    RTPE_REQUIRE(!emits || (c.preds != nullptr && c.out_dtype == RTPE_DTYPE_F32), "forward: the sigmoid map output must be a float32 buffer");
   }
   return RTPE_OK;
+}
+
+// ---- the launch of one op: launch_op()'s switch and the helpers that build its argument blocks -----------------------------
+static const _Float16* op_weights(const rtpe_hrnet* h, const OpState& o) { return reinterpret_cast<const _Float16*>(h->arena + o.w_dev_off[0]); }
+static const float* op_affine(const rtpe_hrnet* h, const OpState& o) { return reinterpret_cast<const float*>(h->arena + o.ab_dev_off); }
+
+static StemArgs stem_args(const Fwd& f, const FwdCall& c, size_t i) {
+  const OpState& o = f.h->ops[i];
+  const rtpe_op_desc& d = o.d;
+  StemArgs a;
+  a.x = c.x; a.x_f32 = c.x_dtype == RTPE_DTYPE_F32;
+  a.w = op_weights(f.h, o);
+  a.alpha = op_affine(f.h, o);
+  a.beta = a.alpha + 64;
+  a.y = f.tptr(d.out_t, d.out_coff);
+  a.N = f.N; a.H = f.H; a.W = f.W; a.out_ld = f.h->tensors[d.out_t].channels;
+  a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
+  a.ext = f.ext ? f.level(0) : nullptr;
+  return a;
+}
+
+// conv1 + bn1 + relu + conv2 + bn2 + relu in one kernel: the half-resolution map stays in LDS (stem_fused.hip); or,
+// option "fused_stem" = 2 (`with_conv2` false), the stem op alone on that kernel's conv1 code (the chain on the matrix pipe),
+// output to memory - the bit-identity test of that chain against the VALU kernel
+static StemFusedArgs stem_fused_args(const Fwd& f, const FwdCall& c, size_t i, bool with_conv2) {
+  const rtpe_hrnet* h = f.h;
+  const OpState& o = h->ops[i];
+  const rtpe_op_desc& d = o.d;
+  StemFusedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = c.x; a.x_f32 = c.x_dtype == RTPE_DTYPE_F32;
+  a.w1 = op_weights(h, o);
+  a.alpha1 = op_affine(h, o);
+  a.beta1 = a.alpha1 + 64;
+  a.N = f.N; a.H = f.H; a.W = f.W;
+  if (with_conv2) {
+    const OpState& o2 = h->ops[i + 1];
+    const rtpe_op_desc& d2 = o2.d;
+    a.w2 = op_weights(h, o2);
+    a.alpha2 = op_affine(h, o2);
+    a.beta2 = a.alpha2 + o2.plan[0].cout_pad;
+    a.y = f.tptr(d2.out_t, d2.out_coff);
+    a.out_ld = h->tensors[d2.out_t].channels;
+    a.relu = (d2.flags & RTPE_F_RELU) ? 1 : 0;
+    a.round_conv = (d2.flags & RTPE_F_ROUND_CONV) ? 1 : 0;
+  } else {
+    a.y1 = f.tptr(d.out_t, d.out_coff);
+    a.out_ld = h->tensors[d.out_t].channels;
+  }
+  return a;
+}
+
+// a fused BasicBlock (conv_block.hip): this conv and the next one
+static int launch_block(const Fwd& f, size_t i, hipStream_t s) {
+  const rtpe_hrnet* h = f.h;
+  const OpState &o = h->ops[i], &o2 = h->ops[i + 1];
+  const rtpe_op_desc& d = o.d;
+  const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+  const int Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
+  return conv_block_launch(f.tptr(d.in_t, d.in_coff), ti.channels, ((size_t)f.N * Hi * Wi * ti.channels - (size_t)d.in_coff) * 2,
+                           f.tptr(o2.d.out_t, o2.d.out_coff), h->tensors[o2.d.out_t].channels, op_weights(h, o), op_affine(h, o),
+                           op_weights(h, o2), op_affine(h, o2), f.N, Hi, Wi, s);
+}
+
+static int launch_fuse(const Fwd& f, size_t i, hipStream_t s) {
+  const rtpe_hrnet* h = f.h;
+  const rtpe_op_desc& d = h->ops[i].d;
+  const rtpe_tensor_desc& to = h->tensors[d.out_t];
+  FuseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_terms = d.n_terms;
+  for (int t = 0; t < d.n_terms; ++t) {
+    const rtpe_tensor_desc& tt = h->tensors[d.term_t[t]];
+    a.term[t] = f.tptr(d.term_t[t], 0);
+    a.term_ld[t] = tt.channels;
+    a.term_up[t] = d.term_up[t];
+    a.term_h[t] = extent(f.H, tt.ds_log2);
+    a.term_w[t] = extent(f.W, tt.ds_log2);
+    if (f.ext) a.ext_term[t] = f.level(tt.ds_log2);
+  }
+  a.y = f.tptr(d.out_t, d.out_coff);
+  a.out_ld = to.channels; a.C = d.cout;
+  a.N = f.N; a.H = extent(f.H, to.ds_log2); a.W = extent(f.W, to.ds_log2);
+  a.nearest = f.rag ? 1 : 0;
+  if (f.ext) a.ext_out = f.level(to.ds_log2);
+  a.f32 = (d.flags & RTPE_F_F32) ? 1 : 0;
+  a.relu = (d.flags & RTPE_F_RELU) ? 1 : 0;
+  return fuse_launch(a, s);
+}
+
+// the students' ops that exist in fp32 only: cast (fp16 -> fp32), aux_pack, resize, gate_mul
+static int launch_f32_op(const Fwd& f, const FwdCall& c, size_t i, hipStream_t s) {
+  const rtpe_hrnet* h = f.h;
+  const rtpe_op_desc& d = h->ops[i].d;
+  const rtpe_tensor_desc& to = h->tensors[d.out_t];
+  const int N = f.N, Ho = extent(f.H, to.ds_log2), Wo = extent(f.W, to.ds_log2);
+  float* y = reinterpret_cast<float*>(f.tptr(d.out_t, d.out_coff));
+  if (d.kind == RTPE_OP_AUX_PACK) return aux_pack_launch(reinterpret_cast<const float*>(c.aux), y, to.channels, N, Ho, Wo, s);
+  const rtpe_tensor_desc& ti = h->tensors[d.in_t];
+  const int Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
+  const size_t pixels = (size_t)N * Hi * Wi;
+  if (d.kind == RTPE_OP_CAST) return cast_launch(f.tptr(d.in_t, d.in_coff), ti.channels, y, to.channels, d.cout, pixels, s);
+  const float* x = reinterpret_cast<const float*>(f.tptr(d.in_t, d.in_coff));
+  if (d.kind == RTPE_OP_RESIZE) return resize_nhwc_launch(x, ti.channels, Hi, Wi, y, to.channels, Ho, Wo, d.cout, N, s);
+  float div;                                     // gate_mul
+  memcpy(&div, &d.reserved[0], sizeof(float));
+  return gate_mul_launch(x, ti.channels, reinterpret_cast<const float*>(f.tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels, y,
+                         to.channels, d.cout, pixels, div, (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(c.preds) : nullptr, s);
+}
+
+// avgpool, se, cam_combine and sigmoid_add on tensors of T: float, or _Float16 for the half body of AttentionStudent (whose
+// conditions check_ops holds); the launch functions are overloaded on the pointer type
+template <typename T>
+static int launch_student_op(const Fwd& f, const FwdCall& c, size_t i, hipStream_t s) {
+  const rtpe_hrnet* h = f.h;
+  const OpState& o = h->ops[i];
+  const rtpe_op_desc& d = o.d;
+  const rtpe_tensor_desc &ti = h->tensors[d.in_t], &to = h->tensors[d.out_t];
+  const int N = f.N, Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
+  auto at = [&](int t, int coff) { return reinterpret_cast<T*>(f.tptr(t, coff)); };
+  const T* x = at(d.in_t, d.in_coff);
+  T* y = at(d.out_t, d.out_coff);
+  const int* ext_in = f.ext ? f.level(ti.ds_log2) : nullptr;            // avgpool, se: image n's own part of the map
+  switch (d.kind) {
+    case RTPE_OP_AVGPOOL:
+      return avgpool_launch(x, ti.channels, y, to.channels, d.cout, N, Hi, Wi, s, ext_in);
+    case RTPE_OP_SE:
+      return se_launch(x, ti.channels, d.cin, d.cout, N, Hi * Wi, reinterpret_cast<const float*>(h->arena + o.w_dev_off[0]), y,
+                       to.channels, s, ext_in, Wi);
+    case RTPE_OP_CAM_COMBINE:
+      return cam_combine_launch(x, ti.channels, at(d.res_t, d.res_coff), h->tensors[d.res_t].channels, at(d.term_t[0], 0),
+                                h->tensors[d.term_t[0]].channels, y, to.channels, d.cout, N, (size_t)Hi * Wi, s);
+    default:   // RTPE_OP_SIGMOID_ADD
+      return sigmoid_add_launch(x, ti.channels, at(d.res_t, d.res_coff), h->tensors[d.res_t].channels, y, to.channels, d.cout,
+                                (size_t)N * Hi * Wi, (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(c.preds) : nullptr, s);
+  }
+}
+
+// What the route of op i says, on stream s: one case per route kind, then the ops that have no conv by their kind
+static int launch_op(const Fwd& f, const FwdCall& c, const std::vector<Route>& routes, const std::vector<ConvArgs>& args, size_t i,
+                     hipStream_t s) {
+  const rtpe_hrnet* h = f.h;
+  const OpState& o = h->ops[i];
+  const Route& r = routes[i];
+  switch (r.how) {
+    case kRouteDoneBy: case kRoutePairHead: case kRoutePairProj:      // computed by the launch at op r.by
+      return RTPE_OK;
+    case kRouteStemFused: case kRouteStemConv1:
+      return stem_fused_launch(stem_fused_args(f, c, i, r.how == kRouteStemFused), s);
+    case kRouteStemPlain:
+      return stem_launch(stem_args(f, c, i), s);
+    case kRouteBlock:
+      return launch_block(f, i, s);
+    case kRouteS2Group: {
+      const ConvPlan* plans[3];
+      for (int m = 0; m < r.by; ++m) plans[m] = &h->ops[i + m].plan[0];
+      return conv48s2_launch_group(plans, &args[i], r.by, s);
+    }
+    case kRoutePairTail: {   // with the head and, where it is folded, the head's skip projection
+      const OpState& oh = h->ops[r.by];
+      const bool proj = oh.proj_op >= 0 && routes[oh.proj_op].how == kRoutePairProj;
+      return conv_pair_launch(oh.plan[0], args[r.by], o.plan[0], args[i], s, proj ? &h->ops[oh.proj_op].plan[0] : nullptr,
+                              proj ? &args[oh.proj_op] : nullptr);
+    }
+    case kRouteDeconvMerged: case kRouteDeconv48:
+      return launch_conv(r.how, o.plan[0], r.tile[0], args[i], s);
+    case kRouteTile: case kRouteStream: case kRouteDirect: case kRouteConv64: case kRouteHead: case kRouteS2: {
+      // a conv on the kernel of its launch shape (a launch per class) or on the head / stride-2 kernel
+      int rc = launch_conv(r.how, o.plan[0], r.tile[0], args[i], s);
+      for (int k = 1; k < o.n_geom && rc == RTPE_OK; ++k)
+        rc = launch_conv(r.how, o.plan[k], r.tile[k], conv_op_args(f, i, k, r.tile[k]), s);
+      return rc;
+    }
+    default:                                                          // kRouteNone: the elementwise and student ops
+      break;
+  }
+  switch (o.d.kind) {
+    case RTPE_OP_CAST: case RTPE_OP_AUX_PACK: case RTPE_OP_RESIZE: case RTPE_OP_GATE_MUL:
+      return launch_f32_op(f, c, i, s);
+    case RTPE_OP_AVGPOOL: case RTPE_OP_SE: case RTPE_OP_CAM_COMBINE: case RTPE_OP_SIGMOID_ADD:
+      return (o.d.flags & RTPE_F_F32) ? launch_student_op<float>(f, c, i, s) : launch_student_op<_Float16>(f, c, i, s);
+    default:
+      return launch_fuse(f, i, s);
+  }
+}
+
+// ---- parallel regions ---------------------------------------------------------------------------------------------------
+// The branches of a HighResolutionModule (pose_higher_hrnet.py:242-243) and the conversion convs of its fuse layers are
+// independent: with lanes on, the ops of lane k > 0 go to an internal stream that forks from the caller's stream at the
+// region's first op and joins it behind its last; an op waits for the events of the ops of other lanes whose output it reads.
+// Timed / recorded runs stay on one stream (one op after another).  The lock is rtpe_hrnet::lane_mu's: taken here, given back
+// when the forward returns, behind the join of its last region.
+class Lanes {
+ public:
+  Lanes(rtpe_hrnet* h, const FwdCall& c, const std::vector<Route>& routes) : h_(h), routes_(routes), main_(c.stream) {
+    if (h->has_regions && c.op_ms == nullptr && c.rec == nullptr && !(c.flags & RTPE_FWD_NO_LANES)) {
+      const int opt = get_option(kOptLanes);
+      on_ = opt == 1 || (opt == 2 && (long long)c.N * c.H * c.W <= 4ll * 640 * 640);
+    }
+    if (on_) lock_ = std::unique_lock<std::mutex>(h->lane_mu);
+  }
+  bool on() const { return on_; }
+
+  // the stream of op i, behind everything the op reads: the join of the region before it, the fork of its own, the events of
+  // the other lanes' ops that it waits for
+  int stream_for(size_t i, hipStream_t* s) {
+    *s = main_;
+    if (!on_) return RTPE_OK;
+    if (h_->fork_event == nullptr) {               // the first forward with lanes on makes the handle's streams and events
+      const int rc = create();
+      if (rc != RTPE_OK) return rc;
+    }
+    const rtpe_op_desc& d = h_->ops[i].d;
+    if (d.region != region_) {
+      const int rc = join();
+      if (rc != RTPE_OK) return rc;
+      region_ = d.region;
+      if (region_ > 0) {                           // fork: every lane starts behind what the caller's stream holds
+        RTPE_HIP_CHECK(hipEventRecord(h_->fork_event, main_));
+        for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamWaitEvent(h_->lane_stream[l], h_->fork_event, 0));
+      }
+    }
+    if (region_ == 0) return RTPE_OK;
+    if (d.lane > 0) { *s = h_->lane_stream[d.lane]; used_[d.lane] = true; }
+    // the op's own waits and those of the ops behind it that this launch computes (a block's second conv, the stem's
+    // conv2, the other convs of a stride-2 group)
+    for (size_t j = i; j == i || (j < routes_.size() && routes_[j].how == kRouteDoneBy && routes_[j].by == (int)i); ++j)
+      for (int w : h_->wait_ops[j]) RTPE_HIP_CHECK(hipStreamWaitEvent(*s, h_->op_event[w], 0));
+    return RTPE_OK;
+  }
+
+  // behind the launch of op i on s: the events that other lanes wait for
+  int after(size_t i, hipStream_t s) {
+    if (!on_ || region_ == 0) return RTPE_OK;
+    const Route& r = routes_[i];
+    // (a 1x1 pair is ONE kernel, launched at the tail's place: the head's output exists behind that launch)
+    if (h_->needs_event[i] && r.how != kRoutePairHead) RTPE_HIP_CHECK(hipEventRecord(h_->op_event[i], s));
+    if (r.how == kRoutePairTail && h_->needs_event[r.by]) RTPE_HIP_CHECK(hipEventRecord(h_->op_event[r.by], s));
+    return RTPE_OK;
+  }
+
+  // the caller's stream waits for every lane the open region used
+  int join() {
+    if (!on_ || region_ == 0) return RTPE_OK;
+    for (int l = 1; l < 4; ++l) {
+      if (!used_[l]) continue;
+      hipEvent_t e = h_->op_event[h_->ops.size() + l];
+      RTPE_HIP_CHECK(hipEventRecord(e, h_->lane_stream[l]));
+      RTPE_HIP_CHECK(hipStreamWaitEvent(main_, e, 0));
+      used_[l] = false;
+    }
+    return RTPE_OK;
+  }
+
+ private:
+  int create() {
+    const size_t n = h_->ops.size();
+    for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamCreateWithFlags(&h_->lane_stream[l], hipStreamNonBlocking));
+    h_->op_event.assign(n + 4, nullptr);
+    for (size_t i = 0; i < n; ++i)
+      if (h_->needs_event[i]) RTPE_HIP_CHECK(hipEventCreateWithFlags(&h_->op_event[i], hipEventDisableTiming));
+    for (size_t l = 0; l < 4; ++l) RTPE_HIP_CHECK(hipEventCreateWithFlags(&h_->op_event[n + l], hipEventDisableTiming));
+    RTPE_HIP_CHECK(hipEventCreateWithFlags(&h_->fork_event, hipEventDisableTiming));
+    return RTPE_OK;
+  }
+
+  rtpe_hrnet* h_;
+  const std::vector<Route>& routes_;
+  hipStream_t main_;
+  bool on_ = false;
+  std::unique_lock<std::mutex> lock_;
+  int region_ = 0;
+  bool used_[4] = {false, false, false, false};
+};
+
+// The per-op events of a timed forward (its own: destroyed when the forward returns, however it returns) and of a recorded one
+// (the handle's: rtpe_hrnet_read_record reads them later)
+class OpEvents {
+ public:
+  explicit OpEvents(const std::vector<Route>& routes) : routes_(routes) {}
+  ~OpEvents() { for (hipEvent_t e : own_) if (e) hipEventDestroy(e); }
+
+  int begin(const FwdCall& c) {
+    const size_t n = routes_.size() + 1;
+    if (c.op_ms != nullptr) {
+      own_.assign(n, nullptr);
+      for (auto& e : own_) RTPE_HIP_CHECK(hipEventCreate(&e));
+      sets_[n_sets_++] = &own_;
+      RTPE_HIP_CHECK(hipEventRecord(own_[0], c.stream));
+    }
+    if (c.rec != nullptr) {                      // non-blocking recording into caller-kept events
+      if (c.rec->ev.size() != n) {
+        for (auto& e : c.rec->ev) hipEventDestroy(e);
+        c.rec->ev.resize(n);
+        for (auto& e : c.rec->ev) RTPE_HIP_CHECK(hipEventCreate(&e));
+      }
+      c.rec->routes = routes_;
+      sets_[n_sets_++] = &c.rec->ev;
+      RTPE_HIP_CHECK(hipEventRecord(c.rec->ev[0], c.stream));
+    }
+    return RTPE_OK;
+  }
+
+  // the event behind op i, where the op has one (op_has_event)
+  int record(size_t i, hipStream_t s) {
+    if (n_sets_ == 0 || !op_has_event(routes_, i)) return RTPE_OK;
+    for (int k = 0; k < n_sets_; ++k) RTPE_HIP_CHECK(hipEventRecord((*sets_[k])[i + 1], s));
+    return RTPE_OK;
+  }
+
+  // a timed forward: wait for the last event and read the times
+  int read(float* op_ms) {
+    if (own_.empty()) return RTPE_OK;
+    RTPE_HIP_CHECK(hipEventSynchronize(own_.back()));
+    return read_op_times(routes_, own_, op_ms);
+  }
+
+ private:
+  const std::vector<Route>& routes_;
+  std::vector<hipEvent_t> own_;
+  std::vector<hipEvent_t>* sets_[2] = {nullptr, nullptr};
+  int n_sets_ = 0;
+};
+
+// a mixed-size batch: whatever the forward left outside an image's own region of the two outputs becomes 0.0
+static int mask_mixed_outputs(const Fwd& f, const FwdCall& c) {
+  const rtpe_hrnet* h = f.h;
+  float* y[2] = {nullptr, nullptr};
+  int C[2] = {0, 0}, lv[2] = {0, 0};
+  for (const OpState& o : h->ops) {
+    const rtpe_op_desc& d = o.d;
+    if (!(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))) continue;
+    const int k = (d.flags & RTPE_F_OUT_REFINED) ? 1 : 0;
+    y[k] = reinterpret_cast<float*>(k ? c.refined : c.preds);
+    C[k] = d.kind == RTPE_OP_SIGMOID_ADD ? 1 : d.cout;
+    lv[k] = h->tensors[d.in_t].ds_log2 + (d.kind == RTPE_OP_CONV && d.stride == 2 ? 1 : 0);
+  }
+  for (int k = 0; k < 2; ++k) if (y[k] == nullptr) C[k] = 0;
+  return mask_outputs_launch(y[0], C[0], extent(f.H, lv[0]), extent(f.W, lv[0]), f.level(lv[0]), y[1], C[1], extent(f.H, lv[1]),
+                             extent(f.W, lv[1]), f.level(lv[1]), f.N, c.stream);
+}
+
+// RTPE_HOST_PROF=n: the host time of a forward and where it goes, to stderr every n forwards.  The second number is the time
+// inside launch_op() and mask_mixed_outputs(): every launch helper with the building of its arguments, for every kind of op
+struct HostProf {
+  typedef std::chrono::steady_clock clock;
+  static int every() { static const int n = env_int("RTPE_HOST_PROF", 0); return n; }
+  const int on = every();
+  const clock::time_point t0 = clock::now();
+  double launch_us = 0.0;
+
+  template <typename F>
+  int launch(F&& fn) {
+    if (!on) return fn();
+    const clock::time_point t = clock::now();
+    const int rc = fn();
+    launch_us += std::chrono::duration<double, std::micro>(clock::now() - t).count();
+    return rc;
+  }
+
+  void report(int N, size_t n_ops, bool lanes) const {
+    if (!on) return;
+    static double sum_total = 0.0, sum_launch = 0.0;
+    static int n_calls = 0;
+    sum_total += std::chrono::duration<double, std::micro>(clock::now() - t0).count();
+    sum_launch += launch_us;
+    if (++n_calls % on == 0) {
+      fprintf(stderr, "rtpe host profile (N=%d, %zu ops, lanes %d): %.0f us per forward on the host, %.0f us of it inside the kernel "
+              "launch helpers (mean of %d calls)\n", N, n_ops, (int)lanes, sum_total / n_calls, sum_launch / n_calls, n_calls);
+    }
+  }
+};
+
+}  // namespace
+
+static int run(rtpe_hrnet* h, const FwdCall& c) {
+  RTPE_REQUIRE(h && c.x && c.ws, "forward: null argument");
+  HostProf prof;
+  // kernels, events and function attributes act on HIP's CURRENT device: make the handle's device current for
+  // the call (the stream and every buffer must belong to it) and give the caller's device back afterwards
+  DeviceGuard guard(h->device);
+  RTPE_HIP_CHECK(guard.err);
+  int rc = check_shape(h, c.N, c.H, c.W, "forward", c.ext != nullptr);
+  if (rc != RTPE_OK) return rc;
+  RTPE_REQUIRE(c.x_dtype == RTPE_DTYPE_F16 || c.x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
+  RTPE_REQUIRE(c.out_dtype == RTPE_DTYPE_F16 || c.out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
+  const Fwd f(h, c.N, c.H, c.W, c.ws, c.preds, c.refined, c.out_dtype, c.ext);
+  if (f.ws_need > c.ws_bytes) { set_error("forward: workspace %zu < %zu", c.ws_bytes, f.ws_need); return RTPE_E_NOMEM; }
+  RTPE_REQUIRE(((uintptr_t)c.ws & 255) == 0, "forward: workspace must be 256-byte aligned");
+  if ((rc = check_ops(f, c)) != RTPE_OK) return rc;
+  std::vector<Route> routes;
+  std::vector<ConvArgs> args;
+  if ((rc = route_ops(f, &routes, &args)) != RTPE_OK) return rc;
+  OpEvents events(routes);                       // nothing is enqueued above this line
+  if ((rc = events.begin(c)) != RTPE_OK) return rc;
+  Lanes lanes(h, c, routes);
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    hipStream_t s;
+    if ((rc = lanes.stream_for(i, &s)) != RTPE_OK) return rc;
+    if ((rc = prof.launch([&] { return launch_op(f, c, routes, args, i, s); })) != RTPE_OK) return rc;
+    if ((rc = lanes.after(i, s)) != RTPE_OK) return rc;
+    if ((rc = events.record(i, s)) != RTPE_OK) return rc;
+  }
+  if ((rc = lanes.join()) != RTPE_OK) return rc;
+  if (c.ext != nullptr && (rc = prof.launch([&] { return mask_mixed_outputs(f, c); })) != RTPE_OK) return rc;
+  prof.report(c.N, h->ops.size(), lanes.on());
+  return events.read(c.op_ms);
 }
 
 extern "C" int rtpe_hrnet_forward(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
                                   int32_t W, void* preds, void* refined, int32_t out_dtype, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+  return run(h, fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream));
 }
 
 extern "C" int rtpe_hrnet_forward_flags(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
                                         int32_t W, void* preds, void* refined, int32_t out_dtype, void* workspace,
                                         size_t workspace_bytes, void* stream, uint32_t flags) {
   RTPE_REQUIRE((flags & ~(uint32_t)RTPE_FWD_NO_LANES) == 0, "forward_flags: unknown flag bits 0x%x", flags);
-  return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, nullptr, nullptr, flags);
+  FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  c.flags = flags;
+  return run(h, c);
 }
 
 extern "C" int rtpe_hrnet_forward_aux(rtpe_hrnet* h, const void* x, int32_t x_dtype, const void* aux_nchw_f32, int32_t N,
                                       int32_t H, int32_t W, void* preds, void* refined, int32_t out_dtype,
                                       void* workspace, size_t workspace_bytes, void* stream) {
   RTPE_REQUIRE(aux_nchw_f32 != nullptr, "forward_aux: the second input is null");
-  return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, nullptr, aux_nchw_f32);
+  FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  c.aux = aux_nchw_f32;
+  return run(h, c);
 }
 
 extern "C" int rtpe_hrnet_forward_timed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
@@ -1305,8 +1473,10 @@ extern "C" int rtpe_hrnet_forward_timed(rtpe_hrnet* h, const void* x, int32_t x_
                                         void* workspace, size_t workspace_bytes, void* stream, float* op_ms,
                                         int32_t n_ops) {
   RTPE_REQUIRE(op_ms != nullptr, "forward_timed: op_ms is null");
-  return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), op_ms, n_ops);
+  FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  c.op_ms = op_ms;
+  c.n_ms = n_ops;
+  return run(h, c);
 }
 
 extern "C" int rtpe_hrnet_op_cost(const rtpe_hrnet* h, int32_t op, int32_t N, int32_t H, int32_t W,
@@ -1433,7 +1603,10 @@ extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_
     // in stream order, from the caller's pinned block: nothing blocks, nothing is allocated
     RTPE_HIP_CHECK(hipMemcpyAsync(table_dev, table_pinned, (size_t)RTPE_MIXED_LEVELS * 2 * N * sizeof(int32_t), hipMemcpyHostToDevice, s));
   }
-  return run(h, x, x_dtype, N, Hc, Wc, preds, refined, out_dtype, workspace, ws_need, s, nullptr, 0, nullptr, nullptr, flags, table_dev);
+  FwdCall c = fwd_call(x, x_dtype, N, Hc, Wc, preds, refined, out_dtype, workspace, ws_need, stream);
+  c.flags = flags;
+  c.ext = table_dev;
+  return run(h, c);
 }
 
 // ---- single-layer entry (layer-level parity tests) -------------------------
@@ -1721,13 +1894,15 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
   RTPE_REQUIRE(h != nullptr, "autotune: null handle");
   // a stream of native-size images has hundreds of shapes: ragged ones run on the default launch shapes and are never tuned
   RTPE_REQUIRE(!ragged(H, W), "autotune: N=%d H=%d W=%d: shapes with a side that is no multiple of 32 are not tuned", N, H, W);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const auto shape = std::make_tuple(N, H, W);
   h->tuned.erase(shape);
   const size_t n_ops = h->ops.size();
   std::vector<float> ms(n_ops);
-  int rc = run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, s, ms.data(), (int)n_ops,
-               nullptr, aux);
+  FwdCall timed = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  timed.aux = aux;
+  timed.op_ms = ms.data();
+  timed.n_ms = (int)n_ops;
+  int rc = run(h, timed);
   if (rc != RTPE_OK) return rc;
   std::vector<Route> routes;                           // (of these forwards: no launch shape decides what is absorbed)
   std::vector<ConvArgs> args;
@@ -1772,8 +1947,7 @@ static int autotune_impl(rtpe_hrnet* h, const void* x, int32_t x_dtype, const vo
     h->tuned[shape] = trial;
     std::vector<float> best_ms(n_ops, 1e30f);
     for (int rep = 0; rep < 6; ++rep) {           // first repetition also warms caches for this choice
-      rc = run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, s, ms.data(), (int)n_ops,
-               nullptr, aux);
+      rc = run(h, timed);
       if (rc != RTPE_OK) { h->tuned.erase(shape); return rc; }
       if (rep == 0) continue;
       for (size_t i = 0; i < n_ops; ++i) best_ms[i] = ms[i] < best_ms[i] ? ms[i] : best_ms[i];
@@ -1825,8 +1999,9 @@ extern "C" int rtpe_hrnet_forward_record(rtpe_hrnet* h, const void* x, int32_t x
                                          int32_t W, void* preds, void* refined, int32_t out_dtype,
                                          void* workspace, size_t workspace_bytes, void* stream, int32_t slot) {
   RTPE_REQUIRE(h != nullptr && slot >= 0 && slot < 64, "forward_record: bad slot");
-  return run(h, x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes,
-             reinterpret_cast<hipStream_t>(stream), nullptr, 0, &h->records[slot]);
+  FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  c.rec = &h->records[slot];
+  return run(h, c);
 }
 
 extern "C" int rtpe_hrnet_read_record(rtpe_hrnet* h, int32_t slot, float* op_ms, int32_t n_ops) {
