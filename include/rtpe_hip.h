@@ -213,6 +213,8 @@ int rtpe_hrnet_forward(rtpe_hrnet* h, const void* x, int32_t x_dtype,
  * "lanes" says (callers that overlap whole forwards on streams of their own,
  * rtpe/engine.py TeacherPipeline.stream; graph capture). */
 #define RTPE_FWD_NO_LANES 1u
+#define RTPE_FWD_TRACE 2u /* keep what this forward enqueues, in host order, for rtpe_hrnet_read_trace (rtpe_hip_trace.h);
+                             launches and outputs are those of the forward without the flag */
 int rtpe_hrnet_forward_flags(rtpe_hrnet* h, const void* x, int32_t x_dtype,
                              int32_t N, int32_t H, int32_t W,
                              void* preds, void* refined, int32_t out_dtype,
@@ -714,5 +716,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_anysize.h"
 #include "rtpe_hip_mixed.h"
 #include "rtpe_hip_mixdec.h"
+#include "rtpe_hip_trace.h"
 
 #endif /* RTPE_HIP_H */

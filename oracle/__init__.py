@@ -24,6 +24,10 @@ What is in here
   that prove the ties are there; with ``decode_ref``'s stable top-k the
   yardstick for the order among equal values, which the reference's
   ``torch.topk`` leaves undefined.
+* ``schedule`` - happens-before checker for the trace of one executor forward
+  (include/rtpe_hip_trace.h): what every launch reads and writes, from the
+  descs and the route kinds; every conflicting pair must be ordered and no
+  workspace slot handed on before its tensor's last read.  Plain Python.
 
 Parity pin
 ----------

@@ -65,6 +65,17 @@ enum {
   kRouteStemFused, kRouteStemConv1, kRouteStemPlain,     // stem_fused.hip with the next op / its conv1 code alone ("fused_stem" = 2) / the VALU kernel
   kRouteDoneBy                                           // computed by the launch at op `by` (a block's second conv, the stem's conv2, a group's others)
 };
+// the numbers a trace reports (rtpe_hip_trace.h): a kind added in the middle of the list must not renumber them silently
+static_assert(kRouteTile == RTPE_ROUTE_TILE && kRouteHead == RTPE_ROUTE_HEAD && kRouteS2 == RTPE_ROUTE_S2 && kRouteS2Group == RTPE_ROUTE_S2_GROUP &&
+              kRouteDeconvMerged == RTPE_ROUTE_DECONV_MERGED && kRoutePairHead == RTPE_ROUTE_PAIR_HEAD && kRoutePairTail == RTPE_ROUTE_PAIR_TAIL &&
+              kRoutePairProj == RTPE_ROUTE_PAIR_PROJ && kRouteBlock == RTPE_ROUTE_BLOCK && kRouteStemFused == RTPE_ROUTE_STEM_FUSED &&
+              kRouteStemConv1 == RTPE_ROUTE_STEM_CONV1 && kRouteStemPlain == RTPE_ROUTE_STEM_PLAIN && kRouteDoneBy == RTPE_ROUTE_DONE_BY,
+              "rtpe_hip_trace.h names other route numbers");
+
+static void trace_put(std::vector<int32_t>* tr, int kind, int a, int b, int c = 0, int d = 0) {
+  const int32_t r[RTPE_TRACE_INTS] = {kind, a, b, c, d};
+  tr->insert(tr->end(), r, r + RTPE_TRACE_INTS);
+}
 
 struct Route {
   int how, by;
@@ -104,6 +115,7 @@ struct rtpe_hrnet {
   std::vector<std::vector<int>> wait_ops;
   hipEvent_t fork_event = nullptr;
   bool has_regions = false;
+  std::vector<int32_t> trace;     // what the last forward with RTPE_FWD_TRACE enqueued (rtpe_hip_trace.h), 5 integers per record
   bool any_size = false;     // rtpe_hrnet_set_any_size: ragged shapes (a side that is no multiple of 32) are taken, on the general paths
 };
 
@@ -1229,7 +1241,8 @@ static int launch_op(const Fwd& f, const FwdCall& c, const std::vector<Route>& r
 // when the forward returns, behind the join of its last region.
 class Lanes {
  public:
-  Lanes(rtpe_hrnet* h, const FwdCall& c, const std::vector<Route>& routes) : h_(h), routes_(routes), main_(c.stream) {
+  Lanes(rtpe_hrnet* h, const FwdCall& c, const std::vector<Route>& routes, std::vector<int32_t>* trace)
+      : h_(h), routes_(routes), main_(c.stream), tr_(trace) {
     if (h->has_regions && c.op_ms == nullptr && c.rec == nullptr && !(c.flags & RTPE_FWD_NO_LANES)) {
       const int opt = get_option(kOptLanes);
       on_ = opt == 1 || (opt == 2 && (long long)c.N * c.H * c.W <= 4ll * 640 * 640);
@@ -1237,6 +1250,11 @@ class Lanes {
     if (on_) lock_ = std::unique_lock<std::mutex>(h->lane_mu);
   }
   bool on() const { return on_; }
+  // the number a trace gives stream s: 0 the caller's, 1..3 the lanes'
+  int stream_id(hipStream_t s) const {
+    for (int l = 1; l < 4; ++l) if (on_ && s == h_->lane_stream[l] && s != main_) return l;
+    return 0;
+  }
 
   // the stream of op i, behind everything the op reads: the join of the region before it, the fork of its own, the events of
   // the other lanes' ops that it waits for
@@ -1253,8 +1271,10 @@ class Lanes {
       if (rc != RTPE_OK) return rc;
       region_ = d.region;
       if (region_ > 0) {                           // fork: every lane starts behind what the caller's stream holds
-        RTPE_HIP_CHECK(hipEventRecord(h_->fork_event, main_));
-        for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamWaitEvent(h_->lane_stream[l], h_->fork_event, 0));
+        const int fork = (int)h_->ops.size() + RTPE_TRACE_FORK_EVENT;
+        int rc2 = record(fork, main_);
+        for (int l = 1; l < 4 && rc2 == RTPE_OK; ++l) rc2 = wait(h_->lane_stream[l], fork);
+        if (rc2 != RTPE_OK) return rc2;
       }
     }
     if (region_ == 0) return RTPE_OK;
@@ -1262,7 +1282,10 @@ class Lanes {
     // the op's own waits and those of the ops behind it that this launch computes (a block's second conv, the stem's
     // conv2, the other convs of a stride-2 group)
     for (size_t j = i; j == i || (j < routes_.size() && routes_[j].how == kRouteDoneBy && routes_[j].by == (int)i); ++j)
-      for (int w : h_->wait_ops[j]) RTPE_HIP_CHECK(hipStreamWaitEvent(*s, h_->op_event[w], 0));
+      for (int w : h_->wait_ops[j]) {
+        const int rc = wait(*s, w);
+        if (rc != RTPE_OK) return rc;
+      }
     return RTPE_OK;
   }
 
@@ -1271,9 +1294,10 @@ class Lanes {
     if (!on_ || region_ == 0) return RTPE_OK;
     const Route& r = routes_[i];
     // (a 1x1 pair is ONE kernel, launched at the tail's place: the head's output exists behind that launch)
-    if (h_->needs_event[i] && r.how != kRoutePairHead) RTPE_HIP_CHECK(hipEventRecord(h_->op_event[i], s));
-    if (r.how == kRoutePairTail && h_->needs_event[r.by]) RTPE_HIP_CHECK(hipEventRecord(h_->op_event[r.by], s));
-    return RTPE_OK;
+    int rc = RTPE_OK;
+    if (h_->needs_event[i] && r.how != kRoutePairHead) rc = record((int)i, s);
+    if (rc == RTPE_OK && r.how == kRoutePairTail && h_->needs_event[r.by]) rc = record(r.by, s);
+    return rc;
   }
 
   // the caller's stream waits for every lane the open region used
@@ -1281,15 +1305,30 @@ class Lanes {
     if (!on_ || region_ == 0) return RTPE_OK;
     for (int l = 1; l < 4; ++l) {
       if (!used_[l]) continue;
-      hipEvent_t e = h_->op_event[h_->ops.size() + l];
-      RTPE_HIP_CHECK(hipEventRecord(e, h_->lane_stream[l]));
-      RTPE_HIP_CHECK(hipStreamWaitEvent(main_, e, 0));
+      const int e = (int)h_->ops.size() + l;
+      int rc = record(e, h_->lane_stream[l]);
+      if (rc == RTPE_OK) rc = wait(main_, e);
+      if (rc != RTPE_OK) return rc;
       used_[l] = false;
     }
     return RTPE_OK;
   }
 
  private:
+  // Every event call of a forward goes through these two: the HIP call and, in a traced forward, its record.  Event ids
+  // (rtpe_hip_trace.h): op i's event, n_ops + l for lane l's join, n_ops + RTPE_TRACE_FORK_EVENT for the fork
+  hipEvent_t event(int id) const { return id == (int)h_->ops.size() + RTPE_TRACE_FORK_EVENT ? h_->fork_event : h_->op_event[id]; }
+  int record(int id, hipStream_t s) {
+    RTPE_HIP_CHECK(hipEventRecord(event(id), s));
+    if (tr_) trace_put(tr_, RTPE_TRACE_RECORD, stream_id(s), id);
+    return RTPE_OK;
+  }
+  int wait(hipStream_t s, int id) {
+    RTPE_HIP_CHECK(hipStreamWaitEvent(s, event(id), 0));
+    if (tr_) trace_put(tr_, RTPE_TRACE_WAIT, stream_id(s), id);
+    return RTPE_OK;
+  }
+
   int create() {
     const size_t n = h_->ops.size();
     for (int l = 1; l < 4; ++l) RTPE_HIP_CHECK(hipStreamCreateWithFlags(&h_->lane_stream[l], hipStreamNonBlocking));
@@ -1304,6 +1343,7 @@ class Lanes {
   rtpe_hrnet* h_;
   const std::vector<Route>& routes_;
   hipStream_t main_;
+  std::vector<int32_t>* tr_;
   bool on_ = false;
   std::unique_lock<std::mutex> lock_;
   int region_ = 0;
@@ -1430,15 +1470,19 @@ static int run(rtpe_hrnet* h, const FwdCall& c) {
   if ((rc = route_ops(f, &routes, &args)) != RTPE_OK) return rc;
   OpEvents events(routes);                       // nothing is enqueued above this line
   if ((rc = events.begin(c)) != RTPE_OK) return rc;
-  Lanes lanes(h, c, routes);
+  std::vector<int32_t>* const tr = (c.flags & RTPE_FWD_TRACE) ? &h->trace : nullptr;     // (an untraced forward tests this pointer, no more)
+  if (tr) tr->clear();
+  Lanes lanes(h, c, routes, tr);
   for (size_t i = 0; i < h->ops.size(); ++i) {
     hipStream_t s;
     if ((rc = lanes.stream_for(i, &s)) != RTPE_OK) return rc;
+    if (tr) trace_put(tr, RTPE_TRACE_LAUNCH, (int)i, lanes.stream_id(s), routes[i].how, routes[i].by);
     if ((rc = prof.launch([&] { return launch_op(f, c, routes, args, i, s); })) != RTPE_OK) return rc;
     if ((rc = lanes.after(i, s)) != RTPE_OK) return rc;
     if ((rc = events.record(i, s)) != RTPE_OK) return rc;
   }
   if ((rc = lanes.join()) != RTPE_OK) return rc;
+  if (c.ext != nullptr && tr) trace_put(tr, RTPE_TRACE_MASK, 0, 0);
   if (c.ext != nullptr && (rc = prof.launch([&] { return mask_mixed_outputs(f, c); })) != RTPE_OK) return rc;
   prof.report(c.N, h->ops.size(), lanes.on());
   return events.read(c.op_ms);
@@ -1453,7 +1497,7 @@ extern "C" int rtpe_hrnet_forward(rtpe_hrnet* h, const void* x, int32_t x_dtype,
 extern "C" int rtpe_hrnet_forward_flags(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
                                         int32_t W, void* preds, void* refined, int32_t out_dtype, void* workspace,
                                         size_t workspace_bytes, void* stream, uint32_t flags) {
-  RTPE_REQUIRE((flags & ~(uint32_t)RTPE_FWD_NO_LANES) == 0, "forward_flags: unknown flag bits 0x%x", flags);
+  RTPE_REQUIRE((flags & ~(uint32_t)(RTPE_FWD_NO_LANES | RTPE_FWD_TRACE)) == 0, "forward_flags: unknown flag bits 0x%x", flags);
   FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
   c.flags = flags;
   return run(h, c);
@@ -1466,6 +1510,27 @@ extern "C" int rtpe_hrnet_forward_aux(rtpe_hrnet* h, const void* x, int32_t x_dt
   FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
   c.aux = aux_nchw_f32;
   return run(h, c);
+}
+
+// ---- the trace of a forward (include/rtpe_hip_trace.h) ---------------------
+extern "C" int rtpe_hrnet_forward_aux_flags(rtpe_hrnet* h, const void* x, int32_t x_dtype, const void* aux_nchw_f32, int32_t N,
+                                            int32_t H, int32_t W, void* preds, void* refined, int32_t out_dtype,
+                                            void* workspace, size_t workspace_bytes, void* stream, uint32_t flags) {
+  RTPE_REQUIRE(aux_nchw_f32 != nullptr, "forward_aux_flags: the second input is null");
+  RTPE_REQUIRE((flags & ~(uint32_t)(RTPE_FWD_NO_LANES | RTPE_FWD_TRACE)) == 0, "forward_aux_flags: unknown flag bits 0x%x", flags);
+  FwdCall c = fwd_call(x, x_dtype, N, H, W, preds, refined, out_dtype, workspace, workspace_bytes, stream);
+  c.aux = aux_nchw_f32;
+  c.flags = flags;
+  return run(h, c);
+}
+
+extern "C" int rtpe_hrnet_read_trace(const rtpe_hrnet* h, int32_t* out, int32_t n_ints, int32_t* count) {
+  RTPE_REQUIRE(h != nullptr && count != nullptr, "read_trace: null argument");
+  *count = (int32_t)h->trace.size();
+  if (out == nullptr) return RTPE_OK;
+  RTPE_REQUIRE(n_ints >= *count, "read_trace: room for %d integers, the trace has %d", n_ints, *count);
+  if (*count) memcpy(out, h->trace.data(), h->trace.size() * sizeof(int32_t));
+  return RTPE_OK;
 }
 
 extern "C" int rtpe_hrnet_forward_timed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t H,
@@ -1579,7 +1644,7 @@ extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_
                                         void* refined, int32_t out_dtype, void* workspace, size_t workspace_bytes, void* stream,
                                         uint32_t flags) {
   RTPE_REQUIRE(h && x && workspace && sizes_hw && table_pinned, "forward_mixed: null argument");
-  RTPE_REQUIRE((flags & ~(uint32_t)RTPE_FWD_NO_LANES) == 0, "forward_mixed: unknown flag bits 0x%x", flags);
+  RTPE_REQUIRE((flags & ~(uint32_t)(RTPE_FWD_NO_LANES | RTPE_FWD_TRACE)) == 0, "forward_mixed: unknown flag bits 0x%x", flags);
   RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F32, "forward_mixed: the outputs are float32 buffers");
   // everything that can be refused is refused here, before the table leaves the host
   int rc = check_shape(h, N, Hc, Wc, "forward_mixed", true);

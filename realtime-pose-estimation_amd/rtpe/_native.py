@@ -263,6 +263,14 @@ _SIGS_MIXDEC = {
     "rtpe_adjust_refine_fused_mixed_topk_n": (c_int32, list(_SIGS_SIZES["rtpe_adjust_refine_fused_topk_sizes_n"][1])),
 }
 EXPORTS_MIXDEC = tuple(_SIGS_MIXDEC)    # those of include/rtpe_hip_mixdec.h, likewise
+# what one forward enqueued (include/rtpe_hip_trace.h): forward_aux with the per-call flags, and the trace's read-back
+FWD_TRACE = 2
+TRACE_INTS, TRACE_LAUNCH, TRACE_RECORD, TRACE_WAIT, TRACE_MASK, TRACE_FORK_EVENT = 5, 1, 2, 3, 4, 4
+_SIGS_TRACE = {
+    "rtpe_hrnet_forward_aux_flags": (c_int32, _SIGS["rtpe_hrnet_forward_aux"][1] + [c_uint32]),
+    "rtpe_hrnet_read_trace": (c_int32, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
+}
+EXPORTS_TRACE = tuple(_SIGS_TRACE)      # those of include/rtpe_hip_trace.h, likewise
 _lib = None
 
 
@@ -287,7 +295,7 @@ def lib():
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
-                list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()):
+                list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()
