@@ -717,5 +717,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_mixed.h"
 #include "rtpe_hip_mixdec.h"
 #include "rtpe_hip_trace.h"
+#include "rtpe_hip_mixed_aux.h"
 
 #endif /* RTPE_HIP_H */

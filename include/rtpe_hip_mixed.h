@@ -24,6 +24,10 @@
  * property, a program with a transposed conv, a fused BasicBlock pair, a grouped stride-2 launch or a second input
  * (aux pack, resize, gate_mul), an op below 1 / 32, a side below 32, an image larger than the canvas, outputs other
  * than float32.
+ *
+ * A program with a second input (AttentionStudentSteps) runs its mixed forward through the entry of
+ * rtpe_hip_mixed_aux.h, which takes the second canvas; the forward entry of this file has no argument for it and keeps
+ * refusing such a program.  rtpe_hrnet_mixed_workspace_bytes sizes the workspace of either kind.
  */
 #ifndef RTPE_HIP_MIXED_H
 #define RTPE_HIP_MIXED_H

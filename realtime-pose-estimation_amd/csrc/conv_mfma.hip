@@ -686,7 +686,8 @@ bool conv_deint(const ConvPlan& p, int kind) {
 
 // ... and those of them that a mixed-size batch can reach (ConvArgs::mixed; the MIXED instantiations): the default launch
 // shapes of the one-workgroup-per-tile kernel (conv_make_tile without the other kernels: 2, 4, 5 or 8 pixel tiles per wave
-// on 4 or 5 waves, whole cout blocks)
+// on 4 or 5 waves, whole cout blocks; never 8 tiles at mt = 4 nor more than 2 at mt = 6: conv_make_tile) - those of the Steps
+// student's 5x5 stride-2 and 100-channel convs among them.  route_ops() asks conv_has_mixed_variant() before the first launch
 #define RTPE_CONV_MIXED_VARIANTS(V)                                                                     \
   V(3, 8, 4) V(3, 4, 4) V(3, 2, 4) V(3, 5, 4) V(3, 5, 5) V(4, 4, 4) V(4, 2, 4) V(4, 5, 4) V(4, 5, 5) V(6, 2, 4)   \
   V(2, 8, 4) V(2, 4, 4) V(2, 2, 4) V(2, 5, 4) V(2, 5, 5) V(1, 8, 4) V(1, 4, 4) V(1, 2, 4) V(1, 5, 4) V(1, 5, 5)
@@ -694,6 +695,15 @@ bool conv_deint(const ConvPlan& p, int kind) {
 static bool conv_has_variant(int mt, int nt, int waves) {
 #define RTPE_V(MTv, NTv, Wv) if (mt == MTv && nt == NTv && waves == Wv) return true;
   RTPE_CONV_VARIANTS(RTPE_V)
+#undef RTPE_V
+  return false;
+}
+
+// (the executor asks before the first launch of a mixed forward: a shape without a MIXED instantiation is an error there,
+// never an unmasked run)
+bool conv_has_mixed_variant(int mt, int nt, int waves) {
+#define RTPE_V(MTv, NTv, Wv) if (mt == MTv && nt == NTv && waves == Wv) return true;
+  RTPE_CONV_MIXED_VARIANTS(RTPE_V)
 #undef RTPE_V
   return false;
 }

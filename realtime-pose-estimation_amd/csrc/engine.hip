@@ -560,17 +560,21 @@ static void slot_layout(const rtpe_hrnet* h, int N, int H, int W, std::vector<si
 // map that the extent rule does not double, and a fused BasicBlock pair or a stride-2 group has no launch of its own to fall
 // back to in the records of a forward.  The nearest-to-size sampler of the fuse ops has one row of workgroups per output row.
 // A mixed-size batch (`mixed`, rtpe_hip_mixed.h) is held to the rules of a ragged shape whatever its canvas size, and its ops
-// to those that mask by the extent table: no second input, and no tensor below 1/32 read by a conv, a fuse sum or an SE mean.
-static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who, bool mixed = false) {
+// to those that mask by the extent table: no tensor below 1/32 read by a conv, a resize, a fuse sum or an SE mean.  A program
+// with a second input goes through rtpe_hrnet_forward_mixed_aux (rtpe_hip_mixed_aux.h), which brings it (`aux_ok`); the entry
+// without one refuses it here.
+static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who, bool mixed = false, bool aux_ok = false) {
   RTPE_REQUIRE(N > 0 && H >= 32 && W >= 32, "%s: N=%d H=%d W=%d", who, N, H, W);
   if (mixed) {
     RTPE_REQUIRE(h->any_size, "%s: a mixed-size batch needs a program with the any_size property (the students'); this program "
                  "takes one size per batch, multiples of 32", who);
     for (size_t i = 0; i < h->ops.size(); ++i) {
       const rtpe_op_desc& d = h->ops[i].d;
-      RTPE_REQUIRE(d.kind != RTPE_OP_AUX_PACK && d.kind != RTPE_OP_RESIZE && d.kind != RTPE_OP_GATE_MUL,
-                   "%s: op %zu: a program with a second input (aux pack, resize, gate_mul) takes no mixed-size batch", who, i);
+      RTPE_REQUIRE(aux_ok || (d.kind != RTPE_OP_AUX_PACK && d.kind != RTPE_OP_RESIZE && d.kind != RTPE_OP_GATE_MUL),
+                   "%s: op %zu: a program with a second input (aux pack, resize, gate_mul) takes a mixed-size batch through "
+                   "rtpe_hrnet_forward_mixed_aux only", who, i);
       int top = -1;                                     // the deepest level whose row of the table this op reads
+      if (d.kind == RTPE_OP_RESIZE) top = h->tensors[d.in_t].ds_log2 > h->tensors[d.out_t].ds_log2 ? h->tensors[d.in_t].ds_log2 : h->tensors[d.out_t].ds_log2;
       if (d.kind == RTPE_OP_CONV) top = h->tensors[d.in_t].ds_log2 + (d.stride == 2 ? 1 : 0);
       if (d.kind == RTPE_OP_STEM) top = 1;
       if (d.kind == RTPE_OP_AVGPOOL || d.kind == RTPE_OP_SE) top = h->tensors[d.in_t].ds_log2;
@@ -850,6 +854,8 @@ static int route_ops(const Fwd& f, std::vector<Route>* routes, std::vector<ConvA
     }
     for (int k = 0; k < o.n_geom; ++k) r.tile[k] = f.tile(i, k, conv_pos(h, d, f.H), conv_pos(h, d, f.W));
     if (f.rag) {       // every conv on the one-workgroup-per-tile kernel, which masks its reads and stores at every edge
+      RTPE_REQUIRE(f.ext == nullptr || conv_has_mixed_variant(o.plan[0].mt, r.tile[0].nt, r.tile[0].waves),
+                   "forward: op %zu: no mixed-size kernel variant mt=%d nt=%d waves=%d", i, o.plan[0].mt, r.tile[0].nt, r.tile[0].waves);
       (*args)[i] = conv_op_args(f, i, 0, r.tile[0]);
       r.how = kRouteTile;
       continue;
@@ -1150,7 +1156,9 @@ static int launch_f32_op(const Fwd& f, const FwdCall& c, size_t i, hipStream_t s
   const size_t pixels = (size_t)N * Hi * Wi;
   if (d.kind == RTPE_OP_CAST) return cast_launch(f.tptr(d.in_t, d.in_coff), ti.channels, y, to.channels, d.cout, pixels, s);
   const float* x = reinterpret_cast<const float*>(f.tptr(d.in_t, d.in_coff));
-  if (d.kind == RTPE_OP_RESIZE) return resize_nhwc_launch(x, ti.channels, Hi, Wi, y, to.channels, Ho, Wo, d.cout, N, s);
+  if (d.kind == RTPE_OP_RESIZE)       // (a mixed-size batch: image n's own scale, clamp and extent, from its rows of the table)
+    return resize_nhwc_launch(x, ti.channels, Hi, Wi, y, to.channels, Ho, Wo, d.cout, N, s, f.ext ? f.level(ti.ds_log2) : nullptr,
+                              f.ext ? f.level(to.ds_log2) : nullptr);
   float div;                                     // gate_mul
   memcpy(&div, &d.reserved[0], sizeof(float));
   return gate_mul_launch(x, ti.channels, reinterpret_cast<const float*>(f.tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels, y,
@@ -1409,7 +1417,7 @@ static int mask_mixed_outputs(const Fwd& f, const FwdCall& c) {
     if (!(d.flags & (RTPE_F_OUT_PREDS | RTPE_F_OUT_REFINED))) continue;
     const int k = (d.flags & RTPE_F_OUT_REFINED) ? 1 : 0;
     y[k] = reinterpret_cast<float*>(k ? c.refined : c.preds);
-    C[k] = d.kind == RTPE_OP_SIGMOID_ADD ? 1 : d.cout;
+    C[k] = d.kind == RTPE_OP_SIGMOID_ADD || d.kind == RTPE_OP_GATE_MUL ? 1 : d.cout;
     lv[k] = h->tensors[d.in_t].ds_log2 + (d.kind == RTPE_OP_CONV && d.stride == 2 ? 1 : 0);
   }
   for (int k = 0; k < 2; ++k) if (y[k] == nullptr) C[k] = 0;
@@ -1457,7 +1465,7 @@ static int run(rtpe_hrnet* h, const FwdCall& c) {
   // the call (the stream and every buffer must belong to it) and give the caller's device back afterwards
   DeviceGuard guard(h->device);
   RTPE_HIP_CHECK(guard.err);
-  int rc = check_shape(h, c.N, c.H, c.W, "forward", c.ext != nullptr);
+  int rc = check_shape(h, c.N, c.H, c.W, "forward", c.ext != nullptr, c.aux != nullptr);
   if (rc != RTPE_OK) return rc;
   RTPE_REQUIRE(c.x_dtype == RTPE_DTYPE_F16 || c.x_dtype == RTPE_DTYPE_F32, "forward: x dtype");
   RTPE_REQUIRE(c.out_dtype == RTPE_DTYPE_F16 || c.out_dtype == RTPE_DTYPE_F32, "forward: out dtype");
@@ -1630,7 +1638,7 @@ extern "C" int rtpe_mixed_table_fill(const int32_t* sizes_hw, int32_t N, int32_t
 extern "C" int rtpe_hrnet_mixed_workspace_bytes(const rtpe_hrnet* h, int32_t N, int32_t Hc, int32_t Wc, size_t* bytes) {
   RTPE_REQUIRE(h != nullptr && bytes != nullptr, "mixed_workspace_bytes: null argument");
   {
-    const int rc = check_shape(h, N, Hc, Wc, "mixed_workspace_bytes", true);
+    const int rc = check_shape(h, N, Hc, Wc, "mixed_workspace_bytes", true, /*aux_ok=*/true);
     if (rc != RTPE_OK) return rc;
   }
   std::vector<size_t> offs;
@@ -1639,16 +1647,21 @@ extern "C" int rtpe_hrnet_mixed_workspace_bytes(const rtpe_hrnet* h, int32_t N, 
   return RTPE_OK;
 }
 
-extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t Hc, int32_t Wc,
-                                        const int32_t* sizes_hw, int32_t* table_pinned, int32_t table_ints, void* preds,
-                                        void* refined, int32_t out_dtype, void* workspace, size_t workspace_bytes, void* stream,
-                                        uint32_t flags) {
+// both entries: `aux` is the second input's canvas, or null for a program that has none
+static int forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_dtype, const void* aux, int32_t N, int32_t Hc, int32_t Wc,
+                         const int32_t* sizes_hw, int32_t* table_pinned, int32_t table_ints, void* preds, void* refined,
+                         int32_t out_dtype, void* workspace, size_t workspace_bytes, void* stream, uint32_t flags) {
   RTPE_REQUIRE(h && x && workspace && sizes_hw && table_pinned, "forward_mixed: null argument");
   RTPE_REQUIRE((flags & ~(uint32_t)(RTPE_FWD_NO_LANES | RTPE_FWD_TRACE)) == 0, "forward_mixed: unknown flag bits 0x%x", flags);
   RTPE_REQUIRE(out_dtype == RTPE_DTYPE_F32, "forward_mixed: the outputs are float32 buffers");
   // everything that can be refused is refused here, before the table leaves the host
-  int rc = check_shape(h, N, Hc, Wc, "forward_mixed", true);
+  int rc = check_shape(h, N, Hc, Wc, "forward_mixed", true, aux != nullptr);
   if (rc != RTPE_OK) return rc;
+  if (aux != nullptr) {
+    bool has_aux = false;
+    for (const OpState& o : h->ops) has_aux = has_aux || o.d.kind == RTPE_OP_AUX_PACK;
+    RTPE_REQUIRE(has_aux, "forward_mixed_aux: this program has no second input (use rtpe_hrnet_forward_mixed)");
+  }
   rc = rtpe_mixed_table_fill(sizes_hw, N, Hc, Wc, table_pinned, table_ints);
   if (rc != RTPE_OK) return rc;
   std::vector<size_t> offs;
@@ -1671,7 +1684,26 @@ extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_
   FwdCall c = fwd_call(x, x_dtype, N, Hc, Wc, preds, refined, out_dtype, workspace, ws_need, stream);
   c.flags = flags;
   c.ext = table_dev;
+  c.aux = aux;
   return run(h, c);
+}
+
+extern "C" int rtpe_hrnet_forward_mixed(rtpe_hrnet* h, const void* x, int32_t x_dtype, int32_t N, int32_t Hc, int32_t Wc,
+                                        const int32_t* sizes_hw, int32_t* table_pinned, int32_t table_ints, void* preds,
+                                        void* refined, int32_t out_dtype, void* workspace, size_t workspace_bytes, void* stream,
+                                        uint32_t flags) {
+  return forward_mixed(h, x, x_dtype, nullptr, N, Hc, Wc, sizes_hw, table_pinned, table_ints, preds, refined, out_dtype, workspace,
+                       workspace_bytes, stream, flags);
+}
+
+// ---- ... of a program with a second input (include/rtpe_hip_mixed_aux.h) ----
+extern "C" int rtpe_hrnet_forward_mixed_aux(rtpe_hrnet* h, const void* x, int32_t x_dtype, const void* aux_nchw_f32, int32_t N,
+                                            int32_t Hc, int32_t Wc, const int32_t* sizes_hw, int32_t* table_pinned,
+                                            int32_t table_ints, void* preds, void* refined, int32_t out_dtype, void* workspace,
+                                            size_t workspace_bytes, void* stream, uint32_t flags) {
+  RTPE_REQUIRE(aux_nchw_f32 != nullptr, "forward_mixed_aux: the second input is null");
+  return forward_mixed(h, x, x_dtype, aux_nchw_f32, N, Hc, Wc, sizes_hw, table_pinned, table_ints, preds, refined, out_dtype,
+                       workspace, workspace_bytes, stream, flags);
 }
 
 // ---- single-layer entry (layer-level parity tests) -------------------------

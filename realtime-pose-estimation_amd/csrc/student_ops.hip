@@ -272,8 +272,15 @@ __device__ __forceinline__ void axis_half_pixel(float scale, int n_in, int n_out
   *l0 = 1.f - l;
 }
 
+// MIXED (a mixed-size batch, rtpe_hip_mixed_aux.h): Hi, Wi, Ho, Wo are the canvas extents and only address; image n's own
+// input and output extents come from its rows of the extent table (ext_in, ext_out), and with them everything that
+// F.interpolate of that image alone derives from its size: the scale (the same correctly rounded float division as on the
+// host), the clamp at h_n - 1, the n_in == n_out shortcut.  Nothing is stored beyond image n's output extent.  !MIXED: the
+// kernel as it was, the scales from the host (an instantiation of its own, as conv_mfma_kernel's).
+template <bool MIXED>
 __global__ void __launch_bounds__(256) resize_nhwc_kernel(const float* x, int in_ld, int Hi, int Wi, float* y, int out_ld,
-                                                          int Ho, int Wo, int C, int N, float sy, float sx) {
+                                                          int Ho, int Wo, int C, int N, float sy, float sx,
+                                                          const int* ext_in, const int* ext_out) {
   const int c4 = C >> 2;
   const size_t total = (size_t)N * Ho * Wo * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -283,10 +290,18 @@ __global__ void __launch_bounds__(256) resize_nhwc_kernel(const float* x, int in
     p /= Wo;
     const int oy = (int)(p % Ho);
     const int n = (int)(p / Ho);
+    int hi = Hi, wi = Wi, ho = Ho, wo = Wo;
+    if constexpr (MIXED) {
+      hi = ext_in[2 * n]; wi = ext_in[2 * n + 1];
+      ho = ext_out[2 * n]; wo = ext_out[2 * n + 1];
+      if (oy >= ho || ox >= wo) continue;
+      sy = __fdiv_rn((float)hi, (float)ho);
+      sx = __fdiv_rn((float)wi, (float)wo);
+    }
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    axis_half_pixel(sy, Hi, Ho, oy, &y0, &y1, &ly0, &ly1);
-    axis_half_pixel(sx, Wi, Wo, ox, &x0, &x1, &lx0, &lx1);
+    axis_half_pixel(sy, hi, ho, oy, &y0, &y1, &ly0, &ly1);
+    axis_half_pixel(sx, wi, wo, ox, &x0, &x1, &lx0, &lx1);
     const float* b = x + (size_t)n * Hi * Wi * in_ld + c;
     const float4 v00 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * Wi + x0) * in_ld);
     const float4 v01 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * Wi + x1) * in_ld);
@@ -480,10 +495,16 @@ int aux_pack_launch(const float* aux_nchw, float* y, int out_ld, int N, int H, i
 }
 
 int resize_nhwc_launch(const float* x, int in_ld, int Hi, int Wi, float* y, int out_ld, int Ho, int Wo, int C, int N,
-                       hipStream_t s) {
+                       hipStream_t s, const int* ext_in, const int* ext_out) {
   RTPE_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0, "resize: channel counts must be multiples of 4");
-  hipLaunchKernelGGL(resize_nhwc_kernel, dim3(grid_for((size_t)N * Ho * Wo * (C / 4))), dim3(256), 0, s, x, in_ld, Hi, Wi,
-                     y, out_ld, Ho, Wo, C, N, (float)Hi / (float)Ho, (float)Wi / (float)Wo);
+  RTPE_REQUIRE((ext_in == nullptr) == (ext_out == nullptr), "resize: a mixed-size batch brings both rows of the extent table");
+  const dim3 grid(grid_for((size_t)N * Ho * Wo * (C / 4)));
+  if (ext_in != nullptr)       // the scales are derived on the device, per image
+    hipLaunchKernelGGL(resize_nhwc_kernel<true>, grid, dim3(256), 0, s, x, in_ld, Hi, Wi, y, out_ld, Ho, Wo, C, N, 0.f, 0.f,
+                       ext_in, ext_out);
+  else
+    hipLaunchKernelGGL(resize_nhwc_kernel<false>, grid, dim3(256), 0, s, x, in_ld, Hi, Wi, y, out_ld, Ho, Wo, C, N,
+                       (float)Hi / (float)Ho, (float)Wi / (float)Wo, ext_in, ext_out);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }

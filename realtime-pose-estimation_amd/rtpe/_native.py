@@ -271,6 +271,13 @@ _SIGS_TRACE = {
     "rtpe_hrnet_read_trace": (c_int32, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
 }
 EXPORTS_TRACE = tuple(_SIGS_TRACE)      # those of include/rtpe_hip_trace.h, likewise
+# a mixed-size batch for a program with a second input (include/rtpe_hip_mixed_aux.h): rtpe_hrnet_forward_mixed's arguments
+# with the second canvas behind x_dtype, where rtpe_hrnet_forward_aux has it
+_m = _SIGS_MIXED["rtpe_hrnet_forward_mixed"][1]
+_SIGS_MIXAUX = {
+    "rtpe_hrnet_forward_mixed_aux": (c_int32, _m[:3] + [c_void_p] + _m[3:]),
+}
+EXPORTS_MIXAUX = tuple(_SIGS_MIXAUX)    # that of include/rtpe_hip_mixed_aux.h, likewise
 _lib = None
 
 
@@ -295,7 +302,8 @@ def lib():
         for name, (res, args) in list(_SIGS.items()) + list(_SIGS_SIZES.items()) + list(_SIGS_WARP.items()) + \
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
-                list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()):
+                list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()) + \
+                list(_SIGS_MIXAUX.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

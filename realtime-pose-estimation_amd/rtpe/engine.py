@@ -553,6 +553,8 @@ class StudentPipeline(TeacherPipeline):
     Images of different sizes: ``call_mixed(images)`` runs ONE forward over all of them (``AttentionStudent.forward_mixed``)
     and ONE decode, every image at its own size, straight from the output canvas (``HeatmapParser.parse_lowres_mixed``);
     ``stream_mixed(batches)`` is the pipelined loop over such batches and ``mixed_batches`` cuts a list of images into them.
+    A model with a second input (``AttentionStudentSteps.forward_mixed``) gets it as ``call_mixed(images, alt=alts)``, as
+    ``(images, alts)`` batches of ``stream_mixed`` and through ``mixed_batches(images, batch_size, alts=alts)``.
     ``stream()`` and ``__call__`` take one size per batch and refuse a mixed batch.
 
     There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
@@ -598,30 +600,76 @@ class StudentPipeline(TeacherPipeline):
 
     @staticmethod
     def _is_mixed(batch):
-        """a list of (3, h, w) images or a (canvas, sizes) pair - what ``call_mixed`` / ``forward_mixed`` take"""
+        """a list of (3, h, w) images, a (canvas, sizes) pair, an (images, alts) pair of two lists or a (canvas, sizes,
+        alt_canvas) triple - what ``call_mixed`` / ``forward_mixed`` take"""
         if not isinstance(batch, (list, tuple)) or not batch:
             return False
         if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
             return True
+        if len(batch) == 3:
+            return torch.is_tensor(batch[0]) and not torch.is_tensor(batch[1]) and batch[1] is not None
         return len(batch) == 2 and not torch.is_tensor(batch[1]) and batch[1] is not None
 
+    def _mixed_takes_alt(self):
+        """the model's ``forward_mixed`` has the second input ``alt`` (``AttentionStudentSteps``) and does not run without it"""
+        import inspect
+        try:
+            return "alt" in inspect.signature(self.model.forward_mixed).parameters
+        except (TypeError, ValueError):
+            return False
+
+    def _mixed_alt(self, alts, sizes, canvas_hw, who):
+        """the ``alt`` images of a mixed batch, checked against the images' sizes on the host and packed into a canvas of
+        the first one's size; None stays None.  A model that needs them and gets none, or gets them and has no use for
+        them, is refused here, before the forward."""
+        from .students import pack_mixed
+        if alts is None:
+            if self._mixed_takes_alt():
+                raise ValueError("%s: the model needs the second input of every image (alt: a list of (3, h_n, w_n) tensors "
+                                 "of the images' sizes)" % who)
+            return None
+        if not self._mixed_takes_alt():
+            raise ValueError("%s: the model's forward_mixed takes no second input (alt)" % who)
+        alts = list(alts)
+        if len(alts) != len(sizes):
+            raise ValueError("%s: %d alt images for %d images" % (who, len(alts), len(sizes)))
+        for n, (a, hw) in enumerate(zip(alts, sizes)):
+            if not torch.is_tensor(a) or a.dim() != 3 or a.shape[0] != 3 or tuple(a.shape[1:]) != tuple(hw):
+                raise ValueError("%s: alt image %d must be a (3, %d, %d) tensor like its image, got %s"
+                                 % (who, n, hw[0], hw[1], tuple(a.shape) if torch.is_tensor(a) else type(a).__name__))
+        return pack_mixed(alts, canvas_hw=canvas_hw)[0]
+
     def _mixed_begin(self, batch):
-        """a mixed batch as ``forward_mixed`` takes it, checked before the forward: a list of (3, h_n, w_n) images is
-        packed (``pack_mixed``, on the current stream), a ``(canvas, sizes)`` pair checked -> ``((canvas, sizes), sizes)``"""
+        """a mixed batch as ``forward_mixed`` takes it, checked before the forward: a list of (3, h_n, w_n) images or an
+        ``(images, alts)`` pair of two such lists is packed (``pack_mixed``, on the current stream), a ``(canvas, sizes)``
+        pair or a ``(canvas, sizes, alt_canvas)`` triple checked -> ``((canvas, sizes[, alt_canvas]), sizes)``"""
         from .students import pack_mixed
         from .third_party.pose_higher_hrnet import check_mixed_sizes
+        who = "StudentPipeline"
         if not hasattr(self.model, "forward_mixed"):
             raise ValueError("StudentPipeline: the model has no forward_mixed")
         if not self._is_mixed(batch):
             raise ValueError("StudentPipeline: a mixed-size batch is a list of (3, h, w) images or a (canvas, sizes) pair")
         if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
             canvas, sizes = pack_mixed(batch)
+            alt = self._mixed_alt(None, sizes, tuple(canvas.shape[2:]), who)
+        elif len(batch) == 2 and isinstance(batch[0], (list, tuple)):        # (images, alts)
+            canvas, sizes = pack_mixed(batch[0])
+            alt = self._mixed_alt(batch[1], sizes, tuple(canvas.shape[2:]), who)
         else:
-            canvas, sizes = batch
+            canvas, sizes = batch[0], batch[1]
             if not torch.is_tensor(canvas) or canvas.dim() != 4 or canvas.shape[1] != 3:
                 raise ValueError("StudentPipeline: the canvas of a mixed batch is (N,3,Hc,Wc)")
             sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])
-        return (canvas, sizes), sizes
+            alt = batch[2] if len(batch) == 3 else None
+            if alt is None:
+                self._mixed_alt(None, sizes, None, who)
+            elif not self._mixed_takes_alt():
+                raise ValueError("StudentPipeline: the model's forward_mixed takes no second input (alt)")
+            elif not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape) or alt.device != canvas.device:
+                raise ValueError("StudentPipeline: the alt canvas of a mixed batch is a tensor like the first canvas, %s on %s"
+                                 % (tuple(canvas.shape), canvas.device))
+        return ((canvas, sizes) if alt is None else (canvas, sizes, alt)), sizes
 
     def _mixed_forwards(self, k, batch, on_forward):
         att, det = self._att_det(on_forward(k, batch) if on_forward is not None else self.model.forward_mixed(*batch))
@@ -634,9 +682,11 @@ class StudentPipeline(TeacherPipeline):
         return self.parser.lowres_topk_mixed(outs[1].float(), sizes)
 
     @torch.no_grad()
-    def call_mixed(self, images, image_ids=None, decode="batch"):
-        """images: a list of (3, h_n, w_n) tensors on the GPU, any sizes >= 32 -> per image what ``self(x_n[None])``
-        returns for it: ``pack_mixed``, ONE ``forward_mixed``, then ONE decode of the whole batch straight from the ``det``
+    def call_mixed(self, images, image_ids=None, decode="batch", alt=None):
+        """images: a list of (3, h_n, w_n) tensors on the GPU, any sizes >= 32 [, ``alt``: the list of the same images in
+        the alternative colour space, same sizes, for a model with a second input] -> per image what ``self(x_n[None])``
+        (``self(x_n[None], alt=alt_n[None])``) returns for it: ``pack_mixed``, ONE ``forward_mixed``, then ONE decode of
+        the whole batch straight from the ``det``
         canvas, every image at its own (h_n, w_n) from its own region (``HeatmapParser.parse_lowres_mixed``: nothing is
         copied).  ``decode="per_image"``: every image decoded on its own with ``parse_lowres_shared`` from a contiguous copy
         of its region - N region copies, N sets of launches and 2N host waits in series; the same bits, kept for A/B
@@ -650,14 +700,16 @@ class StudentPipeline(TeacherPipeline):
         canvas, sizes = pack_mixed(images)
         if image_ids is not None and len(image_ids) != len(sizes):
             raise ValueError("StudentPipeline.call_mixed: %d image ids for %d images" % (len(image_ids), len(sizes)))
+        alt = self._mixed_alt(alt, sizes, tuple(canvas.shape[2:]), "StudentPipeline.call_mixed")
+        batch = (canvas, sizes) if alt is None else (canvas, sizes, alt)
         if decode == "batch":
             records = None if image_ids is None else self.parser.check_records(len(sizes), (image_ids, None))
-            att, det = self._mixed_forwards(0, (canvas, sizes), None)
+            att, det = self._mixed_forwards(0, batch, None)
             res = self.parser.parse_lowres_mixed(det.float(), sizes, records=records)
             return res if records is None else [res[n:n + 1] for n in range(len(sizes))]
         records = [None if image_ids is None else self.parser.check_records(1, ([image_ids[n]], None))
                    for n in range(len(sizes))]
-        att, det = self._mixed_forwards(0, (canvas, sizes), None)
+        att, det = self._mixed_forwards(0, batch, None)
         out = []
         for n, (_, d) in enumerate(unpack_mixed(att, det, sizes)):
             d = d.unsqueeze(0).float().contiguous()
@@ -670,24 +722,32 @@ class StudentPipeline(TeacherPipeline):
         """``stream()`` over mixed-size batches: the same software-pipelined loop F(k) R(k-1) T(k) - decode stream,
         forward streams and workspace slots, ``exclusive``, early stop, two-step delay of the results - with
         F = ``forward_mixed`` and T = ``HeatmapParser.lowres_topk_mixed`` on the ``det`` canvas.  Every batch is a list of
-        (3, h_n, w_n) images (packed on the caller's stream) or a ``(canvas, sizes)`` pair (``pack_mixed``); every image is
-        decoded at its own size.  ``on_forward(k, (canvas, sizes))`` may replace the forward and returns ``(att, det)``.
+        (3, h_n, w_n) images (packed on the caller's stream) or a ``(canvas, sizes)`` pair (``pack_mixed``); for a model
+        with a second input an ``(images, alts)`` pair of two lists or a ``(canvas, sizes, alt_canvas)`` triple.  Every image
+        is decoded at its own size.  ``on_forward(k, (canvas, sizes[, alt_canvas]))`` may replace the forward and returns
+        ``(att, det)``.
         Yields per batch what ``call_mixed`` returns for it, or with ``records`` (``k -> (image_ids, None)``; needs
         ``match_on="device"``) the (N, RECORD_FLOATS) record tensor of the batch."""
         return self._stream_loop(batches, lambda k, x: self._mixed_begin(x), self._mixed_forwards, self._mixed_topk,
                                  on_forward, decode_stream, in_flight, exclusive, records)
 
     @staticmethod
-    def mixed_batches(images, batch_size=32):
+    def mixed_batches(images, batch_size=32, alts=None):
         """cut a list of images of different sizes into batches for ``call_mixed`` / ``stream_mixed``: the images
         sorted by area (so that a canvas wastes little on its smaller images; ties keep the caller's order), then runs
         of ``batch_size``.  ``images``: (3, h, w) tensors, or anything with such a ``.shape``.  Returns
         ``(batches, restore)``: ``batches[b]`` the list of images of batch b, and ``restore(results)`` - ``results[b]`` the
-        per-image list that batch b gave - the results of all images in the caller's order.  Pure host function."""
+        per-image list that batch b gave - the results of all images in the caller's order.  With ``alts`` (one per image,
+        for a model with a second input) they are cut in the same order and ``batches[b]`` is the pair ``(images, alts)``
+        of batch b, as ``stream_mixed`` takes it.  Pure host function."""
         images = list(images)
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("StudentPipeline.mixed_batches: batch_size must be at least 1, not %d" % batch_size)
+        if alts is not None:
+            alts = list(alts)
+            if len(alts) != len(images):
+                raise ValueError("StudentPipeline.mixed_batches: %d alts for %d images" % (len(alts), len(images)))
         order = sorted(range(len(images)), key=lambda i: int(images[i].shape[-2]) * int(images[i].shape[-1]))
         cuts = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
 
@@ -701,6 +761,8 @@ class StudentPipeline(TeacherPipeline):
                 for i, v in zip(c, r):
                     out[i] = v
             return out
+        if alts is not None:
+            return [([images[i] for i in c], [alts[i] for i in c]) for c in cuts], restore
         return [[images[i] for i in c] for c in cuts], restore
 
     @torch.no_grad()

@@ -424,9 +424,33 @@ class AttentionStudentSteps(CompiledModule):
         b.conv(x, self.steps[3], None, out_flag=nat.F_OUT_REFINED, nhwc=False)
         return b.finish()
 
-    def forward_mixed(self, canvas, sizes):
-        raise NotImplementedError("rtpe: AttentionStudentSteps has no mixed-size forward: its second input (aux pack, "
-                                  "resize) and its 5x5 stem are not masked per image; use AttentionStudent")
+    def forward_mixed(self, canvas, sizes, alt=None, att_divisor=None):
+        """one forward over N images of different sizes: ``canvas`` and ``alt`` (N,3,Hc,Wc) fp32 on the GPU with image n
+        (and the image in the alternative colour space) at ``[n, :, :h_n, :w_n]`` of both, ``sizes = [(h_n, w_n)]``
+        (``pack_mixed(images)``, ``pack_mixed(alts, canvas_hw=canvas.shape[2:])``) -> (att, det) canvases as
+        ``AttentionStudent.forward_mixed`` returns them: image n's region ``[n, :, :ceil(h_n/4), :ceil(w_n/4)]`` holds the
+        bits of ``self(x_n[None], alt=alt_n[None], att_divisor=att_divisor)``, every other element is 0.0 whatever either
+        canvas holds outside the images.  One compiled program per ``att_divisor`` value, as for ``forward``.
+
+        The resize of ``alt`` takes image n's own scale, clamp and extents from the extent table, every conv masks by
+        them ("Mixed-size batches: the Steps student").  General kernels on default launch shapes,
+        never autotuned."""
+        who = "AttentionStudentSteps.forward_mixed"
+        if alt is None:                   # (as forward's "alt is expected")
+            raise NotImplementedError("rtpe: %s needs the second input: alt=, the canvas of the images in the alternative "
+                                      "colour space (pack_mixed(alts, canvas_hw=canvas.shape[2:]))" % who)
+        if canvas.dim() != 4 or canvas.shape[1] != 3:
+            raise ValueError("%s: expected a canvas (N,3,Hc,Wc), got %s" % (who, tuple(canvas.shape)))
+        if not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape):
+            raise ValueError("%s: alt must be a canvas like the first, %s, got %s" %
+                             (who, tuple(canvas.shape), tuple(alt.shape) if torch.is_tensor(alt) else type(alt).__name__))
+        if alt.device != canvas.device:
+            raise ValueError("%s: the canvases are on different devices (%s and %s)" % (who, canvas.device, alt.device))
+        sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])     # (before any GPU work)
+        self._check_inference(canvas, who)
+        eng = self._engine(canvas.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))
+        att, det = eng.forward_mixed(canvas.float(), sizes, aux=alt.float())
+        return att, det
 
     def forward(self, x, out_hw=None, alt=None, att_divisor=None):
         """x (N,3,H,W) fp32 on the GPU (any H, W >= 32), alt (N,3,H,W) fp32: the image in the alternative

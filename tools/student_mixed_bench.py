@@ -31,10 +31,18 @@ threads).  ``people`` says how many people a pass finds: the seeded student's ma
 of 30 in every image (7,680 in 256 images), so the grouping and adjust + refine run at full load - real images have a
 handful of people, and less of that work.
 
+``--model steps``: the same two measurements for ``AttentionStudentSteps(inplanes=48)`` (seeded W1 weights of
+tests/golden/student_steps_shapes.json; fp32 body, it has no other).  Every image has a second input of its own size (seeded
+values of a LAB image's span); A is ``stu(x_n[None], alt=alt_n[None])``, B ``forward_mixed(canvas, sizes, alt=alt_canvas)`` with
+both canvases packed beforehand, the pipeline modes ``call_mixed(images, alt=alts)`` / ``stream_mixed`` over the
+``(images, alts)`` batches of ``mixed_batches(images, batch, alts=alts)``.  B's regions must equal A's outputs bit for bit on
+every image before anything is timed (an assertion, with both models).
+
 Prints one JSON line per model (--out FILE also writes them).  Needs a GPU; there is no fallback.
 
     python tools/student_mixed_bench.py [--images 256] [--batch 32] [--repeats 4] [--out profiles/student_mixed_bench.json]
     python tools/student_mixed_bench.py --what pipeline [--match-on host] [--out profiles/student_mixed_decode_bench.json]
+    python tools/student_mixed_bench.py --model steps [--what pipeline] [--out profiles/student_steps_mixed_bench.json]
 """
 import argparse
 import json
@@ -57,6 +65,8 @@ def main():
     ap.add_argument("--what", choices=("forward", "pipeline"), default="forward",
                     help="forward: forward_mixed against the per-image loop; pipeline: call_mixed / stream_mixed, decode included")
     ap.add_argument("--match-on", choices=("host", "device"), default="host", help="--what pipeline: where people are grouped")
+    ap.add_argument("--model", choices=("student", "steps"), default="student",
+                    help="student: AttentionStudent(inplanes=100), both bodies; steps: AttentionStudentSteps(inplanes=48), with alt")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -67,16 +77,18 @@ def main():
     from mixed_size_bench import mix_sizes
     from oracle import synth
     from rtpe import _native as nat
-    from rtpe.students import AttentionStudent, pack_mixed, unpack_mixed
+    from rtpe.students import AttentionStudent, AttentionStudentSteps, pack_mixed, unpack_mixed
     torch.set_num_threads(nat.host_threads(8))
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    with open(os.path.join(ROOT, "tests", "golden", "student_shapes.json")) as f:
+    steps = args.model == "steps"
+    with open(os.path.join(ROOT, "tests", "golden", "student_steps_shapes.json" if steps else "student_shapes.json")) as f:
         shapes = {k: tuple(v) for k, v in json.load(f)["shapes"].items()}
     sizes = mix_sizes(args.images)
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
     images = [torch.randn(3, h, w, generator=g, device=dev) for h, w in sizes]
+    alts = [torch.rand(3, h, w, generator=g, device=dev) * 100 - 30 for h, w in sizes] if steps else None
     order = sorted(range(len(sizes)), key=lambda i: (sizes[i][0] * sizes[i][1], sizes[i]))
     chunks = [order[o:o + args.batch] for o in range(0, len(order), args.batch)]
     image_px = sum(h * w for h, w in sizes)
@@ -89,23 +101,29 @@ def main():
         return res, time.perf_counter() - t0
 
     lines = []
-    for body_half in (False, True):
-        stu = AttentionStudent(None, "cpu", 100, 17, 1, True, None, False, body_half=body_half).eval()
-        stu.load_state_dict(synth.make_state_dict(shapes, 3, "W1"), strict=True)
+    for body_half in ((False,) if steps else (False, True)):
+        if steps:
+            stu = AttentionStudentSteps(None, "cpu", 48, 17, 1, True, None, False).eval()
+            stu.load_state_dict(synth.make_state_dict(shapes, 4, "W1"), strict=True)
+        else:
+            stu = AttentionStudent(None, "cpu", 100, 17, 1, True, None, False, body_half=body_half).eval()
+            stu.load_state_dict(synth.make_state_dict(shapes, 3, "W1"), strict=True)
         stu = stu.to(dev)
+        name = "AttentionStudentSteps(inplanes=48)" if steps else "AttentionStudent(inplanes=100)"
         if args.what == "pipeline":
-            lines.append(pipeline_line(args, stu, images, sizes, body_half, dev, timed))
+            lines.append(pipeline_line(args, stu, images, sizes, body_half, dev, timed, alts, name))
             del stu
             torch.cuda.empty_cache()
             continue
         packed = [pack_mixed([images[i] for i in c]) for c in chunks]
+        packed_alt = [pack_mixed([alts[i] for i in c], canvas_hw=p[0].shape[2:])[0] for c, p in zip(chunks, packed)] if steps else None
         canvas_px = sum(c.shape[0] * c.shape[2] * c.shape[3] for c, _ in packed)
 
         def loop_a(keep=False):
             out = []
             with torch.no_grad():
-                for x in images:
-                    r = stu(x[None])
+                for n, x in enumerate(images):
+                    r = stu(x[None], alt=alts[n][None]) if steps else stu(x[None])
                     if keep:
                         out.append(r)
             return out
@@ -113,10 +131,14 @@ def main():
         def loop_b(keep=False, pack=False):
             out = []
             with torch.no_grad():
-                for c, (canvas, sz) in zip(chunks, packed):
+                for k, (c, (canvas, sz)) in enumerate(zip(chunks, packed)):
                     if pack:
                         canvas, sz = pack_mixed([images[i] for i in c])
-                    r = stu.forward_mixed(canvas, sz)
+                    if steps:
+                        ac = pack_mixed([alts[i] for i in c], canvas_hw=canvas.shape[2:])[0] if pack else packed_alt[k]
+                        r = stu.forward_mixed(canvas, sz, alt=ac)
+                    else:
+                        r = stu.forward_mixed(canvas, sz)
                     if keep:
                         out.append(r)
             return out
@@ -127,6 +149,7 @@ def main():
             for i, (a, d) in zip(c, unpack_mixed(att, det, sz)):
                 same = same and bool(torch.equal(a, ra[i][0][0])) and bool(torch.equal(d, ra[i][1][0]))
         del ra, rb
+        assert same, "forward_mixed's regions differ from the per-image forwards: nothing is timed"
         runs = {"A": [], "B": []}
         for r in range(args.repeats):
             for m in (("A", "B") if r % 2 == 0 else ("B", "A")):
@@ -135,7 +158,7 @@ def main():
         _, dt_pack = timed(lambda: loop_b(pack=True))
         med = {m: float(np.median(v)) for m, v in runs.items()}
         lines.append({
-            "metric": "student_mixed_batch_forward", "model": "AttentionStudent(inplanes=100)", "weights": "W1",
+            "metric": "student_mixed_batch_forward", "model": name, "weights": "W1",
             "body": "half" if body_half else "fp32", "device": torch.cuda.get_device_name(dev), "images": len(images),
             "distinct_sizes": len(set(sizes)), "batch": args.batch, "batches_per_pass": len(chunks), "repeats": args.repeats,
             "order": "A B B A", "results_bit_identical": bool(same),
@@ -160,18 +183,21 @@ def main():
                 f.write(json.dumps(ln) + "\n")
 
 
-def pipeline_line(args, stu, images, sizes, body_half, dev, timed):
-    """--what pipeline for one model -> the JSON line"""
+def pipeline_line(args, stu, images, sizes, body_half, dev, timed, alts=None, name="AttentionStudent(inplanes=100)"):
+    """--what pipeline for one model -> the JSON line (``alts``: the second inputs of a model that has one)"""
     import numpy as np
     import torch
     from rtpe.engine import StudentPipeline
     pipe = StudentPipeline(stu, device=dev, match_on=args.match_on)
-    batches, restore = StudentPipeline.mixed_batches(images, args.batch)
+    batches, restore = StudentPipeline.mixed_batches(images, args.batch, alts=alts)
 
     def run(mode):
         if mode == "C":
             return list(pipe.stream_mixed(iter(batches)))
-        return [pipe.call_mixed(b, decode="per_image" if mode == "A" else "batch") for b in batches]
+        decode = "per_image" if mode == "A" else "batch"
+        if alts is not None:
+            return [pipe.call_mixed(b[0], decode=decode, alt=b[1]) for b in batches]
+        return [pipe.call_mixed(b, decode=decode) for b in batches]
 
     def rows(res):
         return [(np.asarray(p, np.float32), np.array(sc, np.float32)) for p, sc in restore(res)]
@@ -184,6 +210,7 @@ def pipeline_line(args, stu, images, sizes, body_half, dev, timed):
             want = got
         same = same and all(a[0].shape == b[0].shape and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
                             for a, b in zip(got, want))
+    assert same, "the three decodes differ: nothing is timed"
     people = int(sum(len(p) if p.ndim == 3 else 0 for p, _ in want))
     runs = {m: [] for m in "ABC"}
     cpu = {m: [] for m in "ABC"}
@@ -200,7 +227,7 @@ def pipeline_line(args, stu, images, sizes, body_half, dev, timed):
                 "ms_per_batch": round(med[m] * 1e3 / len(batches), 3),
                 "cpu_ms_per_batch": round(float(np.median(cpu[m])) * 1e3 / len(batches), 3),
                 "first_pass_s": round(first[m], 2)}
-    return {"metric": "student_mixed_batch_pipeline", "model": "AttentionStudent(inplanes=100)", "weights": "W1",
+    return {"metric": "student_mixed_batch_pipeline", "model": name, "weights": "W1",
             "body": "half" if body_half else "fp32", "device": torch.cuda.get_device_name(dev), "images": len(images),
             "distinct_sizes": len(set(sizes)), "batch": args.batch, "batches_per_pass": len(batches),
             "repeats": args.repeats, "order": "A B C C B A", "match_on": args.match_on, "people": people,
