@@ -367,6 +367,9 @@ static int launch_direct(const DirectArgs& a, int n_blocks_y, hipStream_t s) {
 // cout tiles one wave carries for a layer (0: the layer is not one this kernel takes)
 int conv_direct_mb(const ConvPlan& p) {
   if (p.esize != 2 || p.tapw != 1 || p.in_mul != 1 || p.dil != 1 || p.cc % 32 != 0 || p.kc * 32 != p.cc) return 0;
+  // whole 32-channel steps only: a row of 56 channels (cc 64) has the same padded plan and is not one this kernel reads -
+  // it stays on the one-workgroup-per-tile kernel (conv_direct_launch asks the same of its arguments)
+  if (p.cin != p.cc * p.n_cchunks) return 0;
   const int ks = p.n_cchunks * p.kc, tiles = p.cout_pad / 16;       // the packed k-steps are the 32-channel steps, in order
   static const int cand[] = {8, 6, 4, 3, 2, 1};
   for (int mb : cand) {

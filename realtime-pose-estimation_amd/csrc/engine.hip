@@ -226,8 +226,10 @@ static int plan_ops(rtpe_hrnet* h, const rtpe_op_desc* ops, int n_ops, size_t we
         set_error("op %d: missing operand tensor", i); return RTPE_E_INVALID;
       }
     } else if (d.kind == RTPE_OP_AUX_PACK) {
-      if (h->tensors[d.out_t].reserved != 4 || h->tensors[d.out_t].channels < 4) {
-        set_error("op %d: the packed second input must be an fp32 tensor of >= 4 channels", i); return RTPE_E_INVALID;
+      const rtpe_tensor_desc& t = h->tensors[d.out_t];      // fp32: rows of (r, g, b, 0); fp16 (no RTPE_F_F32): (r, g, b, 0 x 5)
+      if ((d.flags & RTPE_F_F32) ? (t.reserved != 4 || t.channels < 4) : (t.reserved == 4 || t.channels < 8)) {
+        set_error("op %d: the packed second input must be an fp32 tensor of >= 4 channels (fp16 form: an fp16 tensor of >= 8)", i);
+        return RTPE_E_INVALID;
       }
     } else {
       set_error("op %d: unknown kind %d", i, d.kind); return RTPE_E_INVALID;
@@ -570,9 +572,13 @@ static int check_shape(const rtpe_hrnet* h, int N, int H, int W, const char* who
                  "takes one size per batch, multiples of 32", who);
     for (size_t i = 0; i < h->ops.size(); ++i) {
       const rtpe_op_desc& d = h->ops[i].d;
-      RTPE_REQUIRE(aux_ok || (d.kind != RTPE_OP_AUX_PACK && d.kind != RTPE_OP_RESIZE && d.kind != RTPE_OP_GATE_MUL),
+      const bool aux_op = d.kind == RTPE_OP_AUX_PACK || d.kind == RTPE_OP_RESIZE || d.kind == RTPE_OP_GATE_MUL;
+      RTPE_REQUIRE(aux_ok || !aux_op,
                    "%s: op %zu: a program with a second input (aux pack, resize, gate_mul) takes a mixed-size batch through "
                    "rtpe_hrnet_forward_mixed_aux only", who, i);
+      RTPE_REQUIRE(!aux_op || (d.flags & RTPE_F_F32),
+                   "%s: op %zu: the fp16 forms of the second-input ops (aux pack, resize, gate_mul) have no masked form yet: a half "
+                   "body with a second input takes one size per batch", who, i);
       int top = -1;                                     // the deepest level whose row of the table this op reads
       if (d.kind == RTPE_OP_RESIZE) top = h->tensors[d.in_t].ds_log2 > h->tensors[d.out_t].ds_log2 ? h->tensors[d.in_t].ds_log2 : h->tensors[d.out_t].ds_log2;
       if (d.kind == RTPE_OP_CONV) top = h->tensors[d.in_t].ds_log2 + (d.stride == 2 ? 1 : 0);
@@ -1044,6 +1050,25 @@ static int check_ops(const Fwd& f, const FwdCall& c) {
       RTPE_REQUIRE(d.cout > 0 && d.cout % 8 == 0, "op %zu: the fp16 form of this op needs a channel count that is a multiple of 8 (%d)", i, d.cout);
     }
   }
+  // the fp16 forms of aux_pack, resize and gate_mul (the half body of AttentionStudentStepsHalf): the same rule - fp16 tensors,
+  // rows, offsets and channel counts in multiples of 8; gate_mul's logits (in_t) are read one half per pixel
+  for (size_t i = 0; i < h->ops.size(); ++i) {
+    const rtpe_op_desc& d = h->ops[i].d;
+    if ((d.flags & RTPE_F_F32) || (d.kind != RTPE_OP_AUX_PACK && d.kind != RTPE_OP_RESIZE && d.kind != RTPE_OP_GATE_MUL)) continue;
+    const int ts[3] = {d.kind == RTPE_OP_AUX_PACK ? -1 : d.in_t, d.out_t, d.kind == RTPE_OP_GATE_MUL ? d.res_t : -1};
+    for (int k = 0; k < 3; ++k) {
+      if (ts[k] < 0) continue;
+      const rtpe_tensor_desc& t = h->tensors[ts[k]];
+      const bool row = k == 0 && d.kind == RTPE_OP_GATE_MUL;
+      RTPE_REQUIRE(t.reserved != 4 && (row || t.channels % 8 == 0), "op %zu: the fp16 form of this op needs fp16 tensors with rows of a "
+                   "multiple of 8 channels (tensor %d: %d channels of %d bytes)", i, ts[k], t.channels, t.reserved == 4 ? 4 : 2);
+      const int coff = k == 0 ? d.in_coff : k == 1 ? d.out_coff : d.res_coff;
+      RTPE_REQUIRE(row || (coff >= 0 && coff + d.cout <= t.channels),
+                   "op %zu: channels [%d, %d) do not fit tensor %d of %d channels", i, coff, coff + d.cout, ts[k], t.channels);
+    }
+    RTPE_REQUIRE(d.in_coff % 8 == 0 && d.out_coff % 8 == 0 && d.res_coff % 8 == 0, "op %zu: channel offsets must be multiples of 8", i);
+    RTPE_REQUIRE(d.cout > 0 && d.cout % 8 == 0, "op %zu: the fp16 form of this op needs a channel count that is a multiple of 8 (%d)", i, d.cout);
+  }
   // what the call must bring for an op: the second input, and an fp32 `preds` for the sigmoid map that sigmoid_add and
   // gate_mul emit
   for (const OpState& o : h->ops) {
@@ -1143,25 +1168,29 @@ static int launch_fuse(const Fwd& f, size_t i, hipStream_t s) {
   return fuse_launch(a, s);
 }
 
-// the students' ops that exist in fp32 only: cast (fp16 -> fp32), aux_pack, resize, gate_mul
-static int launch_f32_op(const Fwd& f, const FwdCall& c, size_t i, hipStream_t s) {
+// cast (fp16 -> fp32), and the ops of the second input on tensors of T - aux_pack, resize, gate_mul: float, or _Float16 for the
+// half body of AttentionStudentStepsHalf (whose conditions check_ops holds); the launch functions are overloaded on the pointer type
+template <typename T>
+static int launch_aux_op(const Fwd& f, const FwdCall& c, size_t i, hipStream_t s) {
   const rtpe_hrnet* h = f.h;
   const rtpe_op_desc& d = h->ops[i].d;
   const rtpe_tensor_desc& to = h->tensors[d.out_t];
   const int N = f.N, Ho = extent(f.H, to.ds_log2), Wo = extent(f.W, to.ds_log2);
-  float* y = reinterpret_cast<float*>(f.tptr(d.out_t, d.out_coff));
+  T* y = reinterpret_cast<T*>(f.tptr(d.out_t, d.out_coff));
   if (d.kind == RTPE_OP_AUX_PACK) return aux_pack_launch(reinterpret_cast<const float*>(c.aux), y, to.channels, N, Ho, Wo, s);
   const rtpe_tensor_desc& ti = h->tensors[d.in_t];
   const int Hi = extent(f.H, ti.ds_log2), Wi = extent(f.W, ti.ds_log2);
   const size_t pixels = (size_t)N * Hi * Wi;
-  if (d.kind == RTPE_OP_CAST) return cast_launch(f.tptr(d.in_t, d.in_coff), ti.channels, y, to.channels, d.cout, pixels, s);
-  const float* x = reinterpret_cast<const float*>(f.tptr(d.in_t, d.in_coff));
+  if (d.kind == RTPE_OP_CAST)
+    return cast_launch(f.tptr(d.in_t, d.in_coff), ti.channels, reinterpret_cast<float*>(f.tptr(d.out_t, d.out_coff)), to.channels, d.cout,
+                       pixels, s);
+  const T* x = reinterpret_cast<const T*>(f.tptr(d.in_t, d.in_coff));
   if (d.kind == RTPE_OP_RESIZE)       // (a mixed-size batch: image n's own scale, clamp and extent, from its rows of the table)
     return resize_nhwc_launch(x, ti.channels, Hi, Wi, y, to.channels, Ho, Wo, d.cout, N, s, f.ext ? f.level(ti.ds_log2) : nullptr,
                               f.ext ? f.level(to.ds_log2) : nullptr);
   float div;                                     // gate_mul
   memcpy(&div, &d.reserved[0], sizeof(float));
-  return gate_mul_launch(x, ti.channels, reinterpret_cast<const float*>(f.tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels, y,
+  return gate_mul_launch(x, ti.channels, reinterpret_cast<const T*>(f.tptr(d.res_t, d.res_coff)), h->tensors[d.res_t].channels, y,
                          to.channels, d.cout, pixels, div, (d.flags & RTPE_F_OUT_PREDS) ? reinterpret_cast<float*>(c.preds) : nullptr, s);
 }
 
@@ -1232,8 +1261,10 @@ static int launch_op(const Fwd& f, const FwdCall& c, const std::vector<Route>& r
       break;
   }
   switch (o.d.kind) {
-    case RTPE_OP_CAST: case RTPE_OP_AUX_PACK: case RTPE_OP_RESIZE: case RTPE_OP_GATE_MUL:
-      return launch_f32_op(f, c, i, s);
+    case RTPE_OP_CAST:
+      return launch_aux_op<float>(f, c, i, s);
+    case RTPE_OP_AUX_PACK: case RTPE_OP_RESIZE: case RTPE_OP_GATE_MUL:
+      return (o.d.flags & RTPE_F_F32) ? launch_aux_op<float>(f, c, i, s) : launch_aux_op<_Float16>(f, c, i, s);
     case RTPE_OP_AVGPOOL: case RTPE_OP_SE: case RTPE_OP_CAM_COMBINE: case RTPE_OP_SIGMOID_ADD:
       return (o.d.flags & RTPE_F_F32) ? launch_student_op<float>(f, c, i, s) : launch_student_op<_Float16>(f, c, i, s);
     default:

@@ -369,6 +369,13 @@ int aux_pack_launch(const float* aux_nchw, float* y, int out_ld, int N, int H, i
 // ext_in / ext_out (mixed-size batches): (h, w) of every image at the level of the input / of the output; Hi .. Wo address
 int resize_nhwc_launch(const float* x, int in_ld, int Hi, int Wi, float* y, int out_ld, int Ho, int Wo, int C, int N,
                        hipStream_t s, const int* ext_in = nullptr, const int* ext_out = nullptr);
+// the fp16 forms (the half body of AttentionStudentStepsHalf): rows of 8 halves; the second input stays fp32 NCHW, the packed
+// row is (r, g, b, 0 x 5); the resize takes one size per batch only (ext_in and ext_out must be null)
+int gate_mul_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C,
+                    size_t pixels, float div, float* att_out, hipStream_t s);
+int aux_pack_launch(const float* aux_nchw, _Float16* y, int out_ld, int N, int H, int W, hipStream_t s);
+int resize_nhwc_launch(const _Float16* x, int in_ld, int Hi, int Wi, _Float16* y, int out_ld, int Ho, int Wo, int C, int N,
+                       hipStream_t s, const int* ext_in = nullptr, const int* ext_out = nullptr);
 // conv_mfma_kernel has a mixed-size instantiation (RTPE_CONV_MIXED_VARIANTS) for this launch shape of the one-workgroup-per-tile kernel
 bool conv_has_mixed_variant(int mt, int nt, int waves);
 

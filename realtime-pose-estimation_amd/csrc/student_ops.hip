@@ -1,8 +1,8 @@
 // The small NHWC ops of the dual-head student (config 5: AttentionStudent,
 // rtpe/students.py:595-771 of the reference, built from ContextAwareModule
 // :145-201 and SELayer :118-142).  All are single-pass, HBM/latency-bound;
-// channel counts are multiples of 4 (16-byte rows pieces).  avgpool, se, cam_combine and sigmoid_add also have an
-// fp16 form (the half body: 16-byte pieces of 8 channels).
+// channel counts are multiples of 4 (16-byte rows pieces).  avgpool, se, cam_combine, sigmoid_add, gate_mul, aux_pack and
+// resize also have an fp16 form (the half bodies: 16-byte pieces of 8 channels).
 #include "rtpe_common.h"
 
 namespace rtpe {
@@ -22,10 +22,11 @@ __global__ void __launch_bounds__(256) cast_kernel(const _Float16* x, int in_ld,
   }
 }
 
-// The four ops below exist in two storage precisions, like the convs (conv_mfma.hip, Prec<T>): fp32 (float, 4 channels per
-// 16-byte access) and fp16 (_Float16, 8 channels per 16-byte access: the half body of AttentionStudent, body_half=True).
-// The arithmetic is fp32 in both; Elem<T>::rnd marks the points at which PyTorch-CPU's half ops round to fp16 (pinned by
-// tests/test_student_half_host.py) and is the identity for fp32, whose instantiations compute what they always did.
+// The seven templates below exist in two storage precisions, like the convs (conv_mfma.hip, Prec<T>): fp32 (float, 4 channels
+// per 16-byte access) and fp16 (_Float16, 8 channels per 16-byte access: the half bodies of AttentionStudent(body_half=True)
+// and AttentionStudentStepsHalf).  The arithmetic is fp32 in both; Elem<T>::rnd marks the points at which PyTorch-CPU's half
+// ops round to fp16 (pinned by tests/test_student_half_host.py and tests/test_steps_half_host.py) and is the identity for
+// fp32, whose instantiations compute what they always did.
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int N = 4;
@@ -229,30 +230,42 @@ __global__ void __launch_bounds__(256) sigmoid_add_kernel(const T* att, int att_
 }
 
 // AttentionStudentSteps.forward, students.py:1012-1040: att = sigmoid(att [/ att_divisor]); stem_out * att
-// (broadcast over the channels); also emits att as the first NCHW output (N,1,H,W)
-__global__ void __launch_bounds__(256) gate_mul_kernel(const float* att, int att_ld, const float* x, int x_ld, float* y,
-                                                       int out_ld, int C, size_t pixels, float div, float* att_out) {
-  const int c4 = C >> 2;
+// (broadcast over the channels); also emits att as the first NCHW output (N,1,H,W), fp32 in both precisions; fp16 (the half
+// body of AttentionStudentStepsHalf; rounding points pinned by tests/test_steps_half_host.py) rounds the quotient, the sigmoid
+// and each product
+template <typename T>
+__global__ void __launch_bounds__(256) gate_mul_kernel(const T* att, int att_ld, const T* x, int x_ld, T* y, int out_ld, int C,
+                                                       size_t pixels, float div, float* att_out) {
+  constexpr int EN = Elem<T>::N;
+  const int c4 = C / EN;
   const size_t total = pixels * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t p = i / c4;
-    const int c = (int)(i - p * c4) * 4;
-    float l = att[p * att_ld];
-    if (div != 0.f) l = l / div;
-    const float a = 1.f / (1.f + expf(-l));
+    const int c = (int)(i - p * c4) * EN;
+    float l = (float)att[p * att_ld];
+    if (div != 0.f) l = Elem<T>::rnd(l / div);
+    const float a = Elem<T>::rnd(1.f / (1.f + expf(-l)));
     if (c == 0 && att_out) att_out[p] = a;
-    const float4 v = *reinterpret_cast<const float4*>(x + p * x_ld + c);
-    *reinterpret_cast<float4*>(y + p * out_ld + c) = make_float4(v.x * a, v.y * a, v.z * a, v.w * a);
+    Row<T> v = Row<T>::load(x + p * x_ld + c);
+#pragma unroll
+    for (int j = 0; j < EN; ++j) v.v[j] = Elem<T>::rnd(v.v[j] * a);
+    v.store(y + p * out_ld + c);
   }
 }
 
-// the second network input: (N,3,H,W) fp32 NCHW -> NHWC rows of 4 (r, g, b, 0)
-__global__ void __launch_bounds__(256) aux_pack_kernel(const float* a, float* y, int out_ld, int N, int H, int W) {
+// the second network input: (N,3,H,W) fp32 NCHW -> NHWC rows of 16 bytes: fp32 (r, g, b, 0); fp16 (r, g, b, 0, 0, 0, 0, 0), each
+// value rounded to nearest even (beyond the fp16 range: infinity), as alt.half()
+template <typename T>
+__global__ void __launch_bounds__(256) aux_pack_kernel(const float* a, T* y, int out_ld, int N, int H, int W) {
   const size_t plane = (size_t)H * W, total = (size_t)N * plane;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t n = i / plane, q = i - n * plane;
     const float* b = a + n * 3 * plane + q;
-    *reinterpret_cast<float4*>(y + i * out_ld) = make_float4(b[0], b[plane], b[2 * plane], 0.f);
+    Row<T> r;
+#pragma unroll
+    for (int j = 0; j < Elem<T>::N; ++j) r.v[j] = 0.f;
+    r.v[0] = Elem<T>::rnd(b[0]); r.v[1] = Elem<T>::rnd(b[plane]); r.v[2] = Elem<T>::rnd(b[2 * plane]);
+    r.store(y + i * out_ld);
   }
 }
 
@@ -277,14 +290,20 @@ __device__ __forceinline__ void axis_half_pixel(float scale, int n_in, int n_out
 // F.interpolate of that image alone derives from its size: the scale (the same correctly rounded float division as on the
 // host), the clamp at h_n - 1, the n_in == n_out shortcut.  Nothing is stored beyond image n's output extent.  !MIXED: the
 // kernel as it was, the scales from the host (an instantiation of its own, as conv_mfma_kernel's).
-template <bool MIXED>
-__global__ void __launch_bounds__(256) resize_nhwc_kernel(const float* x, int in_ld, int Hi, int Wi, float* y, int out_ld,
+// fp16 (16-byte pieces of 8 channels, !MIXED only): the same coordinates and weights, fp32 arithmetic on the fp16 values and ONE
+// rounding of the result.  The four taps are combined as PyTorch-CPU's kernel combines them - the weights multiplied first
+// (ly * lx, rounded), then v01 * w01, fma(v00, w00, .), fma(v10, w10, .), fma(v11, w11, .) - not with the three fmas of the
+// fp32 form: the two differ in the last fp32 bit at scales that are no fp32 numbers (33 -> 9), which an fp16 rounding next to
+// a tie turns into a whole fp16 step (pinned by tests/test_steps_half_host.py).  The fp32 form keeps its arithmetic.
+template <bool MIXED, typename T = float>
+__global__ void __launch_bounds__(256) resize_nhwc_kernel(const T* x, int in_ld, int Hi, int Wi, T* y, int out_ld,
                                                           int Ho, int Wo, int C, int N, float sy, float sx,
                                                           const int* ext_in, const int* ext_out) {
-  const int c4 = C >> 2;
+  constexpr int EN = Elem<T>::N;
+  const int c4 = C / EN;
   const size_t total = (size_t)N * Ho * Wo * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c = (int)(i % c4) * 4;
+    const int c = (int)(i % c4) * EN;
     size_t p = i / c4;
     const int ox = (int)(p % Wo);
     p /= Wo;
@@ -302,19 +321,25 @@ __global__ void __launch_bounds__(256) resize_nhwc_kernel(const float* x, int in
     float ly0, ly1, lx0, lx1;
     axis_half_pixel(sy, hi, ho, oy, &y0, &y1, &ly0, &ly1);
     axis_half_pixel(sx, wi, wo, ox, &x0, &x1, &lx0, &lx1);
-    const float* b = x + (size_t)n * Hi * Wi * in_ld + c;
-    const float4 v00 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * Wi + x0) * in_ld);
-    const float4 v01 = *reinterpret_cast<const float4*>(b + ((size_t)y0 * Wi + x1) * in_ld);
-    const float4 v10 = *reinterpret_cast<const float4*>(b + ((size_t)y1 * Wi + x0) * in_ld);
-    const float4 v11 = *reinterpret_cast<const float4*>(b + ((size_t)y1 * Wi + x1) * in_ld);
+    const T* b = x + (size_t)n * Hi * Wi * in_ld + c;
+    const Row<T> v00 = Row<T>::load(b + ((size_t)y0 * Wi + x0) * in_ld);
+    const Row<T> v01 = Row<T>::load(b + ((size_t)y0 * Wi + x1) * in_ld);
+    const Row<T> v10 = Row<T>::load(b + ((size_t)y1 * Wi + x0) * in_ld);
+    const Row<T> v11 = Row<T>::load(b + ((size_t)y1 * Wi + x1) * in_ld);
+    const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;      // (read by the fp16 form only)
     auto one = [&](float a00, float a01, float a10, float a11) {
-      const float t0 = __builtin_fmaf(a00, lx0, a01 * lx1);
-      const float t1 = __builtin_fmaf(a10, lx0, a11 * lx1);
-      return __builtin_fmaf(t0, ly0, t1 * ly1);
+      if constexpr (sizeof(T) == 2) {
+        return __builtin_fmaf(a11, w11, __builtin_fmaf(a10, w10, __builtin_fmaf(a00, w00, a01 * w01)));
+      } else {
+        const float t0 = __builtin_fmaf(a00, lx0, a01 * lx1);
+        const float t1 = __builtin_fmaf(a10, lx0, a11 * lx1);
+        return __builtin_fmaf(t0, ly0, t1 * ly1);
+      }
     };
-    *reinterpret_cast<float4*>(y + (((size_t)n * Ho + oy) * Wo + ox) * out_ld + c) =
-        make_float4(one(v00.x, v01.x, v10.x, v11.x), one(v00.y, v01.y, v10.y, v11.y), one(v00.z, v01.z, v10.z, v11.z),
-                    one(v00.w, v01.w, v10.w, v11.w));
+    Row<T> o;
+#pragma unroll
+    for (int j = 0; j < EN; ++j) o.v[j] = Elem<T>::rnd(one(v00.v[j], v01.v[j], v10.v[j], v11.v[j]));
+    o.store(y + (((size_t)n * Ho + oy) * Wo + ox) * out_ld + c);
   }
 }
 
@@ -478,20 +503,42 @@ int mask_outputs_launch(float* y0, int C0, int H0, int W0, const int* ext0, floa
   return RTPE_OK;
 }
 
-int gate_mul_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C, size_t pixels,
-                    float div, float* att_out, hipStream_t s) {
-  RTPE_REQUIRE(C % 4 == 0 && x_ld % 4 == 0 && out_ld % 4 == 0, "gate_mul: channel counts must be multiples of 4");
-  hipLaunchKernelGGL(gate_mul_kernel, dim3(grid_for(pixels * (C / 4))), dim3(256), 0, s, att, att_ld, x, x_ld, y, out_ld,
+template <typename T>
+static int gate_mul_launch_t(const T* att, int att_ld, const T* x, int x_ld, T* y, int out_ld, int C, size_t pixels, float div,
+                             float* att_out, hipStream_t s) {
+  constexpr int EN = Elem<T>::N;
+  RTPE_REQUIRE(C > 0 && C % EN == 0 && x_ld % EN == 0 && out_ld % EN == 0, "gate_mul: channel counts must be multiples of %d", EN);
+  hipLaunchKernelGGL(gate_mul_kernel<T>, dim3(grid_for(pixels * (C / EN))), dim3(256), 0, s, att, att_ld, x, x_ld, y, out_ld,
                      C, pixels, div, att_out);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }
 
-int aux_pack_launch(const float* aux_nchw, float* y, int out_ld, int N, int H, int W, hipStream_t s) {
-  RTPE_REQUIRE(aux_nchw != nullptr && out_ld >= 4 && out_ld % 4 == 0, "aux_pack: bad argument");
-  hipLaunchKernelGGL(aux_pack_kernel, dim3(grid_for((size_t)N * H * W)), dim3(256), 0, s, aux_nchw, y, out_ld, N, H, W);
+int gate_mul_launch(const float* att, int att_ld, const float* x, int x_ld, float* y, int out_ld, int C, size_t pixels,
+                    float div, float* att_out, hipStream_t s) {
+  return gate_mul_launch_t<float>(att, att_ld, x, x_ld, y, out_ld, C, pixels, div, att_out, s);
+}
+
+int gate_mul_launch(const _Float16* att, int att_ld, const _Float16* x, int x_ld, _Float16* y, int out_ld, int C, size_t pixels,
+                    float div, float* att_out, hipStream_t s) {
+  return gate_mul_launch_t<_Float16>(att, att_ld, x, x_ld, y, out_ld, C, pixels, div, att_out, s);
+}
+
+template <typename T>
+static int aux_pack_launch_t(const float* aux_nchw, T* y, int out_ld, int N, int H, int W, hipStream_t s) {
+  constexpr int EN = Elem<T>::N;
+  RTPE_REQUIRE(aux_nchw != nullptr && out_ld >= EN && out_ld % EN == 0, "aux_pack: bad argument");
+  hipLaunchKernelGGL(aux_pack_kernel<T>, dim3(grid_for((size_t)N * H * W)), dim3(256), 0, s, aux_nchw, y, out_ld, N, H, W);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
+}
+
+int aux_pack_launch(const float* aux_nchw, float* y, int out_ld, int N, int H, int W, hipStream_t s) {
+  return aux_pack_launch_t<float>(aux_nchw, y, out_ld, N, H, W, s);
+}
+
+int aux_pack_launch(const float* aux_nchw, _Float16* y, int out_ld, int N, int H, int W, hipStream_t s) {
+  return aux_pack_launch_t<_Float16>(aux_nchw, y, out_ld, N, H, W, s);
 }
 
 int resize_nhwc_launch(const float* x, int in_ld, int Hi, int Wi, float* y, int out_ld, int Ho, int Wo, int C, int N,
@@ -505,6 +552,18 @@ int resize_nhwc_launch(const float* x, int in_ld, int Hi, int Wi, float* y, int 
   else
     hipLaunchKernelGGL(resize_nhwc_kernel<false>, grid, dim3(256), 0, s, x, in_ld, Hi, Wi, y, out_ld, Ho, Wo, C, N,
                        (float)Hi / (float)Ho, (float)Wi / (float)Wo, ext_in, ext_out);
+  RTPE_HIP_CHECK(hipGetLastError());
+  return RTPE_OK;
+}
+
+// fp16: one size per batch only (the masked form of a mixed-size batch exists in fp32 alone)
+int resize_nhwc_launch(const _Float16* x, int in_ld, int Hi, int Wi, _Float16* y, int out_ld, int Ho, int Wo, int C, int N,
+                       hipStream_t s, const int* ext_in, const int* ext_out) {
+  RTPE_REQUIRE(C > 0 && C % 8 == 0 && in_ld % 8 == 0 && out_ld % 8 == 0, "resize: fp16 channel counts must be multiples of 8");
+  RTPE_REQUIRE(ext_in == nullptr && ext_out == nullptr, "resize: the fp16 form takes no mixed-size batch");
+  const dim3 grid(grid_for((size_t)N * Ho * Wo * (C / 8)));
+  hipLaunchKernelGGL((resize_nhwc_kernel<false, _Float16>), grid, dim3(256), 0, s, x, in_ld, Hi, Wi, y, out_ld, Ho, Wo, C, N,
+                     (float)Hi / (float)Ho, (float)Wi / (float)Wo, ext_in, ext_out);
   RTPE_HIP_CHECK(hipGetLastError());
   return RTPE_OK;
 }

@@ -610,6 +610,13 @@ class StudentPipeline(TeacherPipeline):
             return torch.is_tensor(batch[0]) and not torch.is_tensor(batch[1]) and batch[1] is not None
         return len(batch) == 2 and not torch.is_tensor(batch[1]) and batch[1] is not None
 
+    def _mixed_refusal(self):
+        """a model that has ``forward_mixed`` only to refuse it (``AttentionStudentStepsHalf``) says so through
+        ``refuse_mixed()``: raised here, before anything is packed or launched"""
+        refuse = getattr(self.model, "refuse_mixed", None)
+        if callable(refuse):
+            refuse()
+
     def _mixed_takes_alt(self):
         """the model's ``forward_mixed`` has the second input ``alt`` (``AttentionStudentSteps``) and does not run without it"""
         import inspect
@@ -648,6 +655,7 @@ class StudentPipeline(TeacherPipeline):
         who = "StudentPipeline"
         if not hasattr(self.model, "forward_mixed"):
             raise ValueError("StudentPipeline: the model has no forward_mixed")
+        self._mixed_refusal()
         if not self._is_mixed(batch):
             raise ValueError("StudentPipeline: a mixed-size batch is a list of (3, h, w) images or a (canvas, sizes) pair")
         if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
@@ -697,6 +705,7 @@ class StudentPipeline(TeacherPipeline):
             raise ValueError("StudentPipeline.call_mixed: decode must be 'batch' or 'per_image', not %r" % (decode,))
         if not hasattr(self.model, "forward_mixed"):
             raise ValueError("StudentPipeline.call_mixed: the model has no forward_mixed")
+        self._mixed_refusal()
         canvas, sizes = pack_mixed(images)
         if image_ids is not None and len(image_ids) != len(sizes):
             raise ValueError("StudentPipeline.call_mixed: %d image ids for %d images" % (len(image_ids), len(sizes)))

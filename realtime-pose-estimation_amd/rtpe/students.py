@@ -16,7 +16,8 @@ compiles the tree into one program (fp16 stem under the half wrapper, then a
 cast, then fp32 ops: dilated 3x3 convs on the exact-fp32 MFMA, SE gates, CAM
 combine, average pooling, sigmoid; with ``AttentionStudent(body_half=True)`` no
 cast and the fp16 forms of the same ops) and runs it on the HIP executor.  The quirks
-of the reference forward are reproduced as they are: ``att = hi + 2*up(lo)``
+of the reference forward are reproduced as they are (``AttentionStudentStepsHalf``: the Steps student with an fp16 body,
+a class of its own): ``att = hi + 2*up(lo)``
 (:739-742), ``det_hi`` used for both ``hi`` and ``mid`` and ``det_mid`` never
 called (:759-760).
 """
@@ -328,6 +329,7 @@ class AttentionStudentSteps(CompiledModule):
     CAMs + a 3x3 conv give the heat maps.  Same constructor, attribute names (state-dict keys) and
     ``forward(x, out_hw=None, alt=None, att_divisor=None) -> (att, det)`` as the reference; one compiled program per
     ``att_divisor`` value."""
+    _HALF_BODY = False          # AttentionStudentStepsHalf: the body's parameters are prepared as fp16 behind the stem
 
     def __init__(self, hhrnet_statedict_path=None, device="cuda", inplanes=48, num_heatmaps=17, ae_dims=1,
                  half_precision=True, init_fn=torch.nn.init.kaiming_normal_, trainable_stem=False, bn_momentum=0.1,
@@ -361,6 +363,9 @@ class AttentionStudentSteps(CompiledModule):
             torch.nn.Sequential(torch.nn.Identity(), self.stem)
         if hhrnet_statedict_path is not None:
             self.stem[1].load_pretrained(hhrnet_statedict_path, device, check=False)
+        if self._HALF_BODY:            # fp16 parameters, fp32 BatchNorm: fp32 checkpoints load into them as usual
+            for name in ("mid_stem", "alt_img_stem", "att_lo", "att_mid", "att_hi", "att_top", "steps"):
+                BN_convert_float(getattr(self, name).half())
         self._init_compiled()
         self.to(device)
         self.device = device
@@ -459,6 +464,78 @@ class AttentionStudentSteps(CompiledModule):
         kernels; any other size runs the general kernels on default launch shapes, is never autotuned, and its
         throughput has not been measured."""
         self._check_inference(x, "AttentionStudentSteps.forward")
+        if alt is None:
+            raise NotImplementedError("ATM alt is expected")        # reference :993-994
+        eng = self._engine(x.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))
+        att, det = eng.forward(x.float(), torch.float32, aux=alt.to(x.device).float())
+        return att, det
+
+
+class AttentionStudentStepsHalf(AttentionStudentSteps):
+    """``AttentionStudentSteps`` end to end in fp16: the reference module after ``BN_convert_float(model.half())`` with the
+    ``tofp32`` between stem and body removed and ``alt.half()`` as its second input - fp16 parameters, fp32 BatchNorm, fp16
+    activations, fp32 accumulation, the outputs fp16 values returned as fp32 ("Half body: the Steps
+    student").  Same positional arguments as ``AttentionStudentSteps`` without ``body_half``, same attribute names and
+    state-dict keys; fp32 checkpoints load as usual and the BatchNorms keep their fp32 values.  Every row, offset and concat
+    slice of the compiled program is a multiple of 8 channels, so ``inplanes`` must be one."""
+    _HALF_BODY = True
+
+    def __init__(self, hhrnet_statedict_path=None, device="cuda", inplanes=48, num_heatmaps=17, ae_dims=1,
+                 half_precision=True, init_fn=torch.nn.init.kaiming_normal_, trainable_stem=False, bn_momentum=0.1):
+        if not half_precision:
+            raise ValueError("rtpe: AttentionStudentStepsHalf needs half_precision=True (the half body reads the fp16 output of "
+                             "the half-wrapped stem)")
+        if inplanes <= 0 or inplanes % 8:
+            raise ValueError("rtpe: AttentionStudentStepsHalf needs inplanes to be a multiple of 8 (16-byte rows of fp16 "
+                             "channels), got %r" % (inplanes,))
+        super().__init__(hhrnet_statedict_path, device, inplanes, num_heatmaps, ae_dims, True, init_fn, trainable_stem,
+                         bn_momentum)
+
+    def compile_program(self, variant=None):
+        """the forward of reference :966-1040 as one fp16 program (``variant`` = ("att_divisor", value)): no cast, no fp32 op
+        behind the stem; ``cat1`` = [mid stem (P) | alt at 1/4 resolution (3) | 0 x 5], ``cat2`` = [gated (P + 3) | 0 x 5 |
+        alt stem (P)]"""
+        att_divisor = variant[1] if variant else None
+        P = self.inplanes
+        b = ProgramBuilder(f32=False, any_size=True, granule=8)
+        t = self.stem[1].emit(b)
+        m = self.mid_stem
+        t = b.conv(t, m[0], m[1], relu=True)
+        cat1 = b.new_tensor(P + 8, b.tensors[t][1])
+        b.conv(t, m[3], m[4], relu=True, out=(cat1, 0), cout_store=P)
+        alt = b.aux_input(half=True)                            # alt.half(): rows of (r, g, b, 0 x 5)
+        b.resize(alt, cat1, P, 8, half=True)                    # (the five pad channels: interpolated zeros)
+        a = self.alt_img_stem
+        u = b.conv(alt, a[0], a[1], relu=True)                  # 5x5 stride 2, 8 (3 used) -> 50 stored as 56
+        hi = self.att_hi[0].emit(b, cat1)
+        mid = self.att_mid[1].emit(b, b.avgpool(cat1))
+        lo = self.att_lo[1].emit(b, b.avgpool(mid))
+        att = b.fuse([(hi, 0), (lo, 2), (lo, 2)], relu=False)
+        logits = b.conv(att, self.att_top[0], None)
+        cat2 = b.new_tensor(2 * P + 8, b.tensors[cat1][1])
+        b.gate_mul(logits, cat1, cat2, P + 8, att_divisor, out_flag=nat.F_OUT_PREDS, half=True)
+        b.conv(u, a[3], a[4], relu=True, out=(cat2, P + 8), cout_store=P)      # 5x5 stride 2, 56 (50 used) -> P
+        col_map = list(range(P + 3)) + list(range(P + 8, 2 * P + 8))
+        x = self.steps[0].emit(b, cat2, col_map=col_map)
+        x = self.steps[1].emit(b, x)
+        x = self.steps[2].emit(b, x)
+        b.conv(x, self.steps[3], None, out_flag=nat.F_OUT_REFINED, nhwc=False)
+        return b.finish()
+
+    def forward_mixed(self, canvas, sizes, alt=None, att_divisor=None):
+        """not built: refused before any GPU work"""
+        self.refuse_mixed()
+
+    def refuse_mixed(self):
+        """what ``StudentPipeline.call_mixed`` / ``stream_mixed`` ask before they pack a batch"""
+        raise NotImplementedError("rtpe: AttentionStudentStepsHalf.forward_mixed: the masked fp16 forms of the second-input ops "
+                                  "(aux pack, resize, gate_mul) do not exist yet; run a mixed-size batch on "
+                                  "AttentionStudentSteps, or this model one size per batch")
+
+    def forward(self, x, out_hw=None, alt=None, att_divisor=None):
+        """as ``AttentionStudentSteps.forward``; ``alt`` stays an fp32 (N,3,H,W) tensor and is rounded to fp16 as it is
+        packed; both outputs are fp32 tensors that hold fp16 values"""
+        self._check_inference(x, "AttentionStudentStepsHalf.forward")
         if alt is None:
             raise NotImplementedError("ATM alt is expected")        # reference :993-994
         eng = self._engine(x.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))

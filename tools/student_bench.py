@@ -20,6 +20,12 @@ against the fp32 body, same weights, same input, one process - the forward alone
 warmed up (autotuned), order A B B A; written to profiles/student_half_bench.json.
 
     python tools/student_bench.py --body-half [--steps 12] [--warmup 3] [--repeats 4]
+
+``--steps-half`` is the same protocol for the Steps student: ``AttentionStudentSteps`` (fp32 body) against
+``AttentionStudentStepsHalf``, inplanes 48 and 80, seeded W1 weights, ``alt`` a seeded image of a LAB image's span,
+``att_divisor`` 20; one JSON line per inplanes, written to profiles/steps_half_bench.json.
+
+    python tools/student_bench.py --steps-half [--steps 12] [--warmup 3] [--repeats 4]
 """
 import argparse
 import json
@@ -46,13 +52,17 @@ def main():
     ap.add_argument("--decode-reps", type=int, default=5)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--body-half", action="store_true", help="the half body against the fp32 body (see the module docstring)")
+    ap.add_argument("--steps-half", action="store_true", help="AttentionStudentStepsHalf against AttentionStudentSteps (see the module docstring)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "student_half_bench.json" if args.body_half else "student_pipeline_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "steps_half_bench.json" if args.steps_half else
+                                "student_half_bench.json" if args.body_half else "student_pipeline_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("student_bench: no GPU (the students run on the HIP path only)")
     import __graft_entry__ as entry
     entry.build()
+    if args.steps_half:
+        return steps_half_bench(args)
     from oracle import synth
     from rtpe import _native as nat
     from rtpe import engine
@@ -256,6 +266,89 @@ def body_half_bench(args, stu32, x, shapes, new_parser, expand_args, count):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def steps_half_bench(args):
+    """``AttentionStudentSteps`` against ``AttentionStudentStepsHalf``: forward alone and forward + ``parse_lowres`` on the
+    expanded maps, both models warmed up (autotuned through the aux entry), A B B A; one line per inplanes"""
+    from oracle import synth
+    from rtpe import _native as nat
+    from rtpe import engine
+    from rtpe.students import AttentionStudentSteps, AttentionStudentStepsHalf
+    from rtpe.third_party.group import HeatmapParser
+    torch.set_num_threads(nat.host_threads(8))
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    B, S, J, div = args.batch, args.size, engine.NUM_HEATMAPS, 20.0
+    x = torch.randn(B, 3, S, S, device=dev, generator=torch.Generator(device=dev).manual_seed(1234))
+    alt = torch.rand(B, 3, S, S, device=dev, generator=torch.Generator(device=dev).manual_seed(1235)) * 130.0 - 30.0
+    lines = []
+    for P, shapes_file in ((48, "student_steps_shapes.json"), (80, "student_steps80_shapes.json")):
+        with open(os.path.join(ROOT, "tests", "golden", shapes_file)) as f:
+            shapes = {k: tuple(v) for k, v in json.load(f)["shapes"].items()}
+        sd = synth.make_state_dict(shapes, 4, "W1")
+        models = {}
+        for key, cls in (("fp32_body", AttentionStudentSteps), ("half_body", AttentionStudentStepsHalf)):
+            m = cls(None, "cpu", P, 17, 1, True, None, False).eval()
+            m.load_state_dict(sd, strict=True)
+            models[key] = m.to(dev)
+        parsers = {k: HeatmapParser(num_joints=J, **engine.HM_PARSER_PARAMS) for k in models}
+
+        def forward(key):
+            def run(steps):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                with torch.no_grad():
+                    for _ in range(steps):
+                        models[key](x, alt=alt, att_divisor=div)
+                torch.cuda.synchronize(dev)
+                return B * steps / (time.perf_counter() - t0)
+            return run
+
+        def step(key):
+            def run(steps):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                with torch.no_grad():
+                    for _ in range(steps):
+                        att, det = models[key](x, alt=alt, att_divisor=div)
+                        det = det.float()
+                        parsers[key].parse_lowres(det[:, :J].contiguous(), det[:, J:J + 1].expand(-1, J, -1, -1).contiguous(), (S, S))
+                torch.cuda.synchronize(dev)
+                return B * steps / (time.perf_counter() - t0)
+            return run
+
+        paths = {"forward_fp32_body": forward("fp32_body"), "forward_half_body": forward("half_body"),
+                 "step_fp32_body": step("fp32_body"), "step_half_body": step("half_body")}
+        with torch.no_grad():
+            a32, d32 = models["fp32_body"](x, alt=alt, att_divisor=div)
+            a16, d16 = models["half_body"](x, alt=alt, att_divisor=div)
+        diff = {"att_max": float((a32 - a16).abs().max()), "det_max": float((d32 - d16).abs().max()),
+                "det_mean": float((d32 - d16).abs().mean()), "det_range": float(d32.abs().max())}
+        for run in paths.values():
+            run(args.warmup)
+        runs = {key: [] for key in paths}
+        order = list(paths)
+        for r in range(args.repeats):
+            for key in (order if r % 2 == 0 else order[::-1]):
+                runs[key].append(round(paths[key](args.steps), 1))
+        out = {"metric": "steps_half_body_throughput", "model": "AttentionStudentSteps(inplanes=%d)" % P, "weights": "W1",
+               "att_divisor": div, "batch": B, "size": S, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
+               "device": torch.cuda.get_device_name(dev), "order": "A B B A over " + ", ".join(order),
+               "half_vs_fp32_outputs": diff}
+        for key in order:
+            out[key] = {"img_s": round(float(np.median(runs[key])), 1), "img_s_runs": runs[key],
+                        "img_s_spread": round(max(runs[key]) - min(runs[key]), 1),
+                        "ms_per_step": round(1e3 * B / float(np.median(runs[key])), 3)}
+        out["forward_half_over_fp32"] = round(out["forward_half_body"]["img_s"] / out["forward_fp32_body"]["img_s"], 4)
+        out["step_half_over_fp32"] = round(out["step_half_body"]["img_s"] / out["step_fp32_body"]["img_s"], 4)
+        lines.append(json.dumps(out))
+        print(lines[-1])
+        del models
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
