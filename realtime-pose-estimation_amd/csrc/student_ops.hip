@@ -4,6 +4,7 @@
 // channel counts are multiples of 4 (16-byte rows pieces).  avgpool, se, cam_combine, sigmoid_add, gate_mul, aux_pack and
 // resize also have an fp16 form (the half bodies: 16-byte pieces of 8 channels).
 #include "rtpe_common.h"
+#include "alt_colour.h"
 
 namespace rtpe {
 
@@ -352,34 +353,7 @@ __global__ void __launch_bounds__(256) rgb_to_alt_kernel(const float* src, float
     float* o = dst + n * 3 * plane + q;
     const float r = b[0], g = b[plane], bl = b[2 * plane];
     float o0, o1, o2;
-    if (mode == 0) {
-      // sRGB -> linear -> XYZ (D65) -> Lab; constants of skimage.color.colorconv
-      auto lin = [](float v) { return v > 0.04045f ? powf((v + 0.055f) / 1.055f, 2.4f) : v / 12.92f; };
-      const float R = lin(r), G = lin(g), B = lin(bl);
-      float X = 0.412453f * R + 0.357580f * G + 0.180423f * B;
-      float Y = 0.212671f * R + 0.715160f * G + 0.072169f * B;
-      float Z = 0.019334f * R + 0.119193f * G + 0.950227f * B;
-      X /= 0.95047f; Z /= 1.08883f;
-      auto f = [](float t) { return t > 0.008856f ? cbrtf(t) : 7.787f * t + 16.f / 116.f; };
-      const float fx = f(X), fy = f(Y), fz = f(Z);
-      o0 = 116.f * fy - 16.f;
-      o1 = 500.f * (fx - fy);
-      o2 = 200.f * (fy - fz);
-    } else {
-      const float mx = fmaxf(r, fmaxf(g, bl)), mn = fminf(r, fminf(g, bl));
-      const float d = mx - mn;
-      float h = 0.f;
-      if (d != 0.f) {
-        if (mx == r) h = (g - bl) / d;
-        else if (mx == g) h = 2.f + (bl - r) / d;
-        else h = 4.f + (r - g) / d;
-        h = h / 6.f;
-        h = h - floorf(h);                                   // (h / 6) % 1
-      }
-      o0 = h;
-      o1 = d == 0.f ? 0.f : d / mx;
-      o2 = mx;
-    }
+    rgb_to_alt_pixel(r, g, bl, mode, o0, o1, o2);        // alt_colour.h: frames_kernel calls the same function
     o[0] = o0; o[plane] = o1; o[2 * plane] = o2;
   }
 }

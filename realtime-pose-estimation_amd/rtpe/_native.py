@@ -278,6 +278,17 @@ _SIGS_MIXAUX = {
     "rtpe_hrnet_forward_mixed_aux": (c_int32, _m[:3] + [c_void_p] + _m[3:]),
 }
 EXPORTS_MIXAUX = tuple(_SIGS_MIXAUX)    # that of include/rtpe_hip_mixed_aux.h, likewise
+# the students' front end (include/rtpe_hip_frames.h): the job table of N uint8 frames (host) and the one launch that
+# writes the image canvas and the LAB / HSV canvas
+FRAMES_ALT_MODES = {None: -1, "LAB": 0, "HSV": 1}
+_SIGS_FRAMES = {
+    "rtpe_frames_table_bytes": (c_int32, [c_int32, POINTER(c_size_t)]),
+    "rtpe_frames_table_fill": (c_int32, [POINTER(c_uint64), POINTER(c_int32), c_int32, c_int32, c_int32, c_void_p,
+                                         c_size_t]),
+    "rtpe_frames_to_canvases": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float),
+                                          c_int32, c_void_p, c_void_p, c_void_p]),
+}
+EXPORTS_FRAMES = tuple(_SIGS_FRAMES)    # those of include/rtpe_hip_frames.h, likewise
 _lib = None
 
 
@@ -303,7 +314,7 @@ def lib():
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
                 list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()) + \
-                list(_SIGS_MIXAUX.items()):
+                list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

@@ -625,18 +625,25 @@ class StudentPipeline(TeacherPipeline):
         except (TypeError, ValueError):
             return False
 
+    def _mixed_alt_given(self, given, who):
+        """a model that needs the second input and gets none, or gets one and has no use for it: ValueError;
+        otherwise ``given``"""
+        if not given:
+            if self._mixed_takes_alt():
+                raise ValueError("%s: the model needs the second input of every image (alt: a list of (3, h_n, w_n) tensors "
+                                 "of the images' sizes)" % who)
+            return False
+        if not self._mixed_takes_alt():
+            raise ValueError("%s: the model's forward_mixed takes no second input (alt)" % who)
+        return True
+
     def _mixed_alt(self, alts, sizes, canvas_hw, who):
         """the ``alt`` images of a mixed batch, checked against the images' sizes on the host and packed into a canvas of
         the first one's size; None stays None.  A model that needs them and gets none, or gets them and has no use for
         them, is refused here, before the forward."""
         from .students import pack_mixed
-        if alts is None:
-            if self._mixed_takes_alt():
-                raise ValueError("%s: the model needs the second input of every image (alt: a list of (3, h_n, w_n) tensors "
-                                 "of the images' sizes)" % who)
+        if not self._mixed_alt_given(alts is not None, who):
             return None
-        if not self._mixed_takes_alt():
-            raise ValueError("%s: the model's forward_mixed takes no second input (alt)" % who)
         alts = list(alts)
         if len(alts) != len(sizes):
             raise ValueError("%s: %d alt images for %d images" % (who, len(alts), len(sizes)))
@@ -700,16 +707,26 @@ class StudentPipeline(TeacherPipeline):
         of its region - N region copies, N sets of launches and 2N host waits in series; the same bits, kept for A/B
         measurements and as a fallback.  With ``image_ids`` (N ints; ``match_on="device"``): one (1, RECORD_FLOATS) record
         tensor per image (``"batch"``: views of the one record tensor of the batch)."""
-        from .students import pack_mixed, unpack_mixed
-        if decode not in ("batch", "per_image"):
-            raise ValueError("StudentPipeline.call_mixed: decode must be 'batch' or 'per_image', not %r" % (decode,))
-        if not hasattr(self.model, "forward_mixed"):
-            raise ValueError("StudentPipeline.call_mixed: the model has no forward_mixed")
-        self._mixed_refusal()
+        from .students import pack_mixed
+        who = "StudentPipeline.call_mixed"
+        self._mixed_call_checks(decode, who)
         canvas, sizes = pack_mixed(images)
         if image_ids is not None and len(image_ids) != len(sizes):
-            raise ValueError("StudentPipeline.call_mixed: %d image ids for %d images" % (len(image_ids), len(sizes)))
-        alt = self._mixed_alt(alt, sizes, tuple(canvas.shape[2:]), "StudentPipeline.call_mixed")
+            raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
+        alt = self._mixed_alt(alt, sizes, tuple(canvas.shape[2:]), who)
+        return self._mixed_call(canvas, sizes, alt, image_ids, decode)
+
+    def _mixed_call_checks(self, decode, who):
+        """what ``call_mixed`` and ``call_frames`` refuse before anything is packed"""
+        if decode not in ("batch", "per_image"):
+            raise ValueError("%s: decode must be 'batch' or 'per_image', not %r" % (who, decode))
+        if not hasattr(self.model, "forward_mixed"):
+            raise ValueError("%s: the model has no forward_mixed" % who)
+        self._mixed_refusal()
+
+    def _mixed_call(self, canvas, sizes, alt, image_ids, decode):
+        """``call_mixed`` from its canvases on: ONE ``forward_mixed``, then the decode"""
+        from .students import unpack_mixed
         batch = (canvas, sizes) if alt is None else (canvas, sizes, alt)
         if decode == "batch":
             records = None if image_ids is None else self.parser.check_records(len(sizes), (image_ids, None))
@@ -740,6 +757,40 @@ class StudentPipeline(TeacherPipeline):
         return self._stream_loop(batches, lambda k, x: self._mixed_begin(x), self._mixed_forwards, self._mixed_topk,
                                  on_forward, decode_stream, in_flight, exclusive, records)
 
+    @torch.no_grad()
+    def call_frames(self, frames, alt_colorspace=None, image_ids=None, decode="batch"):
+        """``call_mixed`` from uint8 frames: ``frames`` a sequence of (h_n, w_n, 3) uint8 ndarrays, CPU tensors or device
+        tensors of any sizes >= 32 (or one (N, H, W, 3) array) -> per image what ``call_mixed`` returns for
+        ``Normalize(to_tensor(frame))`` [and, for a model with a second input, ``alt_colorspace`` "LAB" / "HSV": the
+        image in that colour space].  ``students.pack_frames`` - one upload and one launch write both canvases - then
+        exactly what ``call_mixed`` does from its canvases on; ``image_ids`` and ``decode`` as there."""
+        from .students import pack_frames
+        who = "StudentPipeline.call_frames"
+        self._mixed_call_checks(decode, who)
+        self._mixed_alt_given(alt_colorspace is not None, who)
+        canvas, sizes, alt = pack_frames(frames, alt_colorspace, device=self.device)
+        if image_ids is not None and len(image_ids) != len(sizes):
+            raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
+        return self._mixed_call(canvas, sizes, alt, image_ids, decode)
+
+    def stream_frames(self, batches, alt_colorspace=None, **stream_mixed_kwargs):
+        """``stream_mixed`` over batches of uint8 frames (each what ``call_frames`` takes; ``frame_batches`` cuts them):
+        every batch goes through ``students.pack_frames`` on the caller's stream when the loop reaches it and enters
+        ``stream_mixed`` as ``(canvas, sizes[, alt_canvas])``.  ``alt_colorspace`` as ``call_frames``; every other
+        argument is ``stream_mixed``'s."""
+        from .students import pack_frames
+        who = "StudentPipeline.stream_frames"
+        if not hasattr(self.model, "forward_mixed"):
+            raise ValueError("%s: the model has no forward_mixed" % who)
+        self._mixed_refusal()
+        self._mixed_alt_given(alt_colorspace is not None, who)
+
+        def packed():
+            for frames in batches:
+                canvas, sizes, alt = pack_frames(frames, alt_colorspace, device=self.device)
+                yield (canvas, sizes) if alt is None else (canvas, sizes, alt)
+        return self.stream_mixed(packed(), **stream_mixed_kwargs)
+
     @staticmethod
     def mixed_batches(images, batch_size=32, alts=None):
         """cut a list of images of different sizes into batches for ``call_mixed`` / ``stream_mixed``: the images
@@ -749,22 +800,36 @@ class StudentPipeline(TeacherPipeline):
         per-image list that batch b gave - the results of all images in the caller's order.  With ``alts`` (one per image,
         for a model with a second input) they are cut in the same order and ``batches[b]`` is the pair ``(images, alts)``
         of batch b, as ``stream_mixed`` takes it.  Pure host function."""
+        return StudentPipeline._area_batches(images, batch_size, alts, lambda s: int(s[-2]) * int(s[-1]),
+                                             "StudentPipeline.mixed_batches")
+
+    @staticmethod
+    def frame_batches(frames, batch_size=32):
+        """``mixed_batches`` for (h, w, 3) frames, what ``call_frames`` / ``stream_frames`` take: sorted by ``h * w``
+        (``mixed_batches`` would read ``w * 3`` from such a shape), ties keep the caller's order, then runs of
+        ``batch_size``.  ``frames``: anything with an (h, w, 3) ``.shape``.  Returns ``(batches, restore)`` as
+        ``mixed_batches`` does.  Pure host function."""
+        return StudentPipeline._area_batches(frames, batch_size, None, lambda s: int(s[0]) * int(s[1]),
+                                             "StudentPipeline.frame_batches")
+
+    @staticmethod
+    def _area_batches(images, batch_size, alts, area, who):
         images = list(images)
         batch_size = int(batch_size)
         if batch_size < 1:
-            raise ValueError("StudentPipeline.mixed_batches: batch_size must be at least 1, not %d" % batch_size)
+            raise ValueError("%s: batch_size must be at least 1, not %d" % (who, batch_size))
         if alts is not None:
             alts = list(alts)
             if len(alts) != len(images):
-                raise ValueError("StudentPipeline.mixed_batches: %d alts for %d images" % (len(alts), len(images)))
-        order = sorted(range(len(images)), key=lambda i: int(images[i].shape[-2]) * int(images[i].shape[-1]))
+                raise ValueError("%s: %d alts for %d images" % (who, len(alts), len(images)))
+        order = sorted(range(len(images)), key=lambda i: area(images[i].shape))
         cuts = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
 
         def restore(results):
             results = list(results)
             if len(results) != len(cuts) or any(len(r) != len(c) for r, c in zip(results, cuts)):
-                raise ValueError("StudentPipeline.mixed_batches: the results %s do not go with batches of %s images"
-                                 % ([len(r) for r in results], [len(c) for c in cuts]))
+                raise ValueError("%s: the results %s do not go with batches of %s images"
+                                 % (who, [len(r) for r in results], [len(c) for c in cuts]))
             out = [None] * len(images)
             for r, c in zip(results, cuts):
                 for i, v in zip(c, r):

@@ -26,6 +26,7 @@ import torch
 from . import _native as nat
 from .third_party.fp16_utils.fp16util import BN_convert_float, network_to_half, tofp16
 from .third_party.pose_higher_hrnet import BN_MOMENTUM, Bottleneck, CompiledModule, ProgramBuilder, check_mixed_sizes
+from .third_party.transforms import IMAGENET_MEAN, IMAGENET_STD
 
 
 def pack_mixed(images, canvas_hw=None):
@@ -54,6 +55,132 @@ def pack_mixed(images, canvas_hw=None):
     for n, (im, (h, w)) in enumerate(zip(images, sizes)):
         canvas[n, :, :h, :w] = im
     return canvas, sizes
+
+
+def _frame_kind(frame, n):
+    """"device" / "host" for an (h, w, 3) uint8 tensor on a GPU / ndarray or CPU tensor; TypeError for anything else"""
+    import numpy as np
+    is_t = torch.is_tensor(frame)
+    if not (is_t or isinstance(frame, np.ndarray)) or frame.dtype != (torch.uint8 if is_t else np.uint8) \
+            or len(frame.shape) != 3 or frame.shape[2] != 3:
+        raise TypeError("pack_frames: frame %d: expected an (h, w, 3) uint8 ndarray or tensor, got %s %s"
+                        % (n, getattr(frame, "dtype", type(frame).__name__), tuple(getattr(frame, "shape", ()))))
+    return "device" if is_t and frame.is_cuda else "host"
+
+
+def pack_frames(frames, alt_colorspace=None, canvas_hw=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
+                out=None):
+    """uint8 frames of different sizes, as a camera or an image decoder delivers them -> the canvases of
+    ``forward_mixed(canvas, sizes, alt=alt_canvas)``, in one upload and ONE kernel launch (``rtpe_frames_to_canvases``).
+
+    ``frames``: a sequence of (h_n, w_n, 3) uint8 ndarrays, CPU tensors or tensors on the device, freely mixed, or one
+    (N, H, W, 3) uint8 array / tensor (the same-size case); h_n, w_n >= 32.  Returns ``(canvas, sizes, alt_canvas)``:
+    ``canvas`` (N, 3, Hc, Wc) float32 with ``Normalize(mean, std)(to_tensor(frame n))`` at ``[n, :, :h_n, :w_n]`` - the
+    bits of ``(float32(f) / 255 - mean) / std`` in numpy float32 or torch on the CPU, two true divisions - and
+    ``alt_canvas`` the same region in ``alt_colorspace`` ("LAB" / "HSV": the bits of ``dataloaders.rgb2lab`` /
+    ``rgb2hsv`` of ``to_tensor(frame n)``), or None without one.  Every other element of both canvases is exactly 0.0,
+    written by the same kernel: the canvases are ``torch.empty``.  ``Hc, Wc`` are the largest h_n and w_n, or
+    ``canvas_hw`` (not smaller than those); ``sizes = [(h_n, w_n)]``.
+
+    Host frames are copied behind the job table into one pinned staging slot (the ring of
+    ``transforms.warp_normalize_batch``) and go up with one asynchronous copy; frames on the device are read where they
+    lie (any row stride >= 3 * w; made contiguous only if the pixel stride is not 3).  Everything is queued on the
+    current stream.  ``out=(canvas, alt_canvas)`` (``alt_canvas`` None without a colour space): caller-owned contiguous
+    float32 tensors of the right shape on the device, written instead of fresh ones - for a loop that reuses its buffers.
+
+    Frames of ONE size give a plain (N, 3, H, W) batch: ``pipe(canvas, alt=alt_canvas)`` and every student class,
+    ``AttentionStudentStepsHalf`` included, take it as they take any tensor.
+
+    Refused before any GPU work: no frames, a side below 32, a canvas too small, an ``out`` of the wrong shape, dtype or
+    device (ValueError); a frame that is not (h, w, 3) uint8 (TypeError); an unknown colour space (NotImplementedError)."""
+    import ctypes
+    import numpy as np
+    from .third_party.transforms import _staging_slot
+    if (torch.is_tensor(frames) or isinstance(frames, np.ndarray)) and len(frames.shape) == 4:
+        frames = [frames[n] for n in range(frames.shape[0])]
+    elif torch.is_tensor(frames) or isinstance(frames, np.ndarray):
+        raise TypeError("pack_frames: a sequence of (h, w, 3) uint8 frames or one (N, H, W, 3) array, not one %s array"
+                        % (tuple(frames.shape),))
+    frames = list(frames)
+    if not frames:
+        raise ValueError("pack_frames: no frames")
+    if alt_colorspace not in nat.FRAMES_ALT_MODES:
+        raise NotImplementedError("Unknown color space {}".format(alt_colorspace))
+    mode = nat.FRAMES_ALT_MODES[alt_colorspace]
+    kinds = [_frame_kind(f, n) for n, f in enumerate(frames)]
+    N = len(frames)
+    sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
+    if canvas_hw is not None:
+        Hc, Wc = int(canvas_hw[0]), int(canvas_hw[1])
+    sizes = check_mixed_sizes(sizes, N, Hc, Wc)
+    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
+        raise ValueError("pack_frames: mean and std are three numbers each, std positive")
+    device = torch.device(device)
+    if out is not None:
+        if not isinstance(out, (list, tuple)) or len(out) != 2 or (out[1] is None) != (mode < 0):
+            raise ValueError("pack_frames: out is (canvas, alt_canvas), alt_canvas None exactly when there is no "
+                             "colour space")
+        for name, t in (("canvas", out[0]), ("alt_canvas", out[1])):
+            if t is None and name == "alt_canvas":
+                continue
+            if not torch.is_tensor(t) or tuple(t.shape) != (N, 3, Hc, Wc) or t.dtype != torch.float32 or \
+                    not t.is_contiguous() or t.device.type != device.type or \
+                    (device.index is not None and t.device.index != device.index) or t.device != out[0].device:
+                raise ValueError("pack_frames: out: %s must be a contiguous float32 tensor %s on %s, got %s"
+                                 % (name, (N, 3, Hc, Wc), device, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device)
+                                    if torch.is_tensor(t) else type(t).__name__))
+        device = out[0].device
+    if device.type != "cuda":
+        raise RuntimeError("rtpe: pack_frames runs on the MI355X HIP path only and got device %s (there is "
+                           "deliberately no CPU fallback in the product path)" % (device,))
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    L = nat.lib()
+    tb = ctypes.c_size_t()
+    nat.check(L.rtpe_frames_table_bytes(N, ctypes.byref(tb)))
+    # the staging buffer: [job table | host frame 0 | host frame 1 | ...], frames packed (row stride 3 * w)
+    offsets, total = {}, (tb.value + 255) // 256 * 256
+    for n, (h, w) in enumerate(sizes):
+        if kinds[n] == "host":
+            offsets[n] = total
+            total += (h * w * 3 + 15) // 16 * 16
+    with torch.cuda.device(device):
+        slot = _staging_slot(device, total)
+        host = slot["buf"]
+        host_np = host.numpy()
+        stage = torch.empty(total, dtype=torch.uint8, device=device)
+        canvas, alt = out if out is not None else (
+            torch.empty((N, 3, Hc, Wc), dtype=torch.float32, device=device),
+            torch.empty((N, 3, Hc, Wc), dtype=torch.float32, device=device) if mode >= 0 else None)
+        src_addr = (ctypes.c_uint64 * N)()
+        src_hws = (ctypes.c_int32 * (3 * N))()
+        keep = []           # device frames and their contiguous copies: alive until the launch is in the stream
+        for n, (f, (h, w)) in enumerate(zip(frames, sizes)):
+            if kinds[n] == "host":
+                np.copyto(host_np[offsets[n]:offsets[n] + h * w * 3].reshape(h, w, 3),
+                          f.numpy() if torch.is_tensor(f) else f)
+                src_addr[n], stride = stage.data_ptr() + offsets[n], 3 * w
+            else:
+                if f.device != device:
+                    raise RuntimeError("rtpe: pack_frames: frame %d is on %s, the canvases are on %s" % (n, f.device, device))
+                if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * w:
+                    f = f.contiguous()
+                keep.append(f)
+                src_addr[n], stride = f.data_ptr(), f.stride(0)
+            src_hws[3 * n], src_hws[3 * n + 1], src_hws[3 * n + 2] = h, w, stride
+        nat.check(L.rtpe_frames_table_fill(src_addr, src_hws, N, Hc, Wc, ctypes.c_void_p(host.data_ptr()), tb.value))
+        # (all frames on the device: only the table goes up)
+        stage.copy_(host[:total], non_blocking=True)
+        if slot["event"] is None:
+            slot["event"] = torch.cuda.Event()
+        slot["event"].record(torch.cuda.current_stream(device))
+        nat.check(L.rtpe_frames_to_canvases(
+            ctypes.c_void_p(stage.data_ptr()), N, Hc, Wc, (ctypes.c_float * 3)(*[float(v) for v in mean]),
+            (ctypes.c_float * 3)(*[float(v) for v in std]), mode, ctypes.c_void_p(canvas.data_ptr()),
+            ctypes.c_void_p(alt.data_ptr()) if alt is not None else None, nat.stream_ptr(device)))
+        del keep
+    return canvas, sizes, alt
 
 
 def unpack_mixed(att, det, sizes):
