@@ -610,12 +610,19 @@ class StudentPipeline(TeacherPipeline):
             return torch.is_tensor(batch[0]) and not torch.is_tensor(batch[1]) and batch[1] is not None
         return len(batch) == 2 and not torch.is_tensor(batch[1]) and batch[1] is not None
 
-    def _mixed_refusal(self):
-        """a model that has ``forward_mixed`` only to refuse it (``AttentionStudentStepsHalf``) says so through
-        ``refuse_mixed()``: raised here, before anything is packed or launched"""
+    def _mixed_model(self, who):
+        """the one check of the model before a mixed batch is packed or launched: it has ``forward_mixed``, and not only to
+        refuse it - a model that does (``AttentionStudentStepsHalf``) says so through ``refuse_mixed()``, raised here"""
+        if not hasattr(self.model, "forward_mixed"):
+            raise ValueError("%s: the model has no forward_mixed" % who)
         refuse = getattr(self.model, "refuse_mixed", None)
         if callable(refuse):
             refuse()
+
+    @staticmethod
+    def _mixed_batch(canvas, sizes, alt):
+        """a mixed batch as ``forward_mixed`` and ``on_forward`` take it: ``(canvas, sizes[, alt_canvas])``"""
+        return (canvas, sizes) if alt is None else (canvas, sizes, alt)
 
     def _mixed_takes_alt(self):
         """the model's ``forward_mixed`` has the second input ``alt`` (``AttentionStudentSteps``) and does not run without it"""
@@ -660,31 +667,24 @@ class StudentPipeline(TeacherPipeline):
         from .students import pack_mixed
         from .third_party.pose_higher_hrnet import check_mixed_sizes
         who = "StudentPipeline"
-        if not hasattr(self.model, "forward_mixed"):
-            raise ValueError("StudentPipeline: the model has no forward_mixed")
-        self._mixed_refusal()
+        self._mixed_model(who)
         if not self._is_mixed(batch):
             raise ValueError("StudentPipeline: a mixed-size batch is a list of (3, h, w) images or a (canvas, sizes) pair")
-        if torch.is_tensor(batch[0]) and batch[0].dim() == 3:
-            canvas, sizes = pack_mixed(batch)
-            alt = self._mixed_alt(None, sizes, tuple(canvas.shape[2:]), who)
-        elif len(batch) == 2 and isinstance(batch[0], (list, tuple)):        # (images, alts)
-            canvas, sizes = pack_mixed(batch[0])
-            alt = self._mixed_alt(batch[1], sizes, tuple(canvas.shape[2:]), who)
+        one_list = torch.is_tensor(batch[0]) and batch[0].dim() == 3
+        if one_list or (len(batch) == 2 and isinstance(batch[0], (list, tuple))):        # images, or (images, alts)
+            images, alts = (batch, None) if one_list else batch
+            canvas, sizes = pack_mixed(images)
+            alt = self._mixed_alt(alts, sizes, tuple(canvas.shape[2:]), who)
         else:
-            canvas, sizes = batch[0], batch[1]
+            canvas, sizes, alt = batch[0], batch[1], batch[2] if len(batch) == 3 else None
             if not torch.is_tensor(canvas) or canvas.dim() != 4 or canvas.shape[1] != 3:
                 raise ValueError("StudentPipeline: the canvas of a mixed batch is (N,3,Hc,Wc)")
             sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])
-            alt = batch[2] if len(batch) == 3 else None
-            if alt is None:
-                self._mixed_alt(None, sizes, None, who)
-            elif not self._mixed_takes_alt():
-                raise ValueError("StudentPipeline: the model's forward_mixed takes no second input (alt)")
-            elif not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape) or alt.device != canvas.device:
+            if self._mixed_alt_given(alt is not None, who) and (
+                    not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape) or alt.device != canvas.device):
                 raise ValueError("StudentPipeline: the alt canvas of a mixed batch is a tensor like the first canvas, %s on %s"
                                  % (tuple(canvas.shape), canvas.device))
-        return ((canvas, sizes) if alt is None else (canvas, sizes, alt)), sizes
+        return self._mixed_batch(canvas, sizes, alt), sizes
 
     def _mixed_forwards(self, k, batch, on_forward):
         att, det = self._att_det(on_forward(k, batch) if on_forward is not None else self.model.forward_mixed(*batch))
@@ -711,23 +711,22 @@ class StudentPipeline(TeacherPipeline):
         who = "StudentPipeline.call_mixed"
         self._mixed_call_checks(decode, who)
         canvas, sizes = pack_mixed(images)
-        if image_ids is not None and len(image_ids) != len(sizes):
-            raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
-        alt = self._mixed_alt(alt, sizes, tuple(canvas.shape[2:]), who)
-        return self._mixed_call(canvas, sizes, alt, image_ids, decode)
+        return self._mixed_call(who, canvas, sizes, lambda: self._mixed_alt(alt, sizes, tuple(canvas.shape[2:]), who),
+                                image_ids, decode)
 
     def _mixed_call_checks(self, decode, who):
         """what ``call_mixed`` and ``call_frames`` refuse before anything is packed"""
         if decode not in ("batch", "per_image"):
             raise ValueError("%s: decode must be 'batch' or 'per_image', not %r" % (who, decode))
-        if not hasattr(self.model, "forward_mixed"):
-            raise ValueError("%s: the model has no forward_mixed" % who)
-        self._mixed_refusal()
+        self._mixed_model(who)
 
-    def _mixed_call(self, canvas, sizes, alt, image_ids, decode):
-        """``call_mixed`` from its canvases on: ONE ``forward_mixed``, then the decode"""
+    def _mixed_call(self, who, canvas, sizes, alt_canvas, image_ids, decode):
+        """``call_mixed`` from its first canvas on: the count of the image ids, the second canvas (``alt_canvas()``: asked
+        for behind that check, where ``call_mixed`` has always packed it), ONE ``forward_mixed``, then the decode"""
         from .students import unpack_mixed
-        batch = (canvas, sizes) if alt is None else (canvas, sizes, alt)
+        if image_ids is not None and len(image_ids) != len(sizes):
+            raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
+        batch = self._mixed_batch(canvas, sizes, alt_canvas())
         if decode == "batch":
             records = None if image_ids is None else self.parser.check_records(len(sizes), (image_ids, None))
             att, det = self._mixed_forwards(0, batch, None)
@@ -769,9 +768,7 @@ class StudentPipeline(TeacherPipeline):
         self._mixed_call_checks(decode, who)
         self._mixed_alt_given(alt_colorspace is not None, who)
         canvas, sizes, alt = pack_frames(frames, alt_colorspace, device=self.device)
-        if image_ids is not None and len(image_ids) != len(sizes):
-            raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
-        return self._mixed_call(canvas, sizes, alt, image_ids, decode)
+        return self._mixed_call(who, canvas, sizes, lambda: alt, image_ids, decode)
 
     def stream_frames(self, batches, alt_colorspace=None, **stream_mixed_kwargs):
         """``stream_mixed`` over batches of uint8 frames (each what ``call_frames`` takes; ``frame_batches`` cuts them):
@@ -780,15 +777,12 @@ class StudentPipeline(TeacherPipeline):
         argument is ``stream_mixed``'s."""
         from .students import pack_frames
         who = "StudentPipeline.stream_frames"
-        if not hasattr(self.model, "forward_mixed"):
-            raise ValueError("%s: the model has no forward_mixed" % who)
-        self._mixed_refusal()
+        self._mixed_model(who)
         self._mixed_alt_given(alt_colorspace is not None, who)
 
         def packed():
             for frames in batches:
-                canvas, sizes, alt = pack_frames(frames, alt_colorspace, device=self.device)
-                yield (canvas, sizes) if alt is None else (canvas, sizes, alt)
+                yield self._mixed_batch(*pack_frames(frames, alt_colorspace, device=self.device))
         return self.stream_mixed(packed(), **stream_mixed_kwargs)
 
     @staticmethod

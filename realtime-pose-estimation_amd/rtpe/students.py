@@ -29,6 +29,14 @@ from .third_party.pose_higher_hrnet import BN_MOMENTUM, Bottleneck, CompiledModu
 from .third_party.transforms import IMAGENET_MEAN, IMAGENET_STD
 
 
+def _canvas_hw(sizes, canvas_hw=None):
+    """(Hc, Wc) of the canvas of a batch of images of ``sizes``: the largest h_n and w_n, or ``canvas_hw`` as it is given
+    (whether it holds the images is for the caller to check, in its own words)"""
+    if canvas_hw is not None:
+        return int(canvas_hw[0]), int(canvas_hw[1])
+    return max(h for h, _ in sizes), max(w for _, w in sizes)
+
+
 def pack_mixed(images, canvas_hw=None):
     """images of different sizes -> one canvas for ``AttentionStudent.forward_mixed``.
 
@@ -44,12 +52,9 @@ def pack_mixed(images, canvas_hw=None):
         if im.device != images[0].device:
             raise ValueError("pack_mixed: images on different devices (%s and %s)" % (images[0].device, im.device))
     sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
-    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
-    if canvas_hw is not None:
-        ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
-        if ch < Hc or cw < Wc:
-            raise ValueError("pack_mixed: a %d x %d canvas does not hold images of up to %d x %d" % (ch, cw, Hc, Wc))
-        Hc, Wc = ch, cw
+    (Hc, Wc), (Hm, Wm) = _canvas_hw(sizes, canvas_hw), _canvas_hw(sizes)
+    if Hc < Hm or Wc < Wm:
+        raise ValueError("pack_mixed: a %d x %d canvas does not hold images of up to %d x %d" % (Hc, Wc, Hm, Wm))
     sizes = check_mixed_sizes(sizes, len(images), Hc, Wc)
     canvas = torch.zeros((len(images), 3, Hc, Wc), dtype=torch.float32, device=images[0].device)
     for n, (im, (h, w)) in enumerate(zip(images, sizes)):
@@ -110,9 +115,7 @@ def pack_frames(frames, alt_colorspace=None, canvas_hw=None, mean=IMAGENET_MEAN,
     kinds = [_frame_kind(f, n) for n, f in enumerate(frames)]
     N = len(frames)
     sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
-    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
-    if canvas_hw is not None:
-        Hc, Wc = int(canvas_hw[0]), int(canvas_hw[1])
+    Hc, Wc = _canvas_hw(sizes, canvas_hw)
     sizes = check_mixed_sizes(sizes, N, Hc, Wc)
     if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
         raise ValueError("pack_frames: mean and std are three numbers each, std positive")
@@ -216,8 +219,8 @@ class SELayer(torch.nn.Module):
                                       torch.nn.Linear(hidden_chans, in_chans, bias=True),
                                       torch.nn.Sigmoid())
 
-    def emit(self, b, x):
-        return b.se(x, self.fc[0], self.fc[2])
+    def emit(self, b, x, w1=None):
+        return b.se(x, self.fc[0], self.fc[2], w1=w1)
 
     def forward(self, x):
         raise RuntimeError("rtpe: SELayer runs only inside a compiled student program")
@@ -245,10 +248,17 @@ class ContextAwareModule(torch.nn.Module):
     def emit(self, b, x, col_map=None):
         """``col_map``: physical channel of x for every logical input channel (x may carry pad channels in the
         middle of a concat): the input-channel axis of every weight that reads x is re-indexed"""
-        if col_map is not None:
-            return self._emit_mapped(b, x, col_map)
-        res = b.conv(x, self.residual[0], self.residual[1], relu=True)
-        gate = self.se.emit(b, x)
+        phys = b.tensors[x][0] if col_map is not None else None         # (None: the builder takes the weights as they are)
+
+        def remap(w):                                   # (Co, C_logical[, k, k]) -> (Co, C_physical[, k, k])
+            if col_map is None:
+                return None
+            w = w.detach().float().cpu()
+            out = torch.zeros((w.shape[0], phys) + tuple(w.shape[2:]))
+            out[:, col_map] = w
+            return out
+        res = b.conv(x, self.residual[0], self.residual[1], relu=True, weight=remap(self.residual[0].weight), cin=phys)
+        gate = self.se.emit(b, x, w1=remap(self.se.fc[0].weight))
         # torch.cat of the dilated branches (:191) without a copy: every branch writes its
         # channels side by side; each slice is padded to the builder's granule (16 bytes: 4 fp32 or 8 fp16 channels)
         hc = self.hdcs[0][0].out_channels
@@ -256,33 +266,8 @@ class ContextAwareModule(torch.nn.Module):
         nd = len(self.hdcs)
         cat = b.new_tensor(hp * nd, b.tensors[x][1])
         for i, hdc in enumerate(self.hdcs):
-            b.conv(x, hdc[0], hdc[1], relu=True, out=(cat, hp * i), cout_store=hp)
-        w = self.hdc_top[0].weight.detach().cpu()                      # (C, hc*nd, 1, 1)
-        wp = torch.zeros((w.shape[0], hp * nd, 1, 1), dtype=w.dtype)
-        for i in range(nd):
-            wp[:, hp * i:hp * i + hc] = w[:, hc * i:hc * (i + 1)]
-        top = b.conv(cat, self.hdc_top[0], self.hdc_top[1], relu=True, weight=wp, cin=hp * nd)
-        return b.cam_combine(top, res, gate)
-
-    def _emit_mapped(self, b, x, col_map):
-        phys = b.tensors[x][0]
-
-        def remap(w):                                   # (Co, C_logical, k, k) -> (Co, C_physical, k, k)
-            w = w.detach().float().cpu()
-            out = torch.zeros((w.shape[0], phys) + tuple(w.shape[2:]))
-            out[:, col_map] = w
-            return out
-        res = b.conv(x, self.residual[0], self.residual[1], relu=True, weight=remap(self.residual[0].weight), cin=phys)
-        w1 = torch.zeros((self.se.fc[0].out_features, phys))
-        w1[:, col_map] = self.se.fc[0].weight.detach().float().cpu()
-        gate = b.se(x, self.se.fc[0], self.se.fc[2], w1=w1)
-        hc = self.hdcs[0][0].out_channels
-        hp = -(-hc // b.granule) * b.granule
-        nd = len(self.hdcs)
-        cat = b.new_tensor(hp * nd, b.tensors[x][1])
-        for i, hdc in enumerate(self.hdcs):
             b.conv(x, hdc[0], hdc[1], relu=True, out=(cat, hp * i), cout_store=hp, weight=remap(hdc[0].weight), cin=phys)
-        w = self.hdc_top[0].weight.detach().cpu()
+        w = self.hdc_top[0].weight.detach().cpu()                      # (C, hc*nd, 1, 1)
         wp = torch.zeros((w.shape[0], hp * nd, 1, 1), dtype=w.dtype)
         for i in range(nd):
             wp[:, hp * i:hp * i + hc] = w[:, hc * i:hc * (i + 1)]
@@ -334,7 +319,71 @@ def get_pretrained_stem(hhrnet_statedict_path, device="cuda", half_precision=Tru
     return stem
 
 
-class AttentionStudent(CompiledModule):
+def _mixed_canvases(who, canvas, sizes, alt=None):
+    """what every ``forward_mixed`` checks of its canvases before any GPU work: the canvas, [the ``alt`` canvas against
+    it,] then the sizes -> ``sizes`` as ``check_mixed_sizes`` returns them"""
+    if canvas.dim() != 4 or canvas.shape[1] != 3:
+        raise ValueError("%s: expected a canvas (N,3,Hc,Wc), got %s" % (who, tuple(canvas.shape)))
+    if alt is not None:
+        if not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape):
+            raise ValueError("%s: alt must be a canvas like the first, %s, got %s" %
+                             (who, tuple(canvas.shape), tuple(alt.shape) if torch.is_tensor(alt) else type(alt).__name__))
+        if alt.device != canvas.device:
+            raise ValueError("%s: the canvases are on different devices (%s and %s)" % (who, canvas.device, alt.device))
+    return check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])
+
+
+class _StudentTrunk(CompiledModule):
+    """what the student classes share: the trunk (the HigherHRNet stem, then ``mid_stem``) in front of a body of the class's
+    own, the steps of the constructor on either side of that body, and the loading of the bundled attention weights.  The
+    modules are registered in the reference's order - trunk, then body - which is the order of the state-dict keys and
+    the order in which ``init_fn`` draws."""
+
+    def _begin(self, inplanes, num_heatmaps, ae_dims, trainable_stem, bn_momentum):
+        """the attributes and the trunk; the class registers its body next"""
+        self.bn_momentum = bn_momentum
+        self.num_heatmaps, self.ae_dims = num_heatmaps, ae_dims
+        self.stem = StemHRNet()
+        self.stem_out_chans = self.stem.layer1[-1].bn3.num_features
+        self.trainable_stem = trainable_stem
+        self.inplanes = inplanes
+        mid = (self.stem_out_chans + inplanes) // 2
+        m1, m2 = _cbr(self.stem_out_chans, mid, 3, bn_momentum=bn_momentum), _cbr(mid, inplanes, 3, bn_momentum=bn_momentum)
+        self.mid_stem = torch.nn.Sequential(*m1, *m2)
+
+    def _finish(self, hhrnet_statedict_path, device, half_precision, init_fn, body_half):
+        """behind the body: the initialiser, the half wrapper and the pretrained weights of the stem, ``body_half``: every
+        module behind the stem in fp16, then the engines and the device"""
+        if init_fn is not None:
+            self.apply(lambda module: init_weights(module, init_fn, 0.0))
+        self.stem = network_to_half(self.stem) if half_precision else \
+            torch.nn.Sequential(torch.nn.Identity(), self.stem)
+        if hhrnet_statedict_path is not None:
+            self.stem[1].load_pretrained(hhrnet_statedict_path, device, check=False)
+        if body_half:                  # fp16 parameters, fp32 BatchNorm: fp32 checkpoints load into them as usual
+            for name, module in self.named_children():
+                if name != "stem":
+                    BN_convert_float(module.half())
+        self._init_compiled()
+        self.to(device)
+        self.device = device
+
+    def _pool_cam_body(self, chans, dilations, top_chans):
+        """reference :651-706 / :871-899: [AvgPool+CAM, AvgPool+CAM, CAM, 3x3 conv with bias]"""
+        pool = lambda: torch.nn.AvgPool2d(kernel_size=3, stride=2, padding=1, count_include_pad=False)
+        cam = lambda: ContextAwareModule(chans, hdc_dilations=dilations)
+        top = torch.nn.Sequential(torch.nn.Conv2d(chans, top_chans, kernel_size=3, stride=1, dilation=1, padding=1, bias=True))
+        return torch.nn.ModuleList([torch.nn.Sequential(pool(), cam()), torch.nn.Sequential(pool(), cam()),
+                                    torch.nn.Sequential(cam()), top])
+
+    def load_state_dicts(self, inpath):
+        """reference :708-722 / :950-964"""
+        for name in ("mid_stem", "att_lo", "att_mid", "att_hi", "att_top"):
+            getattr(self, name).load_state_dict(torch.load(inpath + name + ".statedict", map_location="cpu"))
+        self.invalidate()
+
+
+class AttentionStudent(_StudentTrunk):
     """reference :595-771"""
 
     def __init__(self, hhrnet_statedict_path=None, device="cuda", inplanes=48, num_heatmaps=17, ae_dims=1,
@@ -348,44 +397,10 @@ class AttentionStudent(CompiledModule):
                              "fp16 output of the half-wrapped stem)")
         super().__init__()
         self.body_half = bool(body_half)
-        self.bn_momentum = bn_momentum
-        self.num_heatmaps, self.ae_dims = num_heatmaps, ae_dims
-        self.stem = StemHRNet()
-        self.stem_out_chans = self.stem.layer1[-1].bn3.num_features
-        self.trainable_stem = trainable_stem
-        self.inplanes = inplanes
-        mid = (self.stem_out_chans + inplanes) // 2
-        m1, m2 = _cbr(self.stem_out_chans, mid, 3, bn_momentum=bn_momentum), _cbr(mid, inplanes, 3, bn_momentum=bn_momentum)
-        self.mid_stem = torch.nn.Sequential(*m1, *m2)
-        self.att_lo, self.att_mid, self.att_hi, self.att_top = self._body([1, 2, 3, 4, 5], 1)
-        self.det_lo, self.det_mid, self.det_hi, self.det_top = self._body([1, 2, 3, 4], num_heatmaps + ae_dims)
-        if init_fn is not None:
-            self.apply(lambda module: init_weights(module, init_fn, 0.0))
-        self.stem = network_to_half(self.stem) if half_precision else \
-            torch.nn.Sequential(torch.nn.Identity(), self.stem)
-        if hhrnet_statedict_path is not None:
-            self.stem[1].load_pretrained(hhrnet_statedict_path, device, check=False)
-        if self.body_half:             # fp16 parameters, fp32 BatchNorm: fp32 checkpoints load into them as usual
-            for name in ("mid_stem", "att_lo", "att_mid", "att_hi", "att_top", "det_lo", "det_mid", "det_hi", "det_top"):
-                BN_convert_float(getattr(self, name).half())
-        self._init_compiled()
-        self.to(device)
-        self.device = device
-
-    def _body(self, dilations, top_chans):
-        """reference :651-706: [AvgPool+CAM, AvgPool+CAM, CAM, 3x3 conv with bias]"""
-        pool = lambda: torch.nn.AvgPool2d(kernel_size=3, stride=2, padding=1, count_include_pad=False)
-        cam = lambda: ContextAwareModule(self.inplanes, hdc_dilations=dilations)
-        top = torch.nn.Sequential(torch.nn.Conv2d(self.inplanes, top_chans, kernel_size=3, stride=1,
-                                                  dilation=1, padding=1, bias=True))
-        return torch.nn.ModuleList([torch.nn.Sequential(pool(), cam()), torch.nn.Sequential(pool(), cam()),
-                                    torch.nn.Sequential(cam()), top])
-
-    def load_state_dicts(self, inpath):
-        """reference :708-722"""
-        for name in ("mid_stem", "att_lo", "att_mid", "att_hi", "att_top"):
-            getattr(self, name).load_state_dict(torch.load(inpath + name + ".statedict", map_location="cpu"))
-        self.invalidate()
+        self._begin(inplanes, num_heatmaps, ae_dims, trainable_stem, bn_momentum)
+        self.att_lo, self.att_mid, self.att_hi, self.att_top = self._pool_cam_body(inplanes, [1, 2, 3, 4, 5], 1)
+        self.det_lo, self.det_mid, self.det_hi, self.det_top = self._pool_cam_body(inplanes, [1, 2, 3, 4], num_heatmaps + ae_dims)
+        self._finish(hhrnet_statedict_path, device, half_precision, init_fn, self.body_half)
 
     def compile_program(self):
         """the forward of reference :724-771 as one program"""
@@ -441,15 +456,13 @@ class AttentionStudent(CompiledModule):
         Every kernel addresses by the canvas extents and masks by image n's own ("Mixed-size
         batches").  A mixed batch always runs the general kernels on default launch shapes and is never autotuned,
         whatever the canvas size."""
-        if canvas.dim() != 4 or canvas.shape[1] != 3:
-            raise ValueError("AttentionStudent.forward_mixed: expected a canvas (N,3,Hc,Wc), got %s" % (tuple(canvas.shape),))
-        sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])     # (before any GPU work)
+        sizes = _mixed_canvases("AttentionStudent.forward_mixed", canvas, sizes)     # (before any GPU work)
         self._check_inference(canvas, "AttentionStudent.forward_mixed")
         att, det = self._engine(canvas.device).forward_mixed(canvas.float(), sizes)
         return att, det
 
 
-class AttentionStudentSteps(CompiledModule):
+class AttentionStudentSteps(_StudentTrunk):
     """reference :786-1063: the student that ``distillation.py:137`` trains.  The stem features get the
     down-scaled ``alt`` image (the input in LAB or HSV, ``rtpe.dataloaders.rgb2lab``) concatenated, the attention head
     gates them (``stem_out * sigmoid(att)``), a second 5x5-stride-2 stem of the alt image is concatenated and three
@@ -467,44 +480,16 @@ class AttentionStudentSteps(CompiledModule):
         super().__init__()
         if inplanes % 4:
             raise NotImplementedError("rtpe: AttentionStudentSteps needs inplanes to be a multiple of 4 (16-byte rows)")
-        self.bn_momentum = bn_momentum
-        self.num_heatmaps, self.ae_dims = num_heatmaps, ae_dims
-        self.stem = StemHRNet()
-        self.stem_out_chans = self.stem.layer1[-1].bn3.num_features
-        self.trainable_stem = trainable_stem
-        self.inplanes = inplanes
-        mid = (self.stem_out_chans + inplanes) // 2
-        m1, m2 = _cbr(self.stem_out_chans, mid, 3, bn_momentum=bn_momentum), _cbr(mid, inplanes, 3, bn_momentum=bn_momentum)
-        self.mid_stem = torch.nn.Sequential(*m1, *m2)
+        self._begin(inplanes, num_heatmaps, ae_dims, trainable_stem, bn_momentum)
         self._alt_planes = 50
 
         def c5(cin, cout):
             return [torch.nn.Conv2d(cin, cout, kernel_size=5, stride=2, dilation=1, padding=2, bias=False),
                     torch.nn.BatchNorm2d(cout, momentum=bn_momentum), torch.nn.ReLU(inplace=True)]
         self.alt_img_stem = torch.nn.Sequential(*c5(3, self._alt_planes), *c5(self._alt_planes, inplanes))
-        self.att_lo, self.att_mid, self.att_hi, self.att_top = self._attention_body()
+        self.att_lo, self.att_mid, self.att_hi, self.att_top = self._pool_cam_body(inplanes + 3, [1, 2, 3, 4], 1)
         self.steps = self._detection_stage()
-        if init_fn is not None:
-            self.apply(lambda module: init_weights(module, init_fn, 0.0))
-        self.stem = network_to_half(self.stem) if half_precision else \
-            torch.nn.Sequential(torch.nn.Identity(), self.stem)
-        if hhrnet_statedict_path is not None:
-            self.stem[1].load_pretrained(hhrnet_statedict_path, device, check=False)
-        if self._HALF_BODY:            # fp16 parameters, fp32 BatchNorm: fp32 checkpoints load into them as usual
-            for name in ("mid_stem", "alt_img_stem", "att_lo", "att_mid", "att_hi", "att_top", "steps"):
-                BN_convert_float(getattr(self, name).half())
-        self._init_compiled()
-        self.to(device)
-        self.device = device
-
-    def _attention_body(self):
-        """reference :871-899"""
-        c = self.inplanes + 3
-        pool = lambda: torch.nn.AvgPool2d(kernel_size=3, stride=2, padding=1, count_include_pad=False)
-        cam = lambda: ContextAwareModule(c, hdc_dilations=[1, 2, 3, 4])
-        top = torch.nn.Sequential(torch.nn.Conv2d(c, 1, kernel_size=3, stride=1, dilation=1, padding=1, bias=True))
-        return torch.nn.ModuleList([torch.nn.Sequential(pool(), cam()), torch.nn.Sequential(pool(), cam()),
-                                    torch.nn.Sequential(cam()), top])
+        self._finish(hhrnet_statedict_path, device, half_precision, init_fn, self._HALF_BODY)
 
     def _detection_stage(self):
         """reference :901-948: three CAMs over [gated stem + alt (inplanes + 3) | alt stem (inplanes)], then 3x3"""
@@ -513,30 +498,29 @@ class AttentionStudentSteps(CompiledModule):
                                    torch.nn.Conv2d(c, self.num_heatmaps + self.ae_dims, kernel_size=3, stride=1,
                                                    dilation=1, padding=1, bias=True))
 
-    def load_state_dicts(self, inpath):
-        """reference :950-964"""
-        for name in ("mid_stem", "att_lo", "att_mid", "att_hi", "att_top"):
-            getattr(self, name).load_state_dict(torch.load(inpath + name + ".statedict", map_location="cpu"))
-        self.invalidate()
-
     def compile_program(self, variant=None):
-        """the forward of reference :966-1040 as one program (``variant`` = ("att_divisor", value))"""
+        """the forward of reference :966-1040 as one program (``variant`` = ("att_divisor", value)), for both bodies.  The
+        half body (``_HALF_BODY``): no cast and no fp32 op behind the stem, the fp16 forms of the second-input ops, and
+        every row and concat slice padded to 8 channels instead of 4 (``pad``: 16 bytes of the body's elements)"""
         att_divisor = variant[1] if variant else None
         half = isinstance(self.stem[0], tofp16)
+        body_half = self._HALF_BODY
         P = self.inplanes
-        b = ProgramBuilder(f32=not half, any_size=True)
+        b = ProgramBuilder(f32=not half, any_size=True, granule=8 if body_half else 4)
+        pad = b.granule
         t = self.stem[1].emit(b)
-        if half:
-            t = b.cast(t)
-        b.f32 = True
+        if half and not body_half:
+            t = b.cast(t)                                       # tofp32 of the wrapped stem
+        b.f32 = not body_half
         m = self.mid_stem
         t = b.conv(t, m[0], m[1], relu=True)
-        # torch.cat((stem_out, alt), 1) (:1002) without a copy: [mid stem (P) | alt at 1/4 resolution (3) | 0]
-        cat1 = b.new_tensor(P + 4, b.tensors[t][1])
+        # torch.cat((stem_out, alt), 1) (:1002) without a copy: [mid stem (P) | alt at 1/4 resolution (3) | 0 x (pad - 3)]
+        cat1 = b.new_tensor(P + pad, b.tensors[t][1])
         b.conv(t, m[3], m[4], relu=True, out=(cat1, 0), cout_store=P)
-        alt = b.aux_input()
-        b.resize(alt, cat1, P, 4)                               # F.interpolate(alt, (h, w), mode="bilinear"), :996-1000
-        # the second stem of the alt image (:984): two 5x5 stride-2 convs
+        alt = b.aux_input(half=body_half)                       # rows of (r, g, b, 0 x (pad - 3)); half: alt.half()
+        # F.interpolate(alt, (h, w), mode="bilinear"), :996-1000 (the pad channels: interpolated zeros)
+        b.resize(alt, cat1, P, pad, half=body_half)
+        # the second stem of the alt image (:984): two 5x5 stride-2 convs, pad (3 used) -> 50 stored as 56 -> P
         a = self.alt_img_stem
         u = b.conv(alt, a[0], a[1], relu=True)
         # attention head (:1004-1019): hi + up(lo) + up(lo), the reference's double use of lo reproduced
@@ -545,11 +529,12 @@ class AttentionStudentSteps(CompiledModule):
         lo = self.att_lo[1].emit(b, b.avgpool(mid))
         att = b.fuse([(hi, 0), (lo, 2), (lo, 2)], relu=False)
         logits = b.conv(att, self.att_top[0], None)
-        # stem_out * att, then torch.cat((stem_out, alt_stem_out), 1) (:1040-1042): [gated (P+3) | 0 | alt stem (P)]
-        cat2 = b.new_tensor(2 * P + 4, b.tensors[cat1][1])
-        b.gate_mul(logits, cat1, cat2, P + 4, att_divisor, out_flag=nat.F_OUT_PREDS)
-        b.conv(u, a[3], a[4], relu=True, out=(cat2, P + 4), cout_store=P)
-        col_map = list(range(P + 3)) + list(range(P + 4, 2 * P + 4))
+        # stem_out * att, then torch.cat((stem_out, alt_stem_out), 1) (:1040-1042):
+        # [gated (P + 3) | 0 x (pad - 3) | alt stem (P)]
+        cat2 = b.new_tensor(2 * P + pad, b.tensors[cat1][1])
+        b.gate_mul(logits, cat1, cat2, P + pad, att_divisor, out_flag=nat.F_OUT_PREDS, half=body_half)
+        b.conv(u, a[3], a[4], relu=True, out=(cat2, P + pad), cout_store=P)
+        col_map = list(range(P + 3)) + list(range(P + pad, 2 * P + pad))
         x = self.steps[0].emit(b, cat2, col_map=col_map)
         x = self.steps[1].emit(b, x)
         x = self.steps[2].emit(b, x)
@@ -571,14 +556,7 @@ class AttentionStudentSteps(CompiledModule):
         if alt is None:                   # (as forward's "alt is expected")
             raise NotImplementedError("rtpe: %s needs the second input: alt=, the canvas of the images in the alternative "
                                       "colour space (pack_mixed(alts, canvas_hw=canvas.shape[2:]))" % who)
-        if canvas.dim() != 4 or canvas.shape[1] != 3:
-            raise ValueError("%s: expected a canvas (N,3,Hc,Wc), got %s" % (who, tuple(canvas.shape)))
-        if not torch.is_tensor(alt) or tuple(alt.shape) != tuple(canvas.shape):
-            raise ValueError("%s: alt must be a canvas like the first, %s, got %s" %
-                             (who, tuple(canvas.shape), tuple(alt.shape) if torch.is_tensor(alt) else type(alt).__name__))
-        if alt.device != canvas.device:
-            raise ValueError("%s: the canvases are on different devices (%s and %s)" % (who, canvas.device, alt.device))
-        sizes = check_mixed_sizes(sizes, canvas.shape[0], canvas.shape[2], canvas.shape[3])     # (before any GPU work)
+        sizes = _mixed_canvases(who, canvas, sizes, alt)     # (before any GPU work)
         self._check_inference(canvas, who)
         eng = self._engine(canvas.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))
         att, det = eng.forward_mixed(canvas.float(), sizes, aux=alt.float())
@@ -589,8 +567,9 @@ class AttentionStudentSteps(CompiledModule):
         colour space -> (att (N,1,ceil(H/4),ceil(W/4)) = sigmoid mask, det (N,num_heatmaps+ae_dims,ceil(H/4),ceil(W/4))),
         both fp32.  Sizes, kernels and tuning: as for ``AttentionStudent.forward`` - multiples of 32 run the tuned fast
         kernels; any other size runs the general kernels on default launch shapes, is never autotuned, and its
-        throughput has not been measured."""
-        self._check_inference(x, "AttentionStudentSteps.forward")
+        throughput has not been measured.  ``AttentionStudentStepsHalf``: ``alt`` stays an fp32 tensor and is rounded to
+        fp16 as it is packed; both outputs are fp32 tensors that hold fp16 values."""
+        self._check_inference(x, type(self).__name__ + ".forward")
         if alt is None:
             raise NotImplementedError("ATM alt is expected")        # reference :993-994
         eng = self._engine(x.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))
@@ -618,37 +597,6 @@ class AttentionStudentStepsHalf(AttentionStudentSteps):
         super().__init__(hhrnet_statedict_path, device, inplanes, num_heatmaps, ae_dims, True, init_fn, trainable_stem,
                          bn_momentum)
 
-    def compile_program(self, variant=None):
-        """the forward of reference :966-1040 as one fp16 program (``variant`` = ("att_divisor", value)): no cast, no fp32 op
-        behind the stem; ``cat1`` = [mid stem (P) | alt at 1/4 resolution (3) | 0 x 5], ``cat2`` = [gated (P + 3) | 0 x 5 |
-        alt stem (P)]"""
-        att_divisor = variant[1] if variant else None
-        P = self.inplanes
-        b = ProgramBuilder(f32=False, any_size=True, granule=8)
-        t = self.stem[1].emit(b)
-        m = self.mid_stem
-        t = b.conv(t, m[0], m[1], relu=True)
-        cat1 = b.new_tensor(P + 8, b.tensors[t][1])
-        b.conv(t, m[3], m[4], relu=True, out=(cat1, 0), cout_store=P)
-        alt = b.aux_input(half=True)                            # alt.half(): rows of (r, g, b, 0 x 5)
-        b.resize(alt, cat1, P, 8, half=True)                    # (the five pad channels: interpolated zeros)
-        a = self.alt_img_stem
-        u = b.conv(alt, a[0], a[1], relu=True)                  # 5x5 stride 2, 8 (3 used) -> 50 stored as 56
-        hi = self.att_hi[0].emit(b, cat1)
-        mid = self.att_mid[1].emit(b, b.avgpool(cat1))
-        lo = self.att_lo[1].emit(b, b.avgpool(mid))
-        att = b.fuse([(hi, 0), (lo, 2), (lo, 2)], relu=False)
-        logits = b.conv(att, self.att_top[0], None)
-        cat2 = b.new_tensor(2 * P + 8, b.tensors[cat1][1])
-        b.gate_mul(logits, cat1, cat2, P + 8, att_divisor, out_flag=nat.F_OUT_PREDS, half=True)
-        b.conv(u, a[3], a[4], relu=True, out=(cat2, P + 8), cout_store=P)      # 5x5 stride 2, 56 (50 used) -> P
-        col_map = list(range(P + 3)) + list(range(P + 8, 2 * P + 8))
-        x = self.steps[0].emit(b, cat2, col_map=col_map)
-        x = self.steps[1].emit(b, x)
-        x = self.steps[2].emit(b, x)
-        b.conv(x, self.steps[3], None, out_flag=nat.F_OUT_REFINED, nhwc=False)
-        return b.finish()
-
     def forward_mixed(self, canvas, sizes, alt=None, att_divisor=None):
         """not built: refused before any GPU work"""
         self.refuse_mixed()
@@ -658,13 +606,3 @@ class AttentionStudentStepsHalf(AttentionStudentSteps):
         raise NotImplementedError("rtpe: AttentionStudentStepsHalf.forward_mixed: the masked fp16 forms of the second-input ops "
                                   "(aux pack, resize, gate_mul) do not exist yet; run a mixed-size batch on "
                                   "AttentionStudentSteps, or this model one size per batch")
-
-    def forward(self, x, out_hw=None, alt=None, att_divisor=None):
-        """as ``AttentionStudentSteps.forward``; ``alt`` stays an fp32 (N,3,H,W) tensor and is rounded to fp16 as it is
-        packed; both outputs are fp32 tensors that hold fp16 values"""
-        self._check_inference(x, "AttentionStudentStepsHalf.forward")
-        if alt is None:
-            raise NotImplementedError("ATM alt is expected")        # reference :993-994
-        eng = self._engine(x.device, ("att_divisor", None if att_divisor is None else float(att_divisor)))
-        att, det = eng.forward(x.float(), torch.float32, aux=alt.to(x.device).float())
-        return att, det

@@ -258,7 +258,7 @@ def _se_program(C, hid, in_ld, zero_cols, ds, wx, bx, w1, b1, w2, b2, w_res, b_r
     net = Net(f32=True)
     src = net.chain(ds)[-1]
     x = net.tensor(src, in_ld, wx, bx)
-    if zero_cols:                                # the re-indexed form of ContextAwareModule._emit_mapped
+    if zero_cols:                                # the re-indexed form of ContextAwareModule.emit(col_map=...)
         gate = net.b.se(x, net.linear(torch.zeros(hid, C - len(zero_cols), dtype=D), b1), net.linear(w2, b2), w1=w1.float())
     else:
         gate = net.b.se(x, net.linear(w1, b1), net.linear(w2, b2))

@@ -371,7 +371,7 @@ def _same_bits(a, b):
 def test_the_programs_emit_what_the_tables_cover():
     e = emitted()
     assert len(e.avgpool) >= 4 and len(e.se) >= 6
-    assert any(z for _, _, _, z in e.se), "the re-indexed w1 of _emit_mapped is gone"
+    assert any(z for _, _, _, z in e.se), "the re-indexed w1 of emit(col_map=...) is gone"
     assert all(c == ld == out for c, ld, out in e.cast), "a cast with ld > C: add it to the cast cases"
     assert all(c <= 512 and hid <= 128 for c, hid, _, _ in e.se)
 
