@@ -719,5 +719,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_trace.h"
 #include "rtpe_hip_mixed_aux.h"
 #include "rtpe_hip_frames.h"
+#include "rtpe_hip_oks.h"
 
 #endif /* RTPE_HIP_H */

@@ -289,6 +289,16 @@ _SIGS_FRAMES = {
                                           c_int32, c_void_p, c_void_p, c_void_p]),
 }
 EXPORTS_FRAMES = tuple(_SIGS_FRAMES)    # those of include/rtpe_hip_frames.h, likewise
+# COCO keypoint scoring of the records (include/rtpe_hip_oks.h): the sizes of the result table and the scratch, and the
+# one launch that ranks, computes OKS and matches per record
+OKS_GT_ROW, OKS_MAX_DETS, OKS_MAX_RANGES, OKS_LDS_DOUBLES = 64, 64, 16, 512
+_SIGS_OKS = {
+    "rtpe_oks_eval_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
+    "rtpe_oks_eval": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_size_t,
+                                c_void_p]),
+}
+EXPORTS_OKS = tuple(_SIGS_OKS)          # those of include/rtpe_hip_oks.h, likewise
 _lib = None
 
 
@@ -314,7 +324,7 @@ def lib():
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
                 list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()) + \
-                list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()):
+                list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()) + list(_SIGS_OKS.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()
