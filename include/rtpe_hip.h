@@ -653,7 +653,8 @@ int rtpe_match_by_tag_batch(const float* tag_k, const int32_t* ind_k, const floa
  * image, those of an image in insertion order; person_img[i] = image of row i (ascending); counts[n] = people of image
  * n; *total = their sum.  Rows beyond *total are not written.  cap >= N*J*K (every candidate founds at most one
  * person).  Limits: K <= 64, 1 <= max_num_people <= 64, J <= 32, D <= 32 and an LDS need (a function of J, K, D,
- * max_num_people) of at most 64 KiB - beyond them RTPE_E_INVALID, never another matcher.  Asynchronous on `stream`;
+ * max_num_people) of at most 96 KiB (J = 17, K = 30, max_num_people = 30, D = 32 need 85,440 bytes) - beyond them
+ * RTPE_E_INVALID, never another matcher.  Asynchronous on `stream`;
  * scratch: rtpe_match_by_tag_dev_scratch_bytes(N, J, K, D) bytes of device memory. */
 int rtpe_match_by_tag_dev_scratch_bytes(int32_t N, int32_t J, int32_t K, int32_t D, size_t* bytes);
 int rtpe_match_by_tag_dev(const float* tag_k, const int32_t* ind_k, const float* val_k,

@@ -24,6 +24,10 @@ What is in here
   that prove the ties are there; with ``decode_ref``'s stable top-k the
   yardstick for the order among equal values, which the reference's
   ``torch.topk`` leaves undefined.
+* ``tagdims`` - decode inputs for every tag dimension and for refine's rare
+  branches (tags on the rounding boundary of each float order, more than 16
+  and more than 512 people, overflowing distances), with their counters;
+  ``decode_ref.FAULTS`` are the wrong orders they are built to expose.
 * ``schedule`` - happens-before checker for the trace of one executor forward
   (include/rtpe_hip_trace.h): what every launch reads and writes, from the
   descs and the route kinds; every conflicting pair must be ordered and no

@@ -104,6 +104,41 @@ def pairwise8_sum_f32(a):
     return s
 
 
+# Deliberately WRONG float orders (and other seeded faults) that ``refine`` / ``match_by_tag`` can be asked for: the
+# scenes of oracle/tagdims.py are built so that each one changes a result (tests/test_decode_dims_host.py).
+#   sequential     sum of squares left to right also for D >= 8 (refine; the float64 distances of the matcher)
+#   float64        refine's squares accumulated in float64
+#   fma            refine's squares contracted into the running sums (one rounding per step)
+#   no_tail        the elements behind the last full block of 8 dropped (D = 9, 17)
+#   pairwise_mean  a D > 1 mean tag summed pairwise (refine's mean; the matcher's centres)
+#   row_mean       refine's mean taken from the tag columns of the rows, not from the tag map
+#   no_fallback    D == 1: round(|d|) with no regard for an overflowing d * d
+FAULTS = ("sequential", "float64", "fma", "no_tail", "pairwise_mean", "row_mean", "no_fallback")
+
+
+def _sum_squares_fma(d):
+    """sum of d * d over the last axis in the reference's order (sequential below 8, numpy's pairwise walk from 8),
+    with every ``acc + d * d`` a fused multiply-add - what a compiler contracting the kernels' expressions would do"""
+    D = d.shape[-1]
+    col = [np.ascontiguousarray(d[..., k]) for k in range(D)]
+    if D < 8:
+        s = col[0] * col[0]
+        for k in range(1, D):
+            s = _fma32(col[k], col[k], s)
+        return s
+    r = [col[k] * col[k] for k in range(8)]
+    i = 8
+    while i + 8 <= D:
+        for k in range(8):
+            r[k] = _fma32(col[i + k], col[i + k], r[k])
+        i += 8
+    s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    while i < D:
+        s = _fma32(col[i], col[i], s)
+        i += 1
+    return s
+
+
 # --------------------------------------------------------------------------- #
 # HeatmapParser
 # --------------------------------------------------------------------------- #
@@ -155,8 +190,8 @@ class HeatmapParserRef:
         val = np.take_along_axis(flat, ind, 1)
         return torch.from_numpy(val.reshape(N, J, K)), torch.from_numpy(ind.reshape(N, J, K))
 
-    def match(self, tag_k, loc_k, val_k):
-        return [match_by_tag(t, l, v, self.params) for t, l, v in zip(tag_k, loc_k, val_k)]
+    def match(self, tag_k, loc_k, val_k, fault=None):
+        return [match_by_tag(t, l, v, self.params, fault) for t, l, v in zip(tag_k, loc_k, val_k)]
 
     def adjust(self, ans, det):
         """group.py:181-200 quarter-pixel shift towards the larger neighbour;
@@ -179,48 +214,69 @@ class HeatmapParserRef:
         return ans
 
     @staticmethod
-    def refine_mean(tag, kp):
-        """group.py:214-222: the float32 mean tag of a person's detected joints.  tag (J,h,w,D), kp (J,3+D)"""
+    def refine_mean(tag, kp, fault=None):
+        """group.py:214-222: the float32 mean tag of a person's detected joints, read from the tag MAP at
+        ``(int(y), int(x))`` of the rows.  tag (J,h,w,D), kp (J,3+D).  ``fault`` (see ``FAULTS``): "row_mean" takes
+        the tags from columns 3.. of the rows instead, "pairwise_mean" sums them pairwise also for D > 1."""
         J, D = tag.shape[0], tag.shape[3]
-        seen = [tag[j, int(kp[j, 1]), int(kp[j, 0])] for j in range(J) if kp[j, 2] > 0]
+        if fault == "row_mean":
+            seen = [kp[j, 3:] for j in range(J) if kp[j, 2] > 0]
+        else:
+            seen = [tag[j, int(kp[j, 1]), int(kp[j, 0])] for j in range(J) if kp[j, 2] > 0]
         seen = np.asarray(seen, f32)                       # (n, D)
-        if D == 1:
-            return np.array([pairwise8_sum_f32(seen[:, 0]) / f32(len(seen))], f32)
+        if D == 1 or fault == "pairwise_mean":
+            return np.array([pairwise8_sum_f32(seen[:, d]) / f32(len(seen)) for d in range(D)], f32)
         s = np.zeros(D, f32)
         for t in seen:
             s = (s + t).astype(f32)
         return (s / f32(len(seen))).astype(f32)
 
     @staticmethod
-    def refine_score(det_j, tag_j, mean):
+    def refine_score(det_j, tag_j, mean, fault=None):
         """group.py:229-232: the map whose first maximum refine takes, heat value minus the rounded tag distance.
-        det_j (h,w), tag_j (h,w,D), mean (D,)"""
+        det_j (h,w), tag_j (h,w,D), mean (D,).  ``fault``: one of the wrong summation orders of ``FAULTS``."""
         D = tag_j.shape[2]
-        d = tag_j - mean[None, None, :]
-        sq = d * d
-        if D < 8:
-            ss = sq[..., 0].copy()
-            for k in range(1, D):
-                ss = ss + sq[..., k]
-        else:
-            ss = sq.sum(axis=2)                            # numpy pairwise, as the reference
-        return det_j - np.rint(np.sqrt(ss))                # np.round == half-to-even
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = tag_j - mean[None, None, :]
+            if fault == "no_fallback" and D == 1:          # round(|d|): equal to the reference unless d * d overflows
+                return det_j - np.rint(np.abs(d[..., 0]))
+            if fault == "float64":
+                ss = np.zeros(d.shape[:2], np.float64)
+                for k in range(D):
+                    ss = ss + d[..., k].astype(np.float64) ** 2
+                return det_j - np.rint(np.sqrt(ss))
+            if fault == "fma":
+                return det_j - np.rint(np.sqrt(_sum_squares_fma(d)))
+            sq = d * d
+            if fault == "no_tail" and D >= 8:
+                sq = np.ascontiguousarray(sq[..., :D // 8 * 8])
+                D = sq.shape[2]
+            if D < 8 or fault == "sequential":
+                ss = sq[..., 0].copy()
+                for k in range(1, D):
+                    ss = ss + sq[..., k]
+            else:
+                ss = sq.sum(axis=2)                        # numpy pairwise, as the reference
+            return det_j - np.rint(np.sqrt(ss))            # np.round == half-to-even
 
-    def refine(self, det, tag, kp):
+    def refine(self, det, tag, kp, fault=None, means=None):
         """group.py:202-264 for one person.  det (J,h,w) f32, tag (J,h,w,D) f32,
-        kp (J,3+D) f32 (modified in place and returned)."""
+        kp (J,3+D) f32 (modified in place and returned).  ``fault``: see ``FAULTS``; ``means``: per joint the mean
+        tag to use instead of the person's own (the seeded slot mix-up of oracle/tagdims.py)."""
         if tag.ndim == 3:
             tag = tag[..., None]
         J, h, w = det.shape
-        mean = self.refine_mean(tag, kp)
+        mean = self.refine_mean(tag, kp, fault)
         for j in range(J):
-            score = self.refine_score(det[j], tag[j], mean)
+            if kp[j, 2] != 0:                              # only undetected joints are filled: nothing to decide here
+                continue
+            score = self.refine_score(det[j], tag[j], mean if means is None else means[j], fault)
             flat = int(np.argmax(score))                   # first maximum
             y, x = divmod(flat, w)
             val = det[j, y, x]
             fx = x + 0.5 + (0.25 if det[j, y, min(x + 1, w - 1)] > det[j, y, max(x - 1, 0)] else -0.25)
             fy = y + 0.5 + (0.25 if det[j, min(y + 1, h - 1), x] > det[j, max(y - 1, 0), x] else -0.25)
-            if val > 0 and kp[j, 2] == 0:                  # fill only undetected joints
+            if val > 0:
                 kp[j, 0], kp[j, 1], kp[j, 2] = fx, fy, val
         return kp
 
@@ -243,9 +299,10 @@ class HeatmapParserRef:
         return ans, scores
 
 
-def match_by_tag(tag_k, loc_k, val_k, P):
+def match_by_tag(tag_k, loc_k, val_k, P, fault=None):
     """group.py:26-97 for one image.  tag_k (J,K,D) f32, loc_k (J,K,2) i64,
-    val_k (J,K) f32 -> (P, J, 3+D) float32 (shape (0,) if nobody found)."""
+    val_k (J,K) f32 -> (P, J, 3+D) float32 (shape (0,) if nobody found).  ``fault``: "sequential" (the distances)
+    or "pairwise_mean" (the centres) of ``FAULTS``."""
     J, D = P.num_joints, tag_k.shape[2]
     people = OrderedDict()      # key = float value of tag[0] -> [rows (J,3+D) f64, [tags f32]]
 
@@ -272,9 +329,9 @@ def match_by_tag(tag_k, loc_k, val_k, P):
         keys = list(people)[:P.max_num_people]
         if P.ignore_too_much and len(keys) == P.max_num_people:
             continue
-        centres = np.stack([_mean_tags_f32(people[k][1]) for k in keys])     # (G, D) f32
+        centres = np.stack([_mean_tags_f32(people[k][1], fault == "pairwise_mean") for k in keys])     # (G, D) f32
         diff = rows[:, None, 3:] - centres[None].astype(np.float64)
-        dist = np.sqrt(_sum_last_f64(diff * diff))                           # (A, G)
+        dist = np.sqrt(_sum_last_f64(diff * diff, fault == "sequential"))                         # (A, G)
         cost = np.rint(dist) * 100 - rows[:, 2:3] if P.use_detection_val else dist.copy()
         A, G = dist.shape
         if A > G:
@@ -288,22 +345,22 @@ def match_by_tag(tag_k, loc_k, val_k, P):
     return np.array([v[0] for v in people.values()]).astype(f32)
 
 
-def _mean_tags_f32(tags):
-    """np.mean(list of (D,) f32, axis=0), group.py:55"""
+def _mean_tags_f32(tags, pairwise=False):
+    """np.mean(list of (D,) f32, axis=0), group.py:55 (``pairwise``: the seeded fault)"""
     a = np.asarray(tags, f32)
     n = f32(len(a))
-    if a.shape[1] == 1:
-        return np.array([pairwise8_sum_f32(a[:, 0]) / n], f32)
+    if a.shape[1] == 1 or pairwise:
+        return np.array([pairwise8_sum_f32(a[:, d]) / n for d in range(a.shape[1])], f32)
     s = np.zeros(a.shape[1], f32)
     for t in a:
         s = (s + t).astype(f32)
     return (s / n).astype(f32)
 
 
-def _sum_last_f64(a):
-    """add.reduce over the contiguous last axis, float64 (np.linalg.norm :62)"""
+def _sum_last_f64(a, sequential=False):
+    """add.reduce over the contiguous last axis, float64 (np.linalg.norm :62; ``sequential``: the seeded fault)"""
     D = a.shape[-1]
-    if D < 8:
+    if D < 8 or sequential:
         s = a[..., 0].copy()
         for k in range(1, D):
             s = s + a[..., k]

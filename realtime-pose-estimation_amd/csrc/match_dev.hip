@@ -25,7 +25,9 @@ typedef unsigned long long u64;
 constexpr int kMatchMaxN = 64;      // K and max_num_people: one lane per candidate / person / row / column
 constexpr int kMatchMaxJ = 32;      // joints: one bit each in a person's joint mask
 constexpr int kMatchMaxD = 32;      // tag width: one lane each when a tag is copied
-constexpr size_t kMatchMaxLds = 64 * 1024;
+// LDS a workgroup may ask for: 1.5 x the 64 KiB a kernel gets without asking, which holds the largest tag (D = 32) at the
+// decode's own sizes (J = 17, K = 30, max_num_people = 30: 85,440 bytes) and leaves 64 KiB of the CU's 160 to others
+constexpr size_t kMatchMaxLds = 96 * 1024;
 constexpr int kCompactPeople = 8;   // people per workgroup of the compaction kernel
 
 struct MatchArgs {
@@ -472,6 +474,10 @@ extern "C" int rtpe_match_by_tag_dev(const float* tag_k, const int32_t* ind_k, c
   a.counts_dev = reinterpret_cast<int32_t*>(a.jmask + (size_t)N * a.cap_img);
   a.nmax = K > max_num_people ? K : max_num_people;
   a.pitch = match_pitch(a.nmax);
+  static unsigned long long attr_mask = 0;                  // beyond 64 KiB a kernel has to be allowed its dynamic LDS
+  if (lds > 64 * 1024 && first_use_on_device(&attr_mask))
+    RTPE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(match_by_tag_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchMaxLds));
   hipLaunchKernelGGL(match_by_tag_kernel, dim3(N), dim3(64), lds, s, a);
   RTPE_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(match_compact_kernel, dim3((a.cap_img + kCompactPeople - 1) / kCompactPeople, N), dim3(256), 0, s,

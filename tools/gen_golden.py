@@ -24,6 +24,8 @@ What gets pinned:
   student_steps.npz   AttentionStudentSteps (students.py:786-1063) outputs + its state-dict contract
   decode_branches.npz tag_per_joint=False (the AGS branch of legacy/valid_ae1dim.py), adjust / refine switched off
   ref_selfspread.npz  the reference against itself (oneDNN off / 1 thread): the spread the GPU tests bound HIP by
+  decode_dims.npz     HeatmapParser / match_by_tag on the scenes of oracle/tagdims.py (--only decode_dims): tag
+                      dimensions 3..32, refine on the rounding boundary, > 512 people, overflow, foreign tag columns
 
 ``rtpe/third_party/group.py`` imports the PyPI package ``munkres`` (unpinned, not vendored).  It
 is not installed for this interpreter, but the pure-Python module of munkres 1.1.4 sits in the
@@ -32,7 +34,7 @@ sys.modules by path, so every decode fixture comes from the reference's own code
 real package.  Only if that file is missing a stand-in backed by oracle/hungarian_ref.py is used
 (with a loud note; it asserts scipy-optimal total cost on every call).
 
-    python tools/gen_golden.py [--only base,w0_640,w2,two_images,e2e,munkres,match]
+    python tools/gen_golden.py [--only base,w0_640,w2,two_images,e2e,munkres,match,decode_dims]
 """
 import json
 import os
@@ -339,6 +341,92 @@ def gen_decode_branches(ref):
     np.savez_compressed(os.path.join(OUT, "decode_branches.npz"), **out)
 
 
+def _write_npz(path, arrays):
+    """np.savez_compressed with a fixed time stamp on every member: the same results give the same bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def gen_decode_dims(real):
+    """The reference's HeatmapParser / match_by_tag on the scenes of oracle/tagdims.py (tag dimensions 3..32, refine
+    penalties on the rounding boundary, more than 16 and more than 512 people, overflowing distances, rows with
+    foreign tag columns, matcher tables): recorded RESULTS only, the inputs are regenerated from the seeded
+    generators.  Tag columns are random float32, so the bulky arrays go in as sha-256 digests (``tagdims.digest``:
+    equal iff bit-equal) next to the x / y / value columns, the scores and the counts in full.  Refused on the
+    munkres stand-in."""
+    if not real:
+        raise SystemExit("decode_dims: the real munkres package is required - the stand-in leaves tie-breaks unpinned")
+    sys.path.insert(0, REF)
+    import warnings
+    warnings.simplefilter("ignore")
+    from rtpe.third_party.group import HeatmapParser, Params, match_by_tag
+    from oracle import tagdims as T
+    out = {"real_package": np.array(int(real)), "dims": np.array(T.DIMS)}
+    # a. blobs
+    for c in T.blob_cases():
+        det_t, tag_t = T.blob_maps(c)
+        parser = T.blob_parser(c, HeatmapParser)
+        tk = parser.top_k(det_t, tag_t)
+        matched = parser.match(**tk)
+        adjusted = parser.adjust([m.copy() for m in matched], det_t)
+        ans, scores = parser.parse(det_t, tag_t, adjust=True, refine=True)
+        live = tk["val_k"] > 0.1
+        k = "a_" + c["name"]
+        out[k + "_meta"] = np.array([c["persons"], c["h"], c["w"], c["seed"], c["D"], int(c["tag_per_joint"])])
+        out[k + "_val_k"] = T.digest(tk["val_k"])
+        out[k + "_live"] = np.packbits(live)
+        out[k + "_loc_k"] = tk["loc_k"][live].astype(np.int16)
+        out[k + "_tag_k"] = T.digest(tk["tag_k"][live])
+        out[k + "_matched"] = T.digest(np.asarray(matched[0], np.float32))
+        out[k + "_adjusted"] = T.digest(np.asarray(adjusted[0], np.float32))
+        out[k + "_final"] = T.digest(np.asarray(ans[0], np.float32))
+        out[k + "_final_xyv"] = np.asarray(ans[0], np.float32)[:, :, :3]
+        out[k + "_scores"] = np.array(scores, np.float32)
+        print(k, "people", len(ans[0]), "live", int(live.sum()))
+
+    def refine(s):
+        parser = HeatmapParser(s["det"].shape[1], 30, 0.1, 1.0, True, False)
+        rows = s["rows"].copy()
+        with np.errstate(all="ignore"):
+            for p in range(len(rows)):
+                rows[p] = parser.refine(s["det"][s["pimg"][p]], s["tag"][s["pimg"][p]], rows[p].copy())
+        return rows
+
+    # b. the rounding boundary, and e. the same people with foreign tag columns
+    for D in T.BOUNDARY_DIMS:
+        s = T.boundary_scene(D)
+        rows = refine(s)
+        out["b_d%d" % D], out["b_d%d_xyv" % D] = T.digest(rows), rows[:, :, :3]
+        for kind in T.FOREIGN:
+            rows = refine(T.foreign_rows(s, kind))
+            out["e_d%d_%s" % (D, kind)], out["e_d%d_%s_xyv" % (D, kind)] = T.digest(rows), rows[:, :, :3]
+    # c. groups and people (of the 530: the digest, and the rows around and beyond the 512th person in full)
+    for name in T.PEOPLE_SCENES:
+        s = T.people_case(name)
+        rows = refine(s)
+        out["c_" + name] = T.digest(rows)
+        out["c_" + name + "_xyv"] = rows[-40:, :, :3] if len(rows) > 64 else rows[:, :, :3]
+        print("c", name, "people", len(rows), "filled", int((rows[:, :, 2] > 0).sum() - (s["rows"][:, :, 2] > 0).sum()))
+    # d. overflow
+    rows = refine(T.overflow_scene())
+    out["d"], out["d_xyv"] = T.digest(rows), rows[:, :, :3]
+    # f. matcher tables
+    for name, cfg, tag, loc, val in T.match_cases():
+        ans = np.asarray(match_by_tag((tag, loc, val), Params(T.F_J, *cfg)), np.float32)
+        out["f_" + name], out["f_" + name + "_shape"] = T.digest(ans), np.array(ans.shape)
+    path = os.path.join(OUT, "decode_dims.npz")
+    _write_npz(path, T.pack_results(out))
+    print("decode_dims:", len(out), "entries,", os.path.getsize(path), "bytes")
+
+
 def gen_munkres(real):
     """Munkres().compute of the real package on cost matrices as match_by_tag builds them (group.py:57-80):
     round(dist)*100 - val with many equal entries, padded to square with 1e10 when there are more candidates than
@@ -576,6 +664,8 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     real = _install_munkres()
+    if only == {"decode_dims"}:                  # needs the reference's group.py alone
+        return gen_decode_dims(real)
     if "base" in only:
         gen_base()
     ref = Ref()
@@ -587,6 +677,8 @@ def main():
         gen_munkres(real)
     if "match" in only:
         gen_match(real)
+    if "decode_dims" in only:
+        gen_decode_dims(real)
 
 
 if __name__ == "__main__":
