@@ -721,5 +721,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_mixed_aux.h"
 #include "rtpe_hip_frames.h"
 #include "rtpe_hip_oks.h"
+#include "rtpe_hip_distill.h"
 
 #endif /* RTPE_HIP_H */

@@ -299,6 +299,25 @@ _SIGS_OKS = {
                                 c_void_p]),
 }
 EXPORTS_OKS = tuple(_SIGS_OKS)          # those of include/rtpe_hip_oks.h, likewise
+# distillation targets and losses (include/rtpe_hip_distill.h): the ground-truth maps, the targets at the output grids,
+# the BCE loss's normalisation, and the loss values
+DISTILL_CHUNK, DISTILL_MAX_PATCH, DISTILL_MAX_BLOCKS, DISTILL_SCRATCH_BYTES, DISTILL_LOSS_BYTES = 64, 1024, 256, 16384, 40
+DISTILL_BCE, DISTILL_MSE = 0, 1
+_SIGS_DISTILL = {
+    "rtpe_gt_heatmaps": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                   c_double, c_void_p, c_void_p]),
+    "rtpe_distill_targets_scratch_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "rtpe_distill_targets": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_double, c_void_p, c_int32,
+                                       c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    "rtpe_distill_normalise": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rtpe_distill_loss": (c_int32, [c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                    c_int32, c_int32, c_int32, c_double, c_float, c_float, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+EXPORTS_DISTILL = tuple(_SIGS_DISTILL)  # those of include/rtpe_hip_distill.h, likewise
 _lib = None
 
 
@@ -324,7 +343,8 @@ def lib():
                 list(_SIGS_SHARED.items()) + list(_SIGS_PAIR.items()) + list(_SIGS_RECORDS.items()) + \
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
                 list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()) + \
-                list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()) + list(_SIGS_OKS.items()):
+                list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()) + list(_SIGS_OKS.items()) + \
+                list(_SIGS_DISTILL.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()
