@@ -126,6 +126,138 @@ def unpack_records(rec):
     return out
 
 
+class _Kind:
+    """One kind of batch: everything of a pipeline that depends on the test protocol, as the five steps that the loop
+    (``TeacherPipeline._stream_loop``) and the synchronous call (``TeacherPipeline._run``) take in this order.
+
+    ``begin(k, batch) -> (batch, hw)``: every host check of the batch and of its decode size(s), before any GPU work;
+    the batch as the forwards take it and the decode size resolved (default: the input size of the first tensor).
+    ``tensors(batch)``: the input tensors of the batch, first the one whose ``shape[0]`` counts the images.
+    ``open(batch, hw, decode) -> state | None``: what the decode needs before the forwards, through ``decode``.
+    ``forwards(k, batch, on_forward, state, decode) -> outs``: the forwards on the current stream -> the tuple of FRESH
+    output tensors the top-k reads.  ``topk(outs, hw, state) -> st``: phase 1 of the decode (on the decode stream) ->
+    the state that ``lowres_match`` / ``lowres_finish`` take.
+    ``decode(fn, *args, after=None, uses=())`` calls ``fn(*args)`` on the decode stream, behind the event ``after``,
+    with the tensors ``uses`` kept for that stream.  ``out_hw_of(k)``: the ``out_hw`` of batch k as the caller gave it."""
+
+    def __init__(self, pipe, out_hw_of=None):
+        self.pipe, self.out_hw_of = pipe, out_hw_of
+
+    def begin(self, k, batch):
+        hw = self.pipe._decode_hw(self.out_hw_of(k), batch)
+        return batch, hw if hw is not None else tuple(self.tensors(batch)[0].shape[2:])
+
+    def tensors(self, batch):
+        return [batch]
+
+    def open(self, batch, hw, decode):
+        return None
+
+
+class _TeacherPlain(_Kind):
+    """a (N,3,H,W) tensor through the teacher: one forward and ``lowres_topk``, or with ``flip_test`` the forwards of
+    the batch and of its mirror image (made and read on the same stream) and ``flip_topk`` of the pair;
+    ``on_forward(k, x)`` replaces each forward"""
+
+    def forwards(self, k, x, on_forward, state, decode):
+        p = self.pipe
+        fwd = on_forward if on_forward is not None else (lambda _k, t: p.model(t))
+        preds, refined = fwd(k, x)
+        if not p.flip_test:
+            return preds, refined
+        preds_f, refined_f = fwd(k, p.mirror(x))
+        return preds, refined, preds_f, refined_f
+
+    def topk(self, outs, hw, state):
+        p = self.pipe
+        if p.flip_test:
+            return p.parser.flip_topk(*outs, hw, p.flip_index)
+        preds, refined = outs
+        return p.parser.lowres_topk(refined, preds[:, NUM_HEATMAPS:], hw)
+
+
+class _TeacherMultiScale(_Kind):
+    """one (N,3,H_i,W_i) tensor per scale through the teacher (``scale_factors``): ``open`` makes the maps buffer
+    (``ms_begin``), every sub-batch of every scale (``forward_plan``) is forwarded [with its mirror image] and prepared
+    on the decode stream behind an event of its own (``ms_prep``), the top-k is ``ms_topk``; ``on_forward(k, x)``
+    replaces each sub-batch's forward.  The check of the per-scale inputs and the default decode size (the scale-1
+    input size) sit in ``open``, behind the check of the records, where callers have always met them."""
+
+    def begin(self, k, batch):
+        return batch, self.pipe._decode_hw(self.out_hw_of(k), batch)
+
+    def tensors(self, batch):
+        return list(batch) if isinstance(batch, (list, tuple)) else [batch]
+
+    def open(self, xs, out_hw, decode):
+        p = self.pipe
+        if not isinstance(xs, (list, tuple)) or len(xs) != len(p.scale_factors):
+            raise ValueError("TeacherPipeline: the multi-scale pipeline takes one input tensor per scale (%d)"
+                             % len(p.scale_factors))
+        for x in xs:
+            if x.dim() != 4 or x.shape[0] != xs[0].shape[0]:
+                raise ValueError("TeacherPipeline: the inputs of the scales must be (N,3,H,W) with the same N")
+        if out_hw is None and p.project2image:  # (without projection the parser takes the refined size of the largest)
+            out_hw = tuple(xs[p.scale_factors.index(1)].shape[2:])
+        return decode(p.parser.ms_begin, xs[0].shape[0], [(x.shape[2] // 2, x.shape[3] // 2) for x in xs], out_hw,
+                      p.scale_factors, p.flip_test, p.flip_index, p.device, p.ags, p.project2image)
+
+    def forwards(self, k, xs, on_forward, st, decode):
+        p = self.pipe
+        fwd = (lambda t: on_forward(k, t)) if on_forward is not None else p.model
+        for i, x in enumerate(xs):
+            for n0, n in forward_plan(x.shape[0], x.shape[2:], p.max_forward_pixels):
+                xb = x[n0:n0 + n]
+                outs = tuple(fwd(xb))
+                if p.flip_test:
+                    outs = outs + tuple(fwd(p.mirror(xb)))
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(p.device))
+                decode(p.parser.ms_prep, st, i, outs, n0, after=ev, uses=outs)
+        return ()                               # (the network outputs are consumed)
+
+    def topk(self, outs, hw, st):
+        return self.pipe.parser.ms_topk(st)
+
+
+class _StudentPlain(_Kind):
+    """a tensor ``x`` or a pair ``(x, alt)`` through a dual-head student: ``model(x[, alt=alt])`` and
+    ``lowres_topk_shared`` straight from ``det``; ``on_forward(k, batch)`` gets the batch as it was given"""
+
+    def tensors(self, batch):
+        return [batch] if torch.is_tensor(batch) else [t for t in batch if torch.is_tensor(t)]
+
+    def forwards(self, k, batch, on_forward, state, decode):
+        if on_forward is not None:
+            att, det = on_forward(k, batch)
+            return att, det
+        x, alt = (batch, None) if torch.is_tensor(batch) else batch
+        return self.pipe._att_det(self.pipe.model(x) if alt is None else self.pipe.model(x, alt=alt))
+
+    def topk(self, outs, hw, state):
+        det = outs[1].float()
+        J = det.shape[1] - 1
+        return self.pipe.parser.lowres_topk_shared(det[:, :J], det[:, J:], hw)
+
+
+class _StudentMixed(_StudentPlain):
+    """a mixed-size batch through a student's ``forward_mixed``: ``hw`` is the list of the images' sizes and the top-k
+    ``lowres_topk_mixed`` on the ``det`` canvas.  ``packed``: the batch is the ``(canvas, sizes[, alt_canvas])`` that
+    ``call_mixed`` / ``call_frames`` have packed and checked themselves"""
+
+    def __init__(self, pipe, packed=False):
+        self.pipe, self.packed = pipe, packed
+
+    def begin(self, k, batch):
+        return (batch, batch[1]) if self.packed else self.pipe._mixed_begin(batch)
+
+    def forwards(self, k, batch, on_forward, state, decode):
+        return self.pipe._mixed_forwards(k, batch, on_forward)
+
+    def topk(self, outs, sizes, state):
+        return self.pipe.parser.lowres_topk_mixed(outs[1].float(), sizes)
+
+
 class TeacherPipeline:
     """forward + decode for batches of pre-processed images on one GPU.
 
@@ -162,7 +294,10 @@ class TeacherPipeline:
     return, per batch, the (N, RECORD_FLOATS) float32 tensor that ``pack_records`` would build from the list result -
     written by a kernel behind adjust + refine (``HeatmapParser.lowres_match``), never read by the host; ``gather``
     takes it as it is.  ``xform`` (N, 6): per image the float64 matrix of ``transforms.final_preds_matrix``, applied
-    to (x, y) as ``get_final_preds`` does."""
+    to (x, y) as ``get_final_preds`` does.
+
+    All of this that depends on the protocol is a kind of batch (``_Kind``; ``_kind`` chooses it).  ``__call__`` is the
+    synchronous runner ``_run`` and ``stream()`` the loop ``_stream_loop`` on that kind; neither knows a protocol."""
 
     project2image = True    # (the default of every pipeline; an instance asked for the other protocol sets its own)
 
@@ -198,49 +333,20 @@ class TeacherPipeline:
             if not self.parser.tag_per_joint and not self.ags:
                 raise ValueError("TeacherPipeline: the multi-scale test needs a parser with tag_per_joint=True")
 
-    def _ms_inputs(self, images):
-        """the per-scale input tensors of one batch, checked: one (N,3,H_i,W_i) tensor per scale"""
-        xs = list(images) if isinstance(images, (list, tuple)) else None
-        if xs is None or len(xs) != len(self.scale_factors):
-            raise ValueError("TeacherPipeline: the multi-scale pipeline takes one input tensor per scale (%d)"
-                             % len(self.scale_factors))
-        for x in xs:
-            if x.dim() != 4 or x.shape[0] != xs[0].shape[0]:
-                raise ValueError("TeacherPipeline: the inputs of the scales must be (N,3,H,W) with the same N")
-        return xs
-
-    def _ms_begin(self, xs, out_hw):
-        """maps buffer of a multi-scale batch (current stream); the decode size defaults to the scale-1 input size"""
-        base = self.scale_factors.index(1)
-        refined_hw = [(x.shape[2] // 2, x.shape[3] // 2) for x in xs]
-        if not self.project2image:              # the decode grid is the refined size of the largest scale
-            return self.parser.ms_begin(xs[0].shape[0], refined_hw, out_hw, self.scale_factors, self.flip_test,
-                                        self.flip_index, self.device, False, False)
-        hw = tuple(out_hw) if out_hw is not None else tuple(xs[base].shape[2:])
-        return self.parser.ms_begin(xs[0].shape[0], refined_hw, hw, self.scale_factors, self.flip_test,
-                                    self.flip_index, self.device, self.ags)
-
-    def _ms_forwards(self, xs, fwd, on_outputs):
-        """every scale's forward (and that of the mirror image) in sub-batches, in scale order, on the current stream;
-        ``on_outputs(i, n0, outs)`` after each sub-batch"""
-        for i, x in enumerate(xs):
-            for n0, n in forward_plan(x.shape[0], x.shape[2:], self.max_forward_pixels):
-                xb = x[n0:n0 + n]
-                outs = tuple(fwd(xb))
-                if self.flip_test:
-                    outs = outs + tuple(fwd(self.mirror(xb)))
-                on_outputs(i, n0, outs)
+    def _kind(self, out_hw_of):
+        """the kind of this pipeline's batches (``_Kind``): the ONE place where the protocol switches choose - the flip
+        test is a switch inside the plain kind.  ``out_hw_of(k)``: the ``out_hw`` of batch k as the caller gave it"""
+        return (_TeacherMultiScale if self.scale_factors is not None else _TeacherPlain)(self, out_hw_of)
 
     def _decode_hw(self, out_hw, images):
         """``out_hw`` of one batch, checked before any GPU work: None, ``(h, w)`` or one ``(h, w)`` per image - the
         plain protocol only: the flip and multi-scale tests decode at the projection size, one per batch"""
         if out_hw is None:
             return None
-        n = (images[0] if isinstance(images, (list, tuple)) else images).shape[0]
-        sizes = per_image_sizes(out_hw, n, "TeacherPipeline")
+        x0 = images[0] if isinstance(images, (list, tuple)) else images
+        sizes = per_image_sizes(out_hw, x0.shape[0], "TeacherPipeline")
         if sizes is None:
             if not self.project2image:
-                x0 = images[0] if isinstance(images, (list, tuple)) else images
                 r0 = (x0.shape[2] // 2, x0.shape[3] // 2)
                 if (int(out_hw[0]), int(out_hw[1])) != r0:
                     raise ValueError("TeacherPipeline: without projection the decode grid is the refined size %s of "
@@ -261,37 +367,29 @@ class TeacherPipeline:
         from .inference import resize_combine
         return resize_combine(images, images.shape[2:], flip=True)
 
-    # The two steps of ``stream()`` that depend on the model (StudentPipeline overrides them); multi-scale batches take
-    # their own path through the loop.
-    def _stream_forwards(self, k, x, on_forward):
-        """the forwards of batch k on the current stream -> the tuple of FRESH output tensors the decode reads:
-        (preds, refined), followed by those of the mirror image with flip_test (the mirrored input is made and read on
-        the same stream)"""
-        fwd = on_forward if on_forward is not None else (lambda _k, t: self.model(t))
-        preds, refined = fwd(k, x)
-        if not self.flip_test:
-            return preds, refined
-        preds_f, refined_f = fwd(k, self.mirror(x))
-        return preds, refined, preds_f, refined_f
-
-    def _stream_topk(self, outs, hw):
-        """phase 1 of the decode from the outputs of ``_stream_forwards`` (on the decode stream) -> the state that
-        ``lowres_match`` / ``lowres_finish`` take"""
-        if self.flip_test:
-            return self.parser.flip_topk(*outs, hw, self.flip_index)
-        preds, refined = outs
-        return self.parser.lowres_topk(refined, preds[:, NUM_HEATMAPS:], hw)
-
-    def _records(self, images, image_ids, xform):
-        """the ``records`` argument of the parser for one batch, checked before any GPU work; None without ids"""
+    def _records(self, x, image_ids, xform):
+        """the ``records`` argument of the parser for one batch, checked before any GPU work; None without ids.
+        ``x``: the tensor whose ``shape[0]`` counts the images (``_Kind.tensors``)"""
         if image_ids is None:
             if xform is not None:
                 raise ValueError("TeacherPipeline: xform goes with image_ids (the device-resident records)")
             return None
-        x = images[0] if isinstance(images, (list, tuple)) else images
         return self.parser.check_records(x.shape[0], (image_ids, xform))
 
     @torch.no_grad()
+    def _run(self, kind, batch, image_ids=None, xform=None):
+        """one batch of any kind, start to finish on the current stream: the synchronous call of every pipeline.  The
+        steps of the kind in the order of the loop, each decode step called where it is asked for."""
+        def decode(fn, *args, after=None, uses=()):
+            return fn(*args)
+        batch, hw = kind.begin(0, batch)
+        records = self._records(kind.tensors(batch)[0], image_ids, xform)
+        state = kind.open(batch, hw, decode)
+        outs = kind.forwards(0, batch, None, state, decode)
+        st = kind.topk(outs, hw, state)
+        self.parser.lowres_match(st, records=records)
+        return self.parser.lowres_finish(st)
+
     def __call__(self, images, out_hw=None, image_ids=None, xform=None):
         """images (N,3,H,W) on the GPU -> list of (people, scores) per image;
         out_hw = decode resolution (original image size), default (H, W) - one ``(h, w)`` for the batch or a sequence
@@ -299,21 +397,7 @@ class TeacherPipeline:
         With ``scale_factors``: images = one tensor per scale (descending), out_hw default = the scale-1 (H, W).
         With ``image_ids`` (N ints; ``match_on="device"``) [and ``xform`` (N, 6) float64]: the (N, RECORD_FLOATS)
         record tensor on the device instead of the lists (class docstring)."""
-        out_hw = self._decode_hw(out_hw, images)
-        records = self._records(images, image_ids, xform)
-        if self.scale_factors is not None:
-            xs = self._ms_inputs(images)
-            st = self._ms_begin(xs, out_hw)
-            self._ms_forwards(xs, self.model, lambda i, n0, outs: self.parser.ms_prep(st, i, outs, n0))
-            self.parser.ms_topk(st)
-            self.parser.lowres_match(st, records=records)
-            return self.parser.lowres_finish(st)
-        preds, refined = self.model(images)
-        hw = out_hw if out_hw is not None else tuple(images.shape[2:])
-        if self.flip_test:
-            preds_f, refined_f = self.model(self.mirror(images))
-            return self.parser.parse_flip(preds, refined, preds_f, refined_f, hw, self.flip_index, records=records)
-        return self.parser.parse_lowres(refined, preds[:, NUM_HEATMAPS:], hw, records=records)
+        return self._run(self._kind(lambda k: out_hw), images, image_ids, xform)
 
     def stream(self, batches, out_hw=None, on_forward=None, decode_stream=None, in_flight=None, exclusive=None,
                records=None):
@@ -358,17 +442,14 @@ class TeacherPipeline:
         stream that was current when the loop started: that stream is made to wait - on the device - for the event
         behind the record kernel.  The loop body then holds no host wait on decode work: every buffer of such a batch
         is device memory handed out again in stream order, or a pinned block reused only when its upload is done."""
-        def begin(k, x):
-            return x, self._decode_hw(out_hw(k) if callable(out_hw) else out_hw, x)
-        return self._stream_loop(batches, begin, self._stream_forwards, self._stream_topk, on_forward, decode_stream,
-                                 in_flight, exclusive, records)
+        kind = self._kind(out_hw if callable(out_hw) else (lambda k: out_hw))
+        return self._stream_loop(batches, kind, on_forward, decode_stream, in_flight, exclusive, records)
 
-    def _stream_loop(self, batches, begin, forwards, topk, on_forward, decode_stream, in_flight, exclusive, records):
-        """the loop of ``stream()`` (its docstring), written once for every kind of batch.  A kind is three steps:
-        ``begin(k, batch) -> (batch, hw)`` - the batch as the forwards take it and its decode size(s), every refusal
-        before any GPU work; ``forwards(k, batch, on_forward)`` - the forwards on the current stream -> the tuple of
-        FRESH output tensors the decode reads; ``topk(outs, hw)`` - phase 1 of the decode -> the state that
-        ``lowres_match`` / ``lowres_finish`` take.  A generator."""
+    def _stream_loop(self, batches, kind, on_forward, decode_stream, in_flight, exclusive, records):
+        """the loop of ``stream()`` (its docstring), written once for every kind of batch: it knows streams, events,
+        workspace slots and the two-step delay, and nothing of any protocol - that is ``kind`` (``_Kind``: ``begin``,
+        ``tensors``, ``open``, ``forwards``, ``topk``), which gets ``on_decode_stream`` as its ``decode``.  The loop
+        keeps each batch's state and checked ``records`` together until its grouping.  A generator."""
         import os
         mode = decode_stream or os.environ.get("RTPE_DECODE_STREAM", "side")
         if mode not in ("side", "same"):
@@ -410,16 +491,8 @@ class TeacherPipeline:
 
         # ``on_forward`` must return FRESH output tensors for every batch (the plain forward does): the decode of
         # batch k runs on the side stream while F(k+1) runs on the main one, and nothing makes F(k+1) wait for it.
-        def run_forwards(k, x):
-            return forwards(k, x, on_forward)
-
-        ms = self.scale_factors is not None
-
-        def xs_of(x):
-            return x if ms or torch.is_tensor(x) else x[0]           # (a pair: StudentPipeline's (x, alt))
-
-        def match(st):
-            on_decode_stream(P.lowres_match, st, True, True, st.pop("records_arg", None))
+        def match(st, rec):
+            on_decode_stream(P.lowres_match, st, True, True, rec)
 
         def finish(st):
             out = P.lowres_finish(st)
@@ -428,31 +501,15 @@ class TeacherPipeline:
                 out.record_stream(main)             # allocated on the decode stream, used on the caller's
             return out
 
-        def run_ms_forwards(k, xs, st):
-            """every forward of multi-scale batch k on the current stream, the maps of each sub-batch prepared on the
-            decode stream behind an event; returns () (the network outputs are consumed)"""
-            fwd = (lambda t: on_forward(k, t)) if on_forward is not None else self.model
-
-            def prep(i, n0, outs):
-                ev = None
-                if side is not None:
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(self.device))
-                on_decode_stream(P.ms_prep, st, i, outs, n0, after=ev, uses=outs)
-            self._ms_forwards(xs, fwd, prep)
-            return ()
-
         try:
             with torch.no_grad():
                 for k, x in enumerate(batches):
-                    x, hw_k = begin(k, x)
+                    x, hw = kind.begin(k, x)
                     rec_k = None
                     if records is not None:
                         ids_k, xf_k = records(k)
-                        rec_k = self._records(xs_of(x), ids_k, xf_k)
-                    if ms:
-                        xs = self._ms_inputs(x)
-                        st_ms = on_decode_stream(self._ms_begin, xs, hw_k)
+                        rec_k = self._records(kind.tensors(x)[0], ids_k, xf_k)
+                    state = kind.open(x, hw, on_decode_stream)
                     fs = main
                     if fwd_streams is not None:
                         # forward k on stream k % n with workspace slot 1 + k % n; the input was produced on `main`
@@ -464,24 +521,20 @@ class TeacherPipeline:
                                 if other is not fs:
                                     fs.wait_stream(other)
                         after_alone = fs if alone else None
-                        # (a pair: StudentPipeline's (x, alt), or the (canvas, sizes) of a mixed batch)
-                        for t in (xs if ms else [x] if torch.is_tensor(x) else x):
-                            if torch.is_tensor(t):
-                                t.record_stream(fs)
+                        for t in kind.tensors(x):
+                            t.record_stream(fs)
                         # lanes off for THIS call only (a per-call flag of the ABI: nothing process-wide is touched,
                         # and nothing stays changed while the generator is suspended or if it is abandoned)
                         prev_slot = set_workspace_slot(1 + k % n_fwd)
                         prev_flags = set_forward_flags(0 if os.environ.get("RTPE_STREAM_LANES", "0") == "1" else FWD_NO_LANES)
                         try:
                             with torch.cuda.stream(fs):
-                                outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
+                                outs = kind.forwards(k, x, on_forward, state, on_decode_stream)
                         finally:
                             set_forward_flags(prev_flags)
                             set_workspace_slot(prev_slot)
                     else:
-                        outs = run_ms_forwards(k, xs, st_ms) if ms else run_forwards(k, x)
-                    hw = None if ms else hw_k if hw_k is not None else \
-                        tuple((x if torch.is_tensor(x) else x[0]).shape[2:])
+                        outs = kind.forwards(k, x, on_forward, state, on_decode_stream)
                     f_done = None
                     if side is not None or fs is not main:
                         f_done = torch.cuda.Event()
@@ -491,21 +544,17 @@ class TeacherPipeline:
                             for t in outs:
                                 t.record_stream(main)
                     if topk_done is not None:
-                        match(topk_done)                                # host matching overlaps F(k) on the GPU
-                    if ms:
-                        st = on_decode_stream(P.ms_topk, st_ms, after=f_done)
-                    else:
-                        st = on_decode_stream(topk, outs, hw, after=f_done, uses=outs)
-                    st["records_arg"] = rec_k
+                        match(*topk_done)                               # host matching overlaps F(k) on the GPU
+                    st = on_decode_stream(kind.topk, outs, hw, state, after=f_done, uses=outs)
                     if refine_done is not None:
-                        yield finish(refine_done)
-                    refine_done, topk_done = topk_done, st
+                        yield finish(refine_done[0])
+                    refine_done, topk_done = topk_done, (st, rec_k)
                 if topk_done is not None:
-                    match(topk_done)
+                    match(*topk_done)
                 if refine_done is not None:
-                    yield finish(refine_done)
+                    yield finish(refine_done[0])
                 if topk_done is not None:
-                    yield finish(topk_done)
+                    yield finish(topk_done[0])
         finally:
             # also when the consumer stops early or an exception propagates: whoever continues on the main stream
             # sees the decode as done
@@ -557,6 +606,9 @@ class StudentPipeline(TeacherPipeline):
     ``(images, alts)`` batches of ``stream_mixed`` and through ``mixed_batches(images, batch_size, alts=alts)``.
     ``stream()`` and ``__call__`` take one size per batch and refuse a mixed batch.
 
+    The class supplies its kinds of batch - ``_StudentPlain`` through ``_kind``, ``_StudentMixed`` in ``stream_mixed``
+    and ``call_mixed`` - and inherits the loop and the synchronous runner.
+
     There is no flip, multi-scale or AGS test protocol for the students: asking for one is a ValueError."""
 
     def __init__(self, model, parser=None, device=None, match_on=None, flip_test=False, scale_factors=None, ags=False,
@@ -585,18 +637,8 @@ class StudentPipeline(TeacherPipeline):
             raise TypeError("StudentPipeline: the model must return (att, det) with det (N, J + 1, h, w)")
         return out[0], out[1]
 
-    def _forward(self, batch):
-        x, alt = (batch, None) if torch.is_tensor(batch) else batch
-        return self._att_det(self.model(x) if alt is None else self.model(x, alt=alt))
-
-    def _stream_forwards(self, k, x, on_forward):
-        att, det = on_forward(k, x) if on_forward is not None else self._forward(x)
-        return att, det
-
-    def _stream_topk(self, outs, hw):
-        det = outs[1].float()
-        J = det.shape[1] - 1
-        return self.parser.lowres_topk_shared(det[:, :J], det[:, J:], hw)
+    def _kind(self, out_hw_of):
+        return _StudentPlain(self, out_hw_of)
 
     @staticmethod
     def _is_mixed(batch):
@@ -693,9 +735,6 @@ class StudentPipeline(TeacherPipeline):
                             % (tuple(det.shape), batch[0].shape[0]))
         return att, det
 
-    def _mixed_topk(self, outs, sizes):
-        return self.parser.lowres_topk_mixed(outs[1].float(), sizes)
-
     @torch.no_grad()
     def call_mixed(self, images, image_ids=None, decode="batch", alt=None):
         """images: a list of (3, h_n, w_n) tensors on the GPU, any sizes >= 32 [, ``alt``: the list of the same images in
@@ -728,10 +767,8 @@ class StudentPipeline(TeacherPipeline):
             raise ValueError("%s: %d image ids for %d images" % (who, len(image_ids), len(sizes)))
         batch = self._mixed_batch(canvas, sizes, alt_canvas())
         if decode == "batch":
-            records = None if image_ids is None else self.parser.check_records(len(sizes), (image_ids, None))
-            att, det = self._mixed_forwards(0, batch, None)
-            res = self.parser.parse_lowres_mixed(det.float(), sizes, records=records)
-            return res if records is None else [res[n:n + 1] for n in range(len(sizes))]
+            res = self._run(_StudentMixed(self, packed=True), batch, image_ids)
+            return res if image_ids is None else [res[n:n + 1] for n in range(len(sizes))]
         records = [None if image_ids is None else self.parser.check_records(1, ([image_ids[n]], None))
                    for n in range(len(sizes))]
         att, det = self._mixed_forwards(0, batch, None)
@@ -753,8 +790,7 @@ class StudentPipeline(TeacherPipeline):
         ``(att, det)``.
         Yields per batch what ``call_mixed`` returns for it, or with ``records`` (``k -> (image_ids, None)``; needs
         ``match_on="device"``) the (N, RECORD_FLOATS) record tensor of the batch."""
-        return self._stream_loop(batches, lambda k, x: self._mixed_begin(x), self._mixed_forwards, self._mixed_topk,
-                                 on_forward, decode_stream, in_flight, exclusive, records)
+        return self._stream_loop(batches, _StudentMixed(self), on_forward, decode_stream, in_flight, exclusive, records)
 
     @torch.no_grad()
     def call_frames(self, frames, alt_colorspace=None, image_ids=None, decode="batch"):
@@ -833,17 +869,13 @@ class StudentPipeline(TeacherPipeline):
             return [([images[i] for i in c], [alts[i] for i in c]) for c in cuts], restore
         return [[images[i] for i in c] for c in cuts], restore
 
-    @torch.no_grad()
     def __call__(self, images, out_hw=None, alt=None, image_ids=None, xform=None):
         """images (N,3,H,W) on the GPU [, alt (N,3,H,W)] -> list of (people, scores) for all N images; out_hw = the
         decode resolution (h, w), default (H, W); with ``image_ids`` [and ``xform``] the record tensor, as
         ``TeacherPipeline.__call__``"""
-        hw = self._decode_hw(out_hw, images)
-        records = self._records(images, image_ids, xform)
-        outs = self._forward(images if alt is None else (images, alt))
-        st = self._stream_topk(outs, hw if hw is not None else tuple(images.shape[2:]))
-        self.parser.lowres_match(st, records=records)
-        return self.parser.lowres_finish(st)
+        # (a mixed-size batch goes alone: it is refused as one, with or without ``alt``)
+        batch = images if alt is None or self._is_mixed(images) else (images, alt)
+        return self._run(self._kind(lambda k: out_hw), batch, image_ids, xform)
 
 
 def _collectives_on(force_collective=False):

@@ -161,6 +161,58 @@ def test_multi_scale_stream_equals_call(nat, teacher):
             _assert_same(a, b)
 
 
+# ---- the pipeline's multi-scale kind at its smallest shapes -----------------------------------------------------------
+SMALL_SCALES = (2, 1, 0.5)
+SMALL_HW = (64, 128)            # the scale-1 input; the inputs are 128 x 256, 64 x 128 and 32 x 64
+SMALL_BUDGET = 128 * 256        # the largest scale goes one image per forward (n0 = 1 occurs), the others whole
+
+
+def _small_batches(count, seed=300):
+    """``count`` batches of 2 images: one input tensor per scale, all different"""
+    return [[synth.make_images(2, int(SMALL_HW[0] * s), int(SMALL_HW[1] * s), seed=seed + 10 * k + i).to("cuda:0")
+             for i, s in enumerate(SMALL_SCALES)] for k in range(count)]
+
+
+def _small_pipe(teacher, **kw):
+    from rtpe.engine import TeacherPipeline
+    return TeacherPipeline(teacher, _parser(), device="cuda:0", flip_test=True, scale_factors=SMALL_SCALES,
+                           max_forward_pixels=SMALL_BUDGET, **kw)
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(ags=True), dict(ags="mean"), dict(project2image=False)],
+                         ids=["per_joint_tags", "ags", "ags_mean", "no_project"])
+def test_pipeline_call_equals_parse_multi_scale_of_whole_batch_forwards(nat, teacher, kw):
+    """``pipe(batch)`` against a reference that runs no line of rtpe/engine.py: the teacher forwarded here on every
+    scale's WHOLE batch and on its mirror image, then the parser's own entry.  The pipeline cuts the largest scale into
+    two forwards of one image; the forward is batch-invariant, so the bits are the same."""
+    from rtpe import inference
+    from rtpe.engine import forward_plan
+    pipe = _small_pipe(teacher, **kw)
+    batch = _small_batches(1)[0]
+    assert [forward_plan(2, x.shape[2:], SMALL_BUDGET) for x in batch] == [[(0, 1), (1, 1)], [(0, 2)], [(0, 2)]]
+    with torch.no_grad():
+        outs = [tuple(teacher(x)) + tuple(teacher(inference.resize_combine(x, x.shape[2:], flip=True))) for x in batch]
+    want = _parser().parse_multi_scale(outs, None if "project2image" in kw else SMALL_HW, SMALL_SCALES, True, **kw)
+    got = pipe(batch)
+    assert len(got) == len(want) == 2
+    for g, w in zip(got, want):
+        _assert_same(g, w)
+    assert sum(len(p) for p, _ in want) >= 1
+
+
+def test_multi_scale_stream_stopped_early_leaves_the_stream_synchronised(nat, teacher):
+    pipe = _small_pipe(teacher)
+    batches = _small_batches(4)
+    gen = pipe.stream(iter(batches), in_flight=2, decode_stream="side")
+    first = next(gen)
+    gen.close()                                                     # three batches were submitted, one was taken
+    again = pipe(batches[0])                                        # on the caller's stream, right behind the closed loop
+    assert len(first) == len(again) == 2
+    for a, b in zip(first, again):
+        _assert_same(a, b)
+    torch.cuda.synchronize()
+
+
 def test_multi_scale_argument_errors(nat):
     from rtpe.engine import TeacherPipeline
     from rtpe.third_party.group import HeatmapParser

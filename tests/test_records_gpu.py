@@ -10,7 +10,7 @@ import torch
 
 from oracle import synth
 from test_match_device_gpu import _ags_outputs, _blob_outputs, _parser, _scale_outputs
-from test_multiscale_decode_gpu import H, W
+from test_multiscale_decode_gpu import H, W, _small_batches, _small_pipe
 from test_records_host import COUNTS, J, P, _as_transform_preds, kernel_inputs, records_restated
 from test_student_pipeline_gpu import STREAM_HW, _StandIn, stream_case  # noqa: F401  (a fixture)
 
@@ -223,21 +223,40 @@ def test_teacher_pipeline_records_equal_the_list_path(nat, teacher, flip):
 def test_student_pipeline_records_equal_the_list_path(nat, stream_case):  # noqa: F811
     from rtpe.engine import StudentPipeline
     dets, xs, _ = stream_case
-    dets, xs, hws = dets[:2], xs[:2], STREAM_HW[:2]
-    ids = [[11, 12, 13, 14], [21, 22, 23, 24]]
-    xf = [None, _xform(4)]
+    dets, xs, hws = dets[:3], xs[:3], STREAM_HW[:3]             # (three: the two-step delay, both workspace slots)
+    ids = [[11, 12, 13, 14], [21, 22, 23, 24], [31, 32, 33, 34]]
+    xf = [None, _xform(4), None]
     got = list(StudentPipeline(_StandIn(dets), _parser(), DEV, match_on="device")
                .stream(iter(xs), out_hw=lambda k: hws[k], records=lambda k: (ids[k], xf[k])))
     lists = list(StudentPipeline(_StandIn(dets), _parser(), DEV, match_on="device")
                  .stream(iter(xs), out_hw=lambda k: hws[k]))
     call = StudentPipeline(_StandIn(dets), _parser(), DEV, match_on="device")
-    assert len(got) == len(lists) == 2
-    for k in range(2):
+    assert len(got) == len(lists) == 3
+    for k in range(3):
         want = _host_records(ids[k], lists[k], xf[k])
         _equal(got[k], want)
         _equal(call(xs[k], hws[k], image_ids=ids[k], xform=xf[k]), want)
     assert sum(_n(p) for r in lists for p, _ in r) >= 3
     assert not torch.equal(got[0][:, 1:], got[1][:, 1:])
+
+
+def test_multi_scale_pipeline_streamed_records_equal_those_of_the_call(nat, teacher):
+    """three batches (the two-step delay, both workspace slots), every batch with ids of its own: the record tensor
+    that the loop yields for batch k is the one ``pipe(batch_k, image_ids=ids_k)`` returns - ``records(k)`` reaches the
+    grouping of batch k, two steps after it was asked for"""
+    from rtpe.engine import RECORD_FLOATS
+    pipe = _small_pipe(teacher, match_on="device")
+    batches = _small_batches(3)
+    ids = [[100 * k + i for i in range(2)] for k in range(3)]
+    got = list(pipe.stream(iter(batches), in_flight=2, decode_stream="side", records=lambda k: (ids[k], None)))
+    assert len(got) == 3
+    for k in range(3):
+        assert tuple(got[k].shape) == (2, RECORD_FLOATS) and got[k][:, 0].tolist() == ids[k]
+        assert torch.equal(got[k], pipe(batches[k], image_ids=ids[k]))
+    assert sum(float(g[:, 1].sum()) for g in got) >= 3
+    for a in range(3):
+        for b in range(a + 1, 3):
+            assert not torch.equal(got[a][:, 1:], got[b][:, 1:])       # (column 0: the ids differ anyway)
 
 
 def test_records_are_refused_before_any_gpu_work(nat, teacher):

@@ -154,8 +154,33 @@ def test_student_pipeline_refuses_per_image_sizes_before_the_forward():
 
 
 def test_stream_loop_is_written_once():
-    """StudentPipeline overrides the two hooks of TeacherPipeline.stream, not the loop"""
+    """StudentPipeline supplies its kinds of batch, not the loop and not the synchronous runner; and neither of those
+    two names a protocol: what depends on one is a kind's"""
+    import inspect
+    from rtpe import engine
     from rtpe.engine import StudentPipeline, TeacherPipeline
     assert StudentPipeline.stream is TeacherPipeline.stream and StudentPipeline.gather is TeacherPipeline.gather
-    for hook in ("_stream_forwards", "_stream_topk"):
-        assert getattr(StudentPipeline, hook) is not getattr(TeacherPipeline, hook)
+    for written_once in ("_stream_loop", "_run"):
+        assert written_once not in vars(StudentPipeline) and written_once in vars(TeacherPipeline)
+    assert "_kind" in vars(StudentPipeline) and StudentPipeline._kind is not TeacherPipeline._kind
+
+    def pipe(cls, **kw):
+        p = cls.__new__(cls)                        # (the constructors move the model to a GPU)
+        p.flip_test, p.scale_factors = kw.get("flip_test", False), kw.get("scale_factors")
+        return p
+    teachers = {type(pipe(TeacherPipeline, **kw)._kind(None))
+                for kw in ({}, dict(flip_test=True), dict(scale_factors=(2, 1)), dict(flip_test=True, scale_factors=(1,)))}
+    assert teachers == {engine._TeacherPlain, engine._TeacherMultiScale}
+    students = {type(pipe(StudentPipeline)._kind(None)), engine._StudentMixed}
+    assert students == {engine._StudentPlain, engine._StudentMixed} and not students & teachers
+    for kind in teachers | students:
+        assert issubclass(kind, engine._Kind)
+        for step in ("begin", "tensors", "open", "forwards", "topk"):
+            assert callable(getattr(kind, step)), (kind, step)
+    # (the loop and the runner: docstring included; a ``__call__`` documents the protocols, its body names none)
+    sources = [inspect.getsource(fn) for fn in (TeacherPipeline._stream_loop, TeacherPipeline._run)]
+    sources += [inspect.getsource(fn).split('"""')[2] for fn in (TeacherPipeline.__call__, StudentPipeline.__call__)]
+    for source in sources:
+        assert "_kind" in source or "kind." in source
+        for word in ("scale_factors", "flip_test", "ms_", "is_tensor"):
+            assert word not in source, (source.splitlines()[0], word)

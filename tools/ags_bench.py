@@ -101,17 +101,15 @@ def main():
         """one batch at a time, every step alone: the device time of prep / top-k / adjust + refine, and the maps"""
         P = pipe.parser
         prep_ms, topk_ms, refine_ms, maps_bytes = [], [], [], 0
+        kind = pipe._kind(lambda k: (S, S))     # the pipeline's own steps, with a timing decode
         with torch.no_grad():
             for r in range(args.decode_reps + 1):
-                batch = batches[r % 2]
-                st = pipe._ms_begin(batch, (S, S))
-                maps_bytes = st["maps"].numel() * 4
                 pr = []
-
-                def on_outputs(i, n0, outs):
-                    pr.append(timed(P.ms_prep, st, i, outs, n0)[1])
-                pipe._ms_forwards(batch, model, on_outputs)
-                _, tk = timed(P.ms_topk, st)
+                batch, hw = kind.begin(r, batches[r % 2])
+                st = kind.open(batch, hw, lambda fn, *a: fn(*a))
+                maps_bytes = st["maps"].numel() * 4
+                kind.forwards(r, batch, None, st, lambda fn, *a, after=None, uses=(): pr.append(timed(fn, *a)[1]))
+                _, tk = timed(kind.topk, (), hw, st)
                 real, nat._lib = nat._lib, Timed()
                 spans.clear()
                 try:

@@ -133,17 +133,15 @@ def main():
                 return rc
             return call
     spans = []
+    kind = ms._kind(lambda k: (S, S))           # the pipeline's own steps, with a timing forward and a timing decode
     with torch.no_grad():
         for r in range(args.decode_reps + 1):
-            batch = xms[r % 2]
-            st = ms._ms_begin(batch, (S, S))
             fw, pr = [], []
-
-            def on_outputs(i, n0, outs):
-                pr.append(timed(P.ms_prep, st, i, outs, n0)[1])
-            fwd = (lambda t: _rec(timed(model, t), fw, tuple(t.shape[2:])))
-            ms._ms_forwards(batch, fwd, on_outputs)
-            _, tk = timed(P.ms_topk, st)
+            batch, hw = kind.begin(r, xms[r % 2])
+            st = kind.open(batch, hw, lambda fn, *a: fn(*a))
+            kind.forwards(r, batch, lambda k, t: _rec(timed(model, t), fw, tuple(t.shape[2:])), st,
+                          lambda fn, *a, after=None, uses=(): pr.append(timed(fn, *a)[1]))
+            _, tk = timed(kind.topk, (), hw, st)
             real, nat._lib = nat._lib, Timed()
             spans.clear()
             try:

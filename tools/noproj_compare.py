@@ -57,19 +57,16 @@ def compare(model, dev, B, S, scales, steps, warmup, repeats, decode_reps, parse
     def decode_times(pipe):
         P = pipe.parser
         prep_ms, topk_ms, refine_ms, maps_bytes = [], [], [], 0
+        # the pipeline's own steps, with a timing decode (parse_flip: no prep, it is part of the top-k entry)
+        kind = pipe._kind(lambda k: None)
         with torch.no_grad():
             for r in range(decode_reps + 1):
-                batch = data[r % 2]
                 pr = []
-                if pipe.scale_factors is None:          # parse_flip: the prep is part of the top-k entry
-                    x = batch[0]
-                    outs = tuple(model(x)) + tuple(model(pipe.mirror(x)))
-                    st, tk = timed(P.flip_topk, *outs, tuple(x.shape[2:]))
-                else:
-                    st = pipe._ms_begin(batch, None)
-                    pipe._ms_forwards(batch, model,
-                                      lambda i, n0, outs: pr.append(timed(P.ms_prep, st, i, outs, n0)[1]))
-                    _, tk = timed(P.ms_topk, st)
+                batch, hw = kind.begin(r, data[r % 2][0] if pipe.scale_factors is None else data[r % 2])
+                state = kind.open(batch, hw, lambda fn, *a: fn(*a))
+                outs = kind.forwards(r, batch, None, state,
+                                     lambda fn, *a, after=None, uses=(): pr.append(timed(fn, *a)[1]))
+                st, tk = timed(kind.topk, outs, hw, state)
                 maps_bytes = st["maps"].numel() * 4
                 real, nat._lib = nat._lib, Timed()
                 spans.clear()
