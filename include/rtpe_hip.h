@@ -722,5 +722,6 @@ int rtpe_adjust_refine_ms_ags_n(const float* maps, int32_t N, int32_t J, int32_t
 #include "rtpe_hip_frames.h"
 #include "rtpe_hip_oks.h"
 #include "rtpe_hip_distill.h"
+#include "rtpe_hip_distill_grad.h"
 
 #endif /* RTPE_HIP_H */

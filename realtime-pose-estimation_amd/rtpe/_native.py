@@ -318,6 +318,12 @@ _SIGS_DISTILL = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 EXPORTS_DISTILL = tuple(_SIGS_DISTILL)  # those of include/rtpe_hip_distill.h, likewise
+# the gradient of the distillation losses with respect to the student's output (include/rtpe_hip_distill_grad.h)
+_SIGS_DISTILL_GRAD = {
+    "rtpe_distill_loss_backward": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                             c_int32, c_int32, c_double, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+}
+EXPORTS_DISTILL_GRAD = tuple(_SIGS_DISTILL_GRAD)    # that of include/rtpe_hip_distill_grad.h, likewise
 _lib = None
 
 
@@ -344,7 +350,7 @@ def lib():
                 list(_SIGS_TAGMEAN.items()) + list(_SIGS_NOPROJ.items()) + list(_SIGS_ANYSIZE.items()) + \
                 list(_SIGS_MIXED.items()) + list(_SIGS_MIXDEC.items()) + list(_SIGS_TRACE.items()) + \
                 list(_SIGS_MIXAUX.items()) + list(_SIGS_FRAMES.items()) + list(_SIGS_OKS.items()) + \
-                list(_SIGS_DISTILL.items()):
+                list(_SIGS_DISTILL.items()) + list(_SIGS_DISTILL_GRAD.items()):
             fn = getattr(L, name)       # AttributeError if an export is missing
             fn.restype, fn.argtypes = res, args
         got = L.rtpe_version()

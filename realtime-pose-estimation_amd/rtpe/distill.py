@@ -5,7 +5,10 @@ loops, the teacher's maps resized to the image, three more resizes down to the s
 normalised loss - as launches of csrc/distill.hip (include/rtpe_hip_distill.h; the rules: DESIGN.md section 4,
 "Distillation targets and losses").  The teacher's maps come from the live teacher and never exist at image resolution.
 
-Forward values only: validation and monitoring.  No gradient flows through any function here.
+By default forward values only: validation and monitoring.  ``loss_values`` and ``distillation_losses`` take
+``differentiable=True`` for the gradient with respect to the student's output, one launch of csrc/distill_grad.hip
+(include/rtpe_hip_distill_grad.h; DESIGN.md section 4, "Distillation losses: backward"); no gradient flows to a target,
+a mask, or through any other function here.
 """
 import ctypes
 from collections import namedtuple
@@ -132,10 +135,23 @@ def _check_tensor(t, name, who, shape=None, ndim=4):
         raise ValueError("%s: %s must be contiguous" % (who, name))
 
 
+def _wants_grad(t):
+    return torch.is_grad_enabled() and bool(getattr(t, "requires_grad", False))
+
+
 def _no_grad(who, *tensors):
-    if torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in tensors):
+    if any(_wants_grad(t) for t in tensors):
         raise NotImplementedError("%s: forward value only - an input requires grad and grad mode is on; call it under "
-                                  "torch.no_grad() or detach the input" % who)
+                                  "torch.no_grad() or detach the input (the losses take differentiable=True for a "
+                                  "gradient with respect to student_pred)" % who)
+
+
+def _no_grad_but_pred(who, **named):
+    """differentiable=True: only ``student_pred`` gets a gradient"""
+    for name, t in named.items():
+        if _wants_grad(t):
+            raise NotImplementedError("%s: %s requires grad and grad mode is on; differentiable=True gives the gradient "
+                                      "with respect to student_pred only - detach %s" % (who, name, name))
 
 
 def _ptr(t):
@@ -226,12 +242,16 @@ def distillation_targets(table, image_hw, det_hw, att_hw=None, teacher=None, mas
     return DistillTargets(gt_out, teacher_out, mask_out, segm_out, minmax)
 
 
-def _check_loss_inputs(who, pred, teacher, gt, mask, alpha, background_factor, minmax=None, more_channels=True):
+def _check_loss_inputs(who, pred, teacher, gt, mask, alpha, background_factor, minmax=None, more_channels=True,
+                       differentiable=False):
     if not 0 <= alpha <= 1:
         raise ValueError("%s: alpha = %r outside [0, 1]" % (who, alpha))
     if not 0 <= background_factor <= 1:
         raise ValueError("%s: background_factor = %r outside [0, 1]" % (who, background_factor))
-    _no_grad(who, pred, teacher, gt, mask)
+    if differentiable:
+        _no_grad_but_pred(who, teacher_pred=teacher, gt=gt, mask=mask, minmax=minmax)
+    else:
+        _no_grad(who, pred, teacher, gt, mask)
     _check_tensor(gt, "gt", who)
     N, J, h, w = gt.shape
     if pred is not None:
@@ -273,16 +293,63 @@ def normalise(gt, teacher=None, mask=None, background_factor=1.0, minmax=None):
     return tuple(outs)
 
 
+class _LossWithGrad(torch.autograd.Function):
+    """the float32 loss vector of ``loss_values`` as a differentiable function of ``student_pred`` alone.  The forward
+    is the plain one with ``keep``; the backward is one launch of rtpe_distill_loss_backward on what the forward kept
+    ("Distillation losses: backward")."""
+
+    @staticmethod
+    def forward(ctx, pred, spec):
+        v = _loss_forward(pred, keep=True, **spec)
+        # the scalars only: the caller's tensors in `spec` must not live as long as the graph does
+        ctx.scalars = (KINDS[spec["kind"]], float(spec["alpha"]), float(spec["teacher_pos_weight"]),
+                       float(spec["gt_pos_weight"]))
+        ctx.save_for_backward(pred, v.gt, v.teacher, v.mask)       # (the version check sees a write in between)
+        ctx.mark_non_differentiable(*[t for t in (v.f64, v.gt, v.teacher, v.mask) if t is not None])
+        return v.f32, v.f64, v.gt, v.teacher, v.mask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_f32, *_):
+        pred, gt_n, teacher_n, mask_eff = ctx.saved_tensors
+        kind, alpha, pw_t, pw_g = ctx.scalars
+        # (a missing upstream gradient arrives as zeros: autograd materialises it)
+        grad_f32 = grad_f32.to(device=pred.device, dtype=torch.float32).contiguous()
+        grad_pred = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        N, J, h, w = gt_n.shape
+        with _native.on_device(pred):
+            _native.check(_native.lib().rtpe_distill_loss_backward(
+                kind, pred.data_ptr(), pred.shape[1], _ptr(teacher_n), gt_n.data_ptr(), _ptr(mask_eff),
+                N, J, h, w, alpha, pw_t, pw_g, grad_f32.data_ptr(), grad_pred.data_ptr(), _native.stream_ptr(pred.device)))
+        return grad_pred, None
+
+
 def loss_values(kind, pred, teacher, gt, alpha=0.5, mask=None, background_factor=1.0, teacher_pos_weight=1.0,
-                gt_pos_weight=1.0, unit=None, minmax=None, keep=False, more_channels=True, who="loss_values"):
-    """One masked distillation loss, forward value only: a ``LossValues`` whose ``f64`` and ``f32`` are device tensors
+                gt_pos_weight=1.0, unit=None, minmax=None, keep=False, more_channels=True, who="loss_values",
+                differentiable=False):
+    """One masked distillation loss: a ``LossValues`` whose ``f64`` and ``f32`` are device tensors
     ``[teacher_loss, gt_loss, alpha * teacher_loss + (1 - alpha) * gt_loss]``.  ``kind``: "bce" (with logits and a
     pos_weight per term) or "mse"; ``unit``: normalise the targets first (default: for "bce"); ``teacher`` None: its
-    loss is 0; ``keep``: also return the normalised targets and the effective mask.  The host waits for nothing."""
+    loss is 0; ``keep``: also return the normalised targets and the effective mask.  The host waits for nothing.
+
+    ``differentiable``: with a ``pred`` that requires grad while grad mode is on, ``f32`` (the same bits) carries a
+    gradient with respect to ``pred`` - and to nothing else; the normalised targets and the effective mask are kept for
+    the backward, three (N, J, h, w) float32 tensors at most.  Otherwise, and by default, forward value only."""
     if kind not in KINDS:
         raise ValueError("%s: kind = %r is neither 'bce' nor 'mse'" % (who, kind))
-    _check_loss_inputs(who, pred, teacher, gt, mask, alpha, background_factor, minmax, more_channels)
+    _check_loss_inputs(who, pred, teacher, gt, mask, alpha, background_factor, minmax, more_channels, differentiable)
     unit = kind == "bce" if unit is None else bool(unit)
+    spec = dict(kind=kind, teacher=teacher, gt=gt, alpha=alpha, mask=mask, background_factor=background_factor,
+                teacher_pos_weight=teacher_pos_weight, gt_pos_weight=gt_pos_weight, unit=unit, minmax=minmax)
+    if differentiable and _wants_grad(pred):
+        f32, f64, gt_n, teacher_n, mask_eff = _LossWithGrad.apply(pred, spec)
+        return LossValues(f64, f32, gt_n, teacher_n, mask_eff)
+    return _loss_forward(pred, keep=keep, **spec)
+
+
+def _loss_forward(pred, kind, teacher, gt, alpha, mask, background_factor, teacher_pos_weight, gt_pos_weight, unit, minmax,
+                  keep):
+    """the launches of ``loss_values`` on checked inputs"""
     N, J, h, w = gt.shape
     outs = [None, None, None]
     if keep:
@@ -301,21 +368,23 @@ def loss_values(kind, pred, teacher, gt, alpha=0.5, mask=None, background_factor
 
 
 def distillation_losses(att, det, targets, alpha=0.5, det_pos_weight=1, att_pos_weight=7, background_factor=1,
-                        kind="bce"):
+                        kind="bce", differentiable=False):
     """``(segmentation_loss, detection_loss)``, the two scalars of the reference's training step, as 0-d float32 device
     tensors: BCE-with-logits (pos_weight ``att_pos_weight``) of ``att`` against ``targets.segm``, and the keypoint-mining
     distillation loss of ``det`` (its channels [0, J), read in place) against ``targets.teacher`` and ``targets.gt``
     under ``targets.mask``.  ``kind="mse"`` is ``DistillationLossKeypointMining``.  A loss whose targets are absent is
-    None."""
+    None.  ``differentiable``: an ``att`` / ``det`` that requires grad gets its gradient from the scalar's
+    ``.backward()`` (a tag channel of ``det``: zeros); by default such an input is refused."""
     who = "distillation_losses"
     if not isinstance(targets, DistillTargets):
         raise TypeError("%s: targets must be what distillation_targets returned" % who)
     seg = None
     if att is not None and targets.segm is not None:
         seg = loss_values("bce", att, None, targets.segm, 0.0, None, 1.0, 1.0, att_pos_weight, unit=False,
-                          more_channels=False, who=who).f32[1]
+                          more_channels=False, who=who, differentiable=differentiable).f32[1]
     det_loss = None
     if det is not None and targets.gt is not None:
         det_loss = loss_values(kind, det, targets.teacher, targets.gt, alpha, targets.mask, background_factor,
-                               det_pos_weight, det_pos_weight, minmax=targets.minmax, who=who).f32[2]
+                               det_pos_weight, det_pos_weight, minmax=targets.minmax, who=who,
+                               differentiable=differentiable).f32[2]
     return seg, det_loss
